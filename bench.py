@@ -1,6 +1,6 @@
 """Headline benchmark: forward+backward Mpixels/s of the splat decoder path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -15,18 +15,27 @@ data-path collective (weak scaling: every rank gets its own 8 x 4 batch).
 on 127.0.0.1, one process per GPU, backend nccl (= RCCL) -- and rank 0 prints the line with `n_gpus: N`.
 
 Launch: one whole step is captured in a HIP graph and replayed (the step's GPU time, ~0.41 ms, is below what one
-Python thread needs to launch its kernels one by one); every 10th step of the timed region is the same step launched
-eagerly, with HIP events around the dominant kernel -- the roofline's live duration.  `--eager`: kernel-by-kernel
-launches for every step (host-bound).
+Python thread needs to launch its kernels one by one).  `--eager`: kernel-by-kernel launches for every step
+(host-bound).
 
-Timing: the `--steps` loop (EXACTLY K steps between barrier + synchronize on both sides, MAX over ranks) is run as
->= 25 back-to-back TRIALS adding up to >= 1 s of GPU work; `ms_per_step` / `value` are the MEDIAN trial and
-`trials_ms` keeps every trial (a single 10 ms sample was a 2 % lottery).
+Timing (default, lean): set-up, W warm-up steps, then EXACTLY K timed steps between barrier + synchronize on both
+sides (MAX over ranks); `ms_per_step` = that time / K, `value` = Mpixels/s over it.  Nothing else is measured.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+`--dump-outputs DIR`: after the timed steps, what the timed path computed in its last step -- the loss, the rendered
+colour and the gradient of every leaf the step differentiates -- is written as DIR/<name>.npy (float32; at most 64 MB
+in all, larger outputs as a fixed seeded sample of their elements).  The inputs are seeded: the same arguments give
+the same inputs in every run, so two builds can be compared output for output.
+
+`--full`: everything else as well.  The `--steps` loop is run as >= 25 back-to-back TRIALS adding up to >= 3 s of GPU
+work (`ms_per_step` / `value` are the MEDIAN trial and `trials_ms` keeps every trial), every 10th step of the timed
+region is the same step launched eagerly, with HIP events around the dominant kernel, and the line gets three more
+objects:
   roofline      dominant kernel's algorithmic HBM bytes / its HIP-event duration over the timed region, plus
                 `valu`: the same kernel's VALU-issue roofline (it is instruction-issue bound, not HBM bound)
   cpu_baseline  the CPU oracle (oracle/splat_ref.py, kind "port") timed on the host cores on a bounded sample
+  secondary     the other workloads (default C2 run on one GPU only), one child run of this script each
+
+Prints ONE JSON line on rank 0 (contract in the task statement).
 """
 from __future__ import annotations
 
@@ -112,6 +121,37 @@ def log(msg: str) -> None:
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_BYTES = 64 << 20       # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(dirname: str, outputs: list[dict]) -> None:
+    """--dump-outputs: the last step's outputs (one dict per micro-batch, scenes in order; rank 0's) as DIR/<name>.npy
+    in float32.  The micro-batches' tensors are joined along the scene axis, their losses summed (each is already
+    weighted by its share of the scenes).  If the arrays add up to more than DUMP_BYTES, every array keeps the same
+    fraction of its elements: a sample of flat indices in ascending order, seeded by the array's name, so the same in
+    every run."""
+    import zlib
+
+    import numpy as np
+    arrays = {}
+    for name in outputs[0]:
+        ts = [o[name] for o in outputs]
+        if any(t is None for t in ts):
+            continue
+        t = sum(ts) if name == "loss" else torch.cat(ts) if len(ts) > 1 else ts[0]
+        arrays[name] = t.detach().float().cpu().numpy()
+    keep = min(1.0, DUMP_BYTES / sum(a.nbytes for a in arrays.values()))
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        if keep < 1.0 and a.size > 1:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, max(1, int(a.size * keep)), replace=False))]
+        np.save(d / f"{name}.npy", a)
+    log(f"outputs of the last step written to {d}: {', '.join(sorted(arrays))}"
+        + (f" (each a seeded sample of {keep:.1%} of its elements)" if keep < 1.0 else ""))
+
+
 def cpu_baseline(args, batch_cpu) -> dict:
     """CPU oracle, fwd+bwd, same workload, bounded sample (first scene, one view at a time until ~`--cpu-budget`
     seconds are spent).  The oracle's per-tile tensors are small, so more than ~16 threads only adds
@@ -153,12 +193,19 @@ def parse_args(argv=None):
     ap.add_argument("--views", type=int, default=None, help="target views per scene (default: per --config)")
     ap.add_argument("--config", default="C2", choices=sorted(WORKLOADS))
     ap.add_argument("--s-mult", type=float, default=1.0)
-    ap.add_argument("--min-trials", type=int, default=25, help="back-to-back repetitions of the --steps loop")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything, not only the headline: repeated trials of the --steps loop, per-stage "
+                         "survey, roofline, CPU baseline and the secondary workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (loss, colour, "
+                         "gradients) as DIR/<name>.npy")
+    ap.add_argument("--min-trials", type=int, default=25,
+                    help="--full: back-to-back repetitions of the --steps loop")
     ap.add_argument("--min-seconds", type=float, default=3.0,
-                    help="GPU work the trials must add up to (3 s: longer than the sampling period of an outside GPU "
-                         "activity monitor)")
-    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU oracle time to spend")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: GPU work the trials must add up to (3 s: longer than the sampling period of an outside "
+                         "GPU activity monitor)")
+    ap.add_argument("--cpu-budget", type=float, default=20.0, help="--full: seconds of CPU oracle time to spend")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the `cpu_baseline` object")
     ap.add_argument("--exact", action="store_true",
                     help="size the pair buffer from a 16-byte device->host read-back in every step (one host sync per "
                          "step) instead of the default: a PairBudget planned from the first step, verified on the "
@@ -180,8 +227,9 @@ def parse_args(argv=None):
                          "below what one Python thread needs to launch it, ~0.45 ms: eager is host-bound now); "
                          "--exact and --allreduce imply it")
     ap.add_argument("--probe-every", type=int, default=10,
-                    help="graph mode: every n-th step of the timed region is an eager launch with HIP events around the "
-                         "dominant kernel (the roofline's live duration); 0: none (duration from the warm-up survey)")
+                    help="--full, graph mode: every n-th step of the timed region is an eager launch with HIP events "
+                         "around the dominant kernel (the roofline's live duration); 0: none (duration from the warm-up "
+                         "survey)")
     ap.add_argument("--streams", type=int, default=1,
                     help="N > 1: the per-GPU batch is split by scene into N micro-batches, each captured in its own HIP "
                          "graph and replayed on its own stream, so that the latency-bound stages of one micro-batch "
@@ -194,9 +242,9 @@ def parse_args(argv=None):
                          "-- on this library's drop-in `diff_gauss_pose` surface (eager; what a caller gets with zero "
                          "source changes).  batched (default): one `DecoderSplattingCUDA`-style call for all renders")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="default single-GPU C2 run only: skip the `secondary` object (BASELINE configs 3 and 5, the "
-                         "reference's real 2-view workload with and without SH band 4, the two-stream C2 step and the "
-                         "test_step-shaped decoder-call latency, each measured by a child run of this script)")
+                    help="--full, default single-GPU C2 run only: skip the `secondary` object (BASELINE configs 3 and 5, "
+                         "the reference's real 2-view workload with and without SH band 4, the two-stream C2 step and "
+                         "the test_step-shaped decoder-call latency, each measured by a child run of this script)")
     ap.add_argument("--eval-latency", action="store_true",
                     help="measure the LATENCY of one decoder call at the reference's test_step shape instead of the "
                          "training step: b = 1 scene of the 2-view model (131,072 Gaussians, 25 SH coefficients), v = 3 "
@@ -304,8 +352,8 @@ def run_secondary(args) -> dict:
                          "LOCAL_WORLD_SIZE", "ROLE_WORLD_SIZE", "TORCHELASTIC_RUN_ID")}
     for name, extra, env_extra in SECONDARY:
         cmd = [sys.executable, str(Path(__file__).resolve()), "--gpus", "1", "--steps", str(args.steps), "--warmup",
-               str(args.warmup), "--no-cpu-baseline", "--no-secondary", "--min-seconds", "1.0", "--min-trials", "5",
-               *extra]
+               str(args.warmup), "--full", "--no-cpu-baseline", "--no-secondary", "--min-seconds", "1.0", "--min-trials",
+               "5", *extra]
         t0 = time.perf_counter()
         try:
             # (a child starts with the affinity this process STARTED with and binds itself: its CPU baselines included)
@@ -625,6 +673,8 @@ def main():
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.dump_outputs and (args.eval_latency or args.rope):
+        sys.exit("bench.py: --dump-outputs writes the outputs of the decoder step, not of --eval-latency / --rope")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args, sys.argv[1:]))
 
@@ -792,6 +842,7 @@ def main():
                                          record=self.record)
                 loss = spf.mse_loss(color, b.target[sl], self.weight)
                 loss.backward(gradient=spf.unit_grad(dev))
+                self.keep_outputs(loss, color)
                 return loss
             if args.with_adapter:
                 ga = adapter_mod(L["means"], L["opacities"], L["raw"], with_covariances=False)
@@ -830,7 +881,15 @@ def main():
                 self.work = self.bucket.all_reduce(async_op=True, skip_single=False)
             else:
                 loss.backward(gradient=spf.unit_grad(dev))
+            self.keep_outputs(loss, color)
             return loss
+
+        def keep_outputs(self, loss, color):
+            """What a caller of the step receives (--dump-outputs).  A capture keeps the graph's own output tensors,
+            which every replay rewrites in place.  Detached: a step's autograd graph must not outlive it (its
+            AccumulateGrad nodes, made on the eager stream, would be reused by the capture on its own stream)."""
+            self.last = {"loss": loss.detach(), "color": color.detach(),
+                         **{f"grad_{n}": t.grad for n, t in self.leaves.items()}}
 
     per = S // args.streams
     if args.allreduce and S > 1:
@@ -862,7 +921,7 @@ def main():
     log(f"batch resident: {S} scenes x {V} views, G={G}, K={K}, {h}x{w}")
     step()
     torch.cuda.synchronize(dev)
-    if args.api == "module" and not args.exact:
+    if args.full and args.api == "module" and not args.exact:
         # the module replays its training calls from its own HIP graphs (a replay launches nothing from the host, so the
         # library's stage events see nothing): the per-stage survey is taken from eager launches first
         _lib.stage_timing_enable(True)
@@ -887,18 +946,23 @@ def main():
     max_pairs = micro[0].max_pairs
     run = step
     eager_survey = None
+    graph_outputs = None
     if args.graph:
-        # per-stage survey and dominant-kernel timing need eager launches (events are recorded at launch time,
-        # a replayed graph launches nothing from the host); with --streams the surveyed launches are one
-        # micro-batch's, timed exclusively (in the timed region the kernels of the streams overlap)
-        _lib.stage_timing_enable(True)
-        n_survey = max(args.warmup, 3)
-        for _ in range(n_survey):
-            micro[0].step()
-        torch.cuda.synchronize(dev)
-        # per STEP (a stage is one launch per chunk of the call, see spf_raster_chunks)
-        eager_survey = {k: (v[0] / n_survey, 1) for k, v in _lib.stage_times().items() if k != "rope2d" and v[1] > 0}
-        _lib.stage_timing_enable(False)
+        if args.full:
+            # per-stage survey and dominant-kernel timing need eager launches (events are recorded at launch time,
+            # a replayed graph launches nothing from the host); with --streams the surveyed launches are one
+            # micro-batch's, timed exclusively (in the timed region the kernels of the streams overlap)
+            _lib.stage_timing_enable(True)
+            n_survey = max(args.warmup, 3)
+            for _ in range(n_survey):
+                micro[0].step()
+            torch.cuda.synchronize(dev)
+            # per STEP (a stage is one launch per chunk of the call, see spf_raster_chunks)
+            eager_survey = {k: (v[0] / n_survey, 1) for k, v in _lib.stage_times().items() if k != "rope2d" and v[1] > 0}
+            _lib.stage_timing_enable(False)
+        else:
+            step()                  # the planned step once eagerly before it is captured
+            torch.cuda.synchronize(dev)
         streams = [torch.cuda.Stream(dev) for _ in micro] if len(micro) > 1 else [torch.cuda.current_stream(dev)]
         graphs = []
         try:
@@ -925,25 +989,28 @@ def main():
                     with torch.cuda.stream(st_):
                         g_.replay()
         if graphs:
+            graph_outputs = [m.last for m in micro]     # (the captured step's outputs: every replay rewrites them)
             log(f"step captured in {len(graphs)} HIP graph(s)")
-    # warm-up doubles as the per-stage survey (HIP events around every stage); the timed region then keeps
+    # --full: warm-up doubles as the per-stage survey (HIP events around every stage); the timed region then keeps
     # events only around the dominant kernel, so the headline number is not diluted by 14 event records/step
-    _lib.stage_timing_enable(True)
+    if args.full:
+        _lib.stage_timing_enable(True)
     for _ in range(max(args.warmup, 1)):
         run()
     torch.cuda.synchronize(dev)
-    survey = {k: v for k, v in _lib.stage_times().items() if k != "rope2d" and v[1] > 0}
-    if eager_survey is None and module_survey is not None:
-        eager_survey = module_survey
-    if eager_survey is not None:
-        survey = {k: (v[0] * max(args.warmup, 1), max(args.warmup, 1)) for k, v in eager_survey.items()}
-    dom = max(survey, key=lambda k: survey[k][0])
-    _lib.stage_timing_enable(False)
+    if args.full:
+        survey = {k: v for k, v in _lib.stage_times().items() if k != "rope2d" and v[1] > 0}
+        if eager_survey is None and module_survey is not None:
+            eager_survey = module_survey
+        if eager_survey is not None:
+            survey = {k: (v[0] * max(args.warmup, 1), max(args.warmup, 1)) for k, v in eager_survey.items()}
+        dom = max(survey, key=lambda k: survey[k][0])
+        _lib.stage_timing_enable(False)
 
-    # graph mode: every probe-th step is the same step launched eagerly (same kernels, same buffers' shapes, same
-    # stream) so that the library's HIP events around the dominant kernel exist inside the timed region; the host
+    # --full, graph mode: every probe-th step is the same step launched eagerly (same kernels, same buffers' shapes,
+    # same stream) so that the library's HIP events around the dominant kernel exist inside the timed region; the host
     # spends ~0.5 ms on it while the GPU still has the replays before it in its queue
-    probe = args.probe_every if (args.graph and len(micro) == 1 and args.probe_every > 0) else 0
+    probe = args.probe_every if (args.full and args.graph and len(micro) == 1 and args.probe_every > 0) else 0
 
     def trial() -> float:
         """EXACTLY --steps steps between barrier + synchronize on both sides."""
@@ -957,19 +1024,23 @@ def main():
         barrier()
         return time.perf_counter() - t0
 
-    # number of trials: >= --min-trials and >= --min-seconds of GPU work in total, agreed between the ranks from a
-    # first (untimed, discarded) trial
-    est = max_over_ranks([trial()])[0]
-    n_trials = int(min(2000, max(args.min_trials, math.ceil(args.min_seconds / max(est, 1e-6)))))
-    # events around every n-th launch of the dominant kernel only (an event pair leaves the GPU idle for ~11 us):
-    # at most ~1000 samples over the whole timed region (the library keeps 1024 per stage)
-    _lib.stage_timing_enable([dom])
-    n_event_launches = n_trials * (args.steps // probe if probe else args.steps)
-    _lib.stage_timing_sample_every(max(1 if probe else 4, math.ceil(n_event_launches / 1000)))
-    trials = [trial() for _ in range(n_trials)]
-    stages = _lib.stage_times()
-    _lib.stage_timing_enable(False)
-    _lib.stage_timing_sample_every(1)
+    if args.full:
+        # number of trials: >= --min-trials and >= --min-seconds of GPU work in total, agreed between the ranks from a
+        # first (untimed, discarded) trial
+        est = max_over_ranks([trial()])[0]
+        n_trials = int(min(2000, max(args.min_trials, math.ceil(args.min_seconds / max(est, 1e-6)))))
+        # events around every n-th launch of the dominant kernel only (an event pair leaves the GPU idle for ~11 us):
+        # at most ~1000 samples over the whole timed region (the library keeps 1024 per stage)
+        _lib.stage_timing_enable([dom])
+        n_event_launches = n_trials * (args.steps // probe if probe else args.steps)
+        _lib.stage_timing_sample_every(max(1 if probe else 4, math.ceil(n_event_launches / 1000)))
+        trials = [trial() for _ in range(n_trials)]
+        stages = _lib.stage_times()
+        _lib.stage_timing_enable(False)
+        _lib.stage_timing_sample_every(1)
+    else:
+        n_trials = 1
+        trials = [trial()]
     if max_pairs is not None and any(spf.plan_flags(m.record) != 0 for m in micro):
         raise RuntimeError(f"the planned pair budget did not hold (flags "
                            f"{[spf.plan_flags(m.record) for m in micro]}): results invalid")
@@ -977,40 +1048,44 @@ def main():
     dt = sorted(trials)[len(trials) // 2]                 # median trial
     log(f"timed region: {n_trials} trials x {args.steps} steps = {sum(trials):.3f} s; median trial {dt * 1e3:.3f} ms, "
         f"min {min(trials) * 1e3:.3f}, max {max(trials) * 1e3:.3f}")
+    if args.dump_outputs and rank == 0:
+        last_eager = run is step or bool(probe and (args.steps - 1) % probe == probe - 1)
+        dump_outputs(args.dump_outputs, [m.last for m in micro] if last_eager else graph_outputs)
 
     failed_children = []
     if rank == 0:
         P = h * w
         renders = world * S * V
         value = renders * P * args.steps / dt / 1e6
-        # the library runs a call as `chunks` launch chains of whole scenes on two streams (spf_raster_chunks): the
-        # dominant kernel is launched once per chunk, each launch processes 1/chunks of the step's units
-        lib_ = _lib.load()
-        chunk_stages = {"bin_pairs": 0, "tile_sort": 0, "render_fwd": 0, "render_bwd": 1, "project_bwd": 1}
-        chunks = lib_.spf_raster_chunks(S // len(micro), V, h, w, chunk_stages[dom]) if dom in chunk_stages else 1
-        dom_ms = (stages[dom][0] / stages[dom][1]) if stages[dom][1] else survey[dom][0] / survey[dom][1] / chunks
-        # (with --streams the surveyed launch is one micro-batch's: its share of the scenes and pairs)
-        # band-split harmonics evaluated to degree 3: the algorithm needs (and the kernels move) 16 of the 25 coefficients
-        K_model = 16 if (args.sh_split and os.environ.get("SPF_SH_BAND4", "0") != "1") else K
-        dom_bytes = stage_bytes(dom, S // len(micro), V, G, K_model, P, D_total // len(micro)) / chunks
-        if args.api == "per-view":          # one launch per render
-            dom_bytes = stage_bytes(dom, 1, 1, G, K_model, P, D_total // (S * V))
-        achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
-        traffic = None
         # the counter passes under profiles/ (tools/refresh_profiles.sh) were collected per config on its default batch
         default_workload = args.config if ((S, V) == WORKLOADS[args.config] and args.s_mult == 1.0 and
                                            not args.allreduce and len(micro) == 1 and args.api == "batched" and
                                            not args.sh_split and not args.with_adapter) else None
-        prof = ROOT / "profiles" / f"pmc_summary_{args.config}.json"
-        kernel = _lib.stage_kernel_name(dom)
-        if prof.exists() and default_workload:      # the PMC passes were collected on exactly this workload
-            try:
-                traffic = json.loads(prof.read_text()).get(kernel, {}).get("hbm_bytes_per_launch")
-            except Exception:
-                traffic = None
-        A = total_bytes(S, V, G, K_model, P, D_total)
-        if args.with_adapter and not args.raw_fused:   # + the adapter, both directions: raw in / parameters out, gradients in / dL/draw out
-            A += 2.0 * S * G * (2 * (7 + 3 * K) * 4 - (0 if K_model == K else 4 * 3 * (K - K_model)))
+        if args.full:
+            # the library runs a call as `chunks` launch chains of whole scenes on two streams (spf_raster_chunks): the
+            # dominant kernel is launched once per chunk, each launch processes 1/chunks of the step's units
+            lib_ = _lib.load()
+            chunk_stages = {"bin_pairs": 0, "tile_sort": 0, "render_fwd": 0, "render_bwd": 1, "project_bwd": 1}
+            chunks = lib_.spf_raster_chunks(S // len(micro), V, h, w, chunk_stages[dom]) if dom in chunk_stages else 1
+            dom_ms = (stages[dom][0] / stages[dom][1]) if stages[dom][1] else survey[dom][0] / survey[dom][1] / chunks
+            # (with --streams the surveyed launch is one micro-batch's: its share of the scenes and pairs)
+            # band-split harmonics evaluated to degree 3: the algorithm needs (and the kernels move) 16 of the 25 coefficients
+            K_model = 16 if (args.sh_split and os.environ.get("SPF_SH_BAND4", "0") != "1") else K
+            dom_bytes = stage_bytes(dom, S // len(micro), V, G, K_model, P, D_total // len(micro)) / chunks
+            if args.api == "per-view":          # one launch per render
+                dom_bytes = stage_bytes(dom, 1, 1, G, K_model, P, D_total // (S * V))
+            achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
+            traffic = None
+            prof = ROOT / "profiles" / f"pmc_summary_{args.config}.json"
+            kernel = _lib.stage_kernel_name(dom)
+            if prof.exists() and default_workload:      # the PMC passes were collected on exactly this workload
+                try:
+                    traffic = json.loads(prof.read_text()).get(kernel, {}).get("hbm_bytes_per_launch")
+                except Exception:
+                    traffic = None
+            A = total_bytes(S, V, G, K_model, P, D_total)
+            if args.with_adapter and not args.raw_fused:   # + the adapter, both directions: raw in / parameters out, gradients in / dL/draw out
+                A += 2.0 * S * G * (2 * (7 + 3 * K) * 4 - (0 if K_model == K else 4 * 3 * (K - K_model)))
         deg = int(K ** 0.5) - 1
         out = {
             "metric": "Mpixels/s fwd+bwd, 256x256 @ ~65k Gaussians" if args.config == "C2" else
@@ -1053,26 +1128,29 @@ def main():
                                                         "barrier+synchronize, max over ranks",
                        "seconds_timed": round(sum(trials), 4)},
             "trials_ms": [round(t * 1e3, 4) for t in trials],
-            "roofline": {"bound": "hbm", "kernel": kernel, "achieved": round(achieved, 2),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-                         "traffic": None if traffic is None else traffic / chunks, "launch_ms": round(dom_ms, 5),
-                         # the same fraction from the COUNTER bytes (FETCH_SIZE doubled + WRITE_SIZE per launch): where the
-                         # kernel moves fewer bytes than SURVEY.md 8(d)'s model charges (REF2V / REF10V: the projection
-                         # backward), this is the smaller, honest figure of what crosses HBM
-                         "frac_by_counters": None if traffic is None else
-                         round(traffic / chunks / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                         "launches_per_step": chunks,
-                         "algorithmic_bytes_per_launch": dom_bytes,
-                         "valu": valu_roofline(kernel, dom_ms, default_workload, chunks),
-                         "path_achieved_GBs": round(A / (dt / args.steps) / 1e9, 2),
-                         "path_frac_of_copy_ceiling": round(A / (dt / args.steps) / 1e9 / HBM_COPY_GBS, 5)},
-            "stage_ms_per_step_warmup": {k: round(v[0] / max(args.warmup, 1), 5) for k, v in survey.items()},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": kernel, "achieved": round(achieved, 2),
+                             "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+                             "traffic": None if traffic is None else traffic / chunks, "launch_ms": round(dom_ms, 5),
+                             # the same fraction from the COUNTER bytes (FETCH_SIZE doubled + WRITE_SIZE per launch): where the
+                             # kernel moves fewer bytes than SURVEY.md 8(d)'s model charges (REF2V / REF10V: the projection
+                             # backward), this is the smaller, honest figure of what crosses HBM
+                             "frac_by_counters": None if traffic is None else
+                             round(traffic / chunks / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                             "launches_per_step": chunks,
+                             "algorithmic_bytes_per_launch": dom_bytes,
+                             "valu": valu_roofline(kernel, dom_ms, default_workload, chunks),
+                             "path_achieved_GBs": round(A / (dt / args.steps) / 1e9, 2),
+                             "path_frac_of_copy_ceiling": round(A / (dt / args.steps) / 1e9 / HBM_COPY_GBS, 5)},
+                "stage_ms_per_step_warmup": {k: round(v[0] / max(args.warmup, 1), 5) for k, v in survey.items()},
+            })
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, batch_cpu)
         headline_defaults = (args.config == "C2" and default_workload == "C2" and not args.eager and not args.exact
                              and not args.torch_loss)
-        if world == 1 and headline_defaults and not args.no_secondary:
+        if args.full and world == 1 and headline_defaults and not args.no_secondary:
             torch.cuda.empty_cache()
             out["secondary"] = run_secondary(args)
             failed_children = out["secondary"].pop("_failed", [])

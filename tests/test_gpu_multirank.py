@@ -133,8 +133,8 @@ def test_world2_product_path_scene_shard_and_allreduce(hip_lib):
 def test_bench_gpus2_starts_two_ranks_itself(hip_lib):
     """`python bench.py --gpus 2` with WORLD_SIZE unset (it silently ran one rank)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--one-device", "--backend", "gloo",
-                        "--steps", "3", "--warmup", "1", "--min-trials", "3", "--min-seconds", "0", "--scenes", "2",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "2", "--one-device", "--backend",
+                        "gloo", "--steps", "3", "--warmup", "1", "--min-trials", "3", "--min-seconds", "0", "--scenes", "2",
                         "--views", "2", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env,
                        cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
@@ -144,8 +144,8 @@ def test_bench_gpus2_starts_two_ranks_itself(hip_lib):
     assert out["n_gpus"] == 2 and out["value"] > 0 and out["config"]["renders_per_step"] == 8
     assert out["timing"]["trials"] == 3 and len(out["trials_ms"]) == 3
     # and the view-split + all-reduce variant (BASELINE config 5's exchange step)
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--one-device", "--backend", "gloo",
-                        "--steps", "2", "--warmup", "1", "--min-trials", "2", "--min-seconds", "0", "--scenes", "1",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "2", "--one-device", "--backend",
+                        "gloo", "--steps", "2", "--warmup", "1", "--min-trials", "2", "--min-seconds", "0", "--scenes", "1",
                         "--views", "2", "--no-cpu-baseline", "--allreduce"], capture_output=True, text=True,
                        timeout=900, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
@@ -156,7 +156,7 @@ def test_bench_gpus2_starts_two_ranks_itself(hip_lib):
 def test_bench_streams2_micro_batches(hip_lib):
     """`bench.py --streams 2`: two micro-batches, two HIP graphs, two streams -- same renders per step, one JSON line."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--streams", "2", "--steps", "3", "--warmup", "2",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--streams", "2", "--steps", "3", "--warmup", "2",
                         "--min-trials", "3", "--min-seconds", "0", "--scenes", "2", "--views", "2", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
@@ -174,7 +174,7 @@ def test_rccl_preflight_world_of_one(hip_lib):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     base = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr",
-            "127.0.0.1", "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3",
+            "127.0.0.1", "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--full", "--gpus", "1", "--steps", "3",
             "--warmup", "1", "--min-trials", "2", "--min-seconds", "0", "--scenes", "2", "--views", "2",
             "--no-cpu-baseline"]
     for extra in ([], ["--allreduce"]):

@@ -1,7 +1,7 @@
 """development: why is `secondary.C2_module` (a child of the default bench run) slower than the same command on its own?"""
 import json, subprocess, sys, time, os
 import torch
-CMD = [sys.executable, "bench.py", "--gpus", "1", "--steps", "50", "--warmup", "10", "--no-cpu-baseline", "--no-secondary",
+CMD = [sys.executable, "bench.py", "--full", "--gpus", "1", "--steps", "50", "--warmup", "10", "--no-cpu-baseline", "--no-secondary",
        "--min-seconds", "1.0", "--min-trials", "5", "--config", "C2", "--api", "module"]
 def run(tag, **kw):
     r = subprocess.run(CMD, capture_output=True, text=True, **kw)

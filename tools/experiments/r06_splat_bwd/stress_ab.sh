@@ -1,4 +1,4 @@
-run() { python bench.py --config C2 --s-mult 10 --no-cpu-baseline --no-secondary --min-trials 10 2>/dev/null | python -c "
+run() { python bench.py --full --config C2 --s-mult 10 --no-cpu-baseline --no-secondary --min-trials 10 2>/dev/null | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); st=d['stage_ms_per_step_warmup']
 print('$1', d['value'], d['ms_per_step'], ' '.join(f'{k[:10]}={v*1e3:.1f}' for k, v in st.items()))"; }
 run default
