@@ -238,9 +238,6 @@ class PreparedStep {
         near_b_ = cam_.scale_invariant ? held_[2].view({dims_.S, dims_.V, 1, 1}) : Tensor();
     }
 
-    // [extrinsics, intrinsics, near, far, means, scales, rotations, opacities, shs, shs_high | None] of the current binding
-    std::vector<Tensor> held() const { return held_; }
-
     // camera + projection + bins, sort, compositing into fresh outputs; early: wait for the projection's verdict (the GPU
     // works on through the wait).  Returns (colour [S,V,3,H,W], depth [S,V,H,W] x near when scale-invariant, alpha, failed).
     std::tuple<Tensor, Tensor, Tensor, bool> forward(bool early) {
@@ -267,9 +264,12 @@ class PreparedStep {
         return {color, depth, alpha, failed};
     }
 
-    // the whole backward chain into fresh gradients: [means, opacities, scales, rotations, harmonics, harmonics_band4,
-    // extrinsics]; undefined = None.  g_depth is the gradient of the [S,V,H,W] depth output (x near is undone here).
-    std::vector<Tensor> backward(const OptTensor& g_image, const OptTensor& g_depth, const OptTensor& g_alpha) {
+    // the whole backward chain: [means, opacities, scales, rotations, harmonics, harmonics_band4, extrinsics]; undefined =
+    // None.  g_depth is the gradient of the [S,V,H,W] depth output (x near is undone here).  `out`, in the same order:
+    // buffers to write those gradients into (the caller's, e.g. views of a gradient bucket); an undefined entry, or no
+    // list, is a fresh tensor.
+    std::vector<Tensor> backward(const OptTensor& g_image, const OptTensor& g_depth, const OptTensor& g_alpha,
+                                 const std::optional<std::vector<OptTensor>>& out) {
         const c10::DeviceGuard guard(view_.device());
         void* const stream = c10::hip::getCurrentHIPStream(view_.device().index()).stream();
         auto grad_in = [&](const OptTensor& g) -> Tensor {
@@ -279,12 +279,22 @@ class PreparedStep {
         const Tensor gi = grad_in(g_image), ga = grad_in(g_alpha);
         Tensor gd = grad_in(g_depth);
         if (gd.defined() && near_b_.defined()) gd = gd * near_b_;
-        Tensor d_means = at::empty_like(held_[4]), d_opac = at::empty_like(held_[7]);
+        TORCH_CHECK(!out.has_value() || out->size() == 7, "PreparedStep.backward: `out` holds the 7 gradients or is None");
+        auto grad_out = [&](size_t i, const Tensor& like) -> Tensor {
+            const OptTensor* o = out.has_value() ? &(*out)[i] : nullptr;
+            if (!o || !o->has_value() || !(*o)->defined()) return at::empty_like(like);
+            const Tensor& t = **o;        // (the kernels write like.numel() floats through its pointer)
+            TORCH_CHECK(t.sizes() == like.sizes() && t.scalar_type() == at::kFloat && t.device() == like.device() &&
+                        t.is_contiguous(), "PreparedStep.backward: output buffer ", i, " is not a dense float32 tensor of ",
+                        like.sizes(), " on ", like.device());
+            return t;
+        };
+        Tensor d_means = grad_out(0, held_[4]), d_opac = grad_out(1, held_[7]);
         Tensor d_scales, d_rot, d_shs, d_high, d_ext;
-        if (want_scales_rot_) { d_scales = at::empty_like(held_[5]); d_rot = at::empty_like(held_[6]); }
-        if (want_shs_) d_shs = at::empty_like(held_[8]);
-        if (want_high_) d_high = at::empty_like(held_[9]);
-        if (want_view_) d_ext = at::empty_like(view_);
+        if (want_scales_rot_) { d_scales = grad_out(2, held_[5]); d_rot = grad_out(3, held_[6]); }
+        if (want_shs_) d_shs = grad_out(4, held_[8]);
+        if (want_high_) d_high = grad_out(5, held_[9]);
+        if (want_view_) d_ext = grad_out(6, view_);
         SpfGrads gr = gr_;
         gr.dL_dimage = ptr<const float>(gi); gr.dL_ddepth = ptr<const float>(gd); gr.dL_dalpha = ptr<const float>(ga);
         gr.dL_dmeans3D = ptr<float>(d_means); gr.dL_dopacities = ptr<float>(d_opac); gr.dL_dscales = ptr<float>(d_scales);
@@ -312,9 +322,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def(pybind11::init<uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, const Tensor&, int64_t, int64_t,
                             int64_t, const Tensor&, const Tensor&, const OptTensor&, bool, bool, bool, bool>())
         .def("bind", &PreparedStep::bind)
-        .def("held", &PreparedStep::held)
         .def("forward", &PreparedStep::forward)
-        .def("backward", &PreparedStep::backward);
+        .def("backward", &PreparedStep::backward, pybind11::arg("g_image"), pybind11::arg("g_depth"),
+             pybind11::arg("g_alpha"), pybind11::arg("out") = pybind11::none());
     m.doc() = "compiled host binding of libspfsplat_hip.so's rasterizer entry points (no arithmetic of its own)";
     m.def("abi_version", []() { return spf_abi_version(); });
     m.def("raster_forward", &raster_forward);

@@ -336,7 +336,6 @@ class _PreparedRender(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_color, g_depth, g_alpha, _g_radii):
-        from . import rasterizer as rz
         from .shard import active_bucket
         entry, token = ctx.entry, ctx.token
         step = entry.step
@@ -348,34 +347,9 @@ class _PreparedRender(torch.autograd.Function):
             step.raise_if_failed()                   # (one host sync, as in the eager path: a failed plan raises here)
         token.consumed = True                        # (a retained graph's second backward finds the same state: gen matches)
         need = ctx.needs_input_grad      # (entry, check, want_extra, extrinsics, means, scales, rotations, opacities, shs, shs_high)
-        if active_bucket() is None:
-            if step.fast is not None:
-                with rz._spf_errors():
-                    d_means, d_opac, d_scales, d_rot, d_shs, d_high, d_ext = step.fast.backward(g_color, g_depth, g_alpha)
-                return (None, None, None, d_ext if need[3] else None, d_means, d_scales, d_rot, d_opac, d_shs, d_high)
-            with torch.cuda.device(step.dev):
-                g = step.backward(g_color, g_depth, g_alpha)
-            return (None, None, None, g.get("extrinsics") if need[3] else None, g["means"], g.get("scales"),
-                    g.get("rotations"), g["opacities"], g.get("harmonics"), g.get("harmonics_band4"))
-        step.ensure_python_binding()
-        # a gradient bucket supplies the output buffers (shard.GradBucket): the general launcher, same state
-        if g_depth is not None:
-            g_depth = g_depth[:, :, None] * step.near_b if step.scale_invariant else g_depth[:, :, None]
-        res = rz._backward_impl(step.inputs, step.state, step.geom, (g_color, g_depth, g_alpha),
-                                dict(step.want, view="partials" if step.want["view"] else False), shs_high=step.shs_high)
-        d_means, d_scales, d_rot, d_opac, d_shs, _d_col, vpartial, _ = res[:8]
-        d_high = res[8] if len(res) > 8 else None
-        d_ext = None
-        if need[3] and vpartial is not None:
-            import ctypes as C
-
-            from . import _lib
-            d_ext = torch.empty_like(step.view)
-            with torch.cuda.device(step.dev):
-                _lib.check(step.lib.spf_camera_backward_partials(C.byref(step.cam_b), rz._ptr(vpartial), vpartial.shape[1],
-                                                                 rz._ptr(d_ext), rz._stream_ptr(step.dev)),
-                           "spf_camera_backward_partials")
-        return (None, None, None, d_ext, d_means, d_scales, d_rot, d_opac, d_shs, d_high)
+        # (a data-parallel rank's gradient bucket, shard.GradBucket, supplies the output buffers it holds)
+        d_means, d_opac, d_scales, d_rot, d_shs, d_high, d_ext = step.backward(g_color, g_depth, g_alpha, active_bucket())
+        return (None, None, None, d_ext if need[3] else None, d_means, d_scales, d_rot, d_opac, d_shs, d_high)
 
 
 class DecoderSplattingCUDA(Decoder[DecoderSplattingCUDACfg]):
@@ -616,11 +590,7 @@ class DecoderSplattingCUDA(Decoder[DecoderSplattingCUDACfg]):
             step = entry.step
             color, depth, alpha, failed = step.forward(check != "deferred")
             if failed:
-                self.last_call, self._last_call_borrowed = CallRecord(), False
-                with torch.no_grad():
-                    color, depth, alpha, radii = self._render_eager(gaussians, extrinsics, intrinsics, near, far,
-                                                                    image_shape, None, self.last_call)
-                return DecoderOutput(color, depth), alpha, radii
+                return self._render_exact_instead(gaussians, extrinsics, intrinsics, near, far, image_shape)
             radii = step.radii.view(alpha.shape[0], alpha.shape[1], -1).clone() if want_extra else None
             self.last_call, self._last_call_borrowed = entry.record, True
             return DecoderOutput(color, depth), (alpha if want_extra else None), radii
@@ -629,6 +599,19 @@ class DecoderSplattingCUDA(Decoder[DecoderSplattingCUDACfg]):
             gaussians.opacities, gaussians.harmonics, getattr(gaussians, "harmonics_band4", None))
         self.last_call, self._last_call_borrowed = entry.record, True
         return DecoderOutput(color, depth), alpha, radii
+
+    def _render_general(self, gaussians, extrinsics, intrinsics, near, far, image_shape):
+        """This call by the general launcher, under the current plan, into the decoder's own record."""
+        return self._render_eager(gaussians, extrinsics, intrinsics, near, far, image_shape, self.max_pairs,
+                                  self._own_record())
+
+    def _render_exact_instead(self, gaussians, extrinsics, intrinsics, near, far, image_shape):
+        """An evaluation call whose plan did not hold for THESE inputs (the planned outputs are NaN): the call once more
+        in exact mode, on a record of its own (the prepared step's or the graph's record must keep the counters its next
+        call is checked by)."""
+        self.last_call, self._last_call_borrowed = CallRecord(), False
+        with torch.no_grad():
+            return self._render_eager(gaussians, extrinsics, intrinsics, near, far, image_shape, None, self.last_call)
 
     def _render_eager(self, gaussians, extrinsics, intrinsics, near, far, image_shape, max_pairs, record):
         color, depth, alpha, radii = render_views(
@@ -641,7 +624,7 @@ class DecoderSplattingCUDA(Decoder[DecoderSplattingCUDACfg]):
         depth = depth[:, :, 0]                                   # "(b v) 1 h w -> b v h w"
         if self.make_scale_invariant:
             depth = depth * near[:, :, None, None]               # decoder_splatting_cuda.py:72-76
-        return color, depth, alpha, radii
+        return DecoderOutput(color, depth), alpha, radii
 
     def _eval_graph_key(self, tensors, image_shape):
         """None unless this call may run from a captured graph: planned, nothing will be differentiated, every tensor a
@@ -730,9 +713,7 @@ class DecoderSplattingCUDA(Decoder[DecoderSplattingCUDACfg]):
 
     def _render_planned(self, tensors, gaussians, extrinsics, intrinsics, near, far, image_shape, want_extra: bool):
         if getattr(gaussians, "raw", None) is not None:           # (fused adapter: the general launcher, planned or exact)
-            color, depth, alpha, radii = self._render_eager(gaussians, extrinsics, intrinsics, near, far, image_shape,
-                                                            self.max_pairs, self._own_record())
-            return DecoderOutput(color, depth), alpha, radii
+            return self._render_general(gaussians, extrinsics, intrinsics, near, far, image_shape)
         tkey = self._prepare_key(tensors, image_shape)
         trains = tkey is not None and any(tkey[1])
         if tkey is not None:
@@ -760,9 +741,7 @@ class DecoderSplattingCUDA(Decoder[DecoderSplattingCUDACfg]):
                                              image_shape)
         key = None if trains else self._eval_graph_key(tensors, image_shape)
         if key is None:
-            color, depth, alpha, radii = self._render_eager(gaussians, extrinsics, intrinsics, near, far, image_shape,
-                                                            self.max_pairs, self._own_record())
-            return DecoderOutput(color, depth), alpha, radii
+            return self._render_general(gaussians, extrinsics, intrinsics, near, far, image_shape)
         entry = self._graphs.get(key)
         if entry is None:
             first_sight = key not in self._graph_seen
@@ -772,15 +751,11 @@ class DecoderSplattingCUDA(Decoder[DecoderSplattingCUDACfg]):
                         self._graph_seen.clear()
                     self._graph_seen[key] = None
                 with torch.no_grad():
-                    color, depth, alpha, radii = self._render_eager(gaussians, extrinsics, intrinsics, near, far,
-                                                                    image_shape, self.max_pairs, self._own_record())
-                return DecoderOutput(color, depth), alpha, radii
+                    return self._render_general(gaussians, extrinsics, intrinsics, near, far, image_shape)
             entry = self._capture(key, gaussians, extrinsics, intrinsics, near, far, image_shape)
             if entry is None:        # the capture failed (another thread's HIP call, out of memory ...): this call eagerly
                 with torch.no_grad():
-                    color, depth, alpha, radii = self._render_eager(gaussians, extrinsics, intrinsics, near, far,
-                                                                    image_shape, self.max_pairs, self._own_record())
-                return DecoderOutput(color, depth), alpha, radii
+                    return self._render_general(gaussians, extrinsics, intrinsics, near, far, image_shape)
         else:
             self._graph_unused = 0
         verdict = entry.record.get("verdict_host") if entry.record.get("verdict_mirrored") else None
@@ -803,13 +778,7 @@ class DecoderSplattingCUDA(Decoder[DecoderSplattingCUDACfg]):
             else:
                 failed = plan_flags(entry.record) != 0
             if failed:
-                # the plan did not hold for THESE inputs (the graph's outputs are NaN): this call in exact mode instead
-                # (on a record of its own: the graph's record must keep the counters its next replay is checked by)
-                self.last_call, self._last_call_borrowed = CallRecord(), False
-                with torch.no_grad():
-                    color, depth, alpha, radii = self._render_eager(gaussians, extrinsics, intrinsics, near, far,
-                                                                    image_shape, None, self.last_call)
-                return DecoderOutput(color, depth), alpha, radii
+                return self._render_exact_instead(gaussians, extrinsics, intrinsics, near, far, image_shape)
         out = DecoderOutput(color.view(entry.color_shape), depth.view(entry.depth_shape))   # both contiguous, as ever
         return out, extra[0], extra[1]
 

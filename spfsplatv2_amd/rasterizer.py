@@ -677,11 +677,11 @@ class StaticStep:
     backward -> pose chain) PREPARED once: the state the chain keeps between its kernels (records, bins, tile bookkeeping,
     per-pixel state, gradient records, pose partials) lives at fixed addresses, the argument structs are built once, and
     what a call costs the host is a handful of C-ABI calls -- no allocation besides its OUTPUTS, no validation, no struct
-    marshalling.  Outputs (image | depth, alpha; every gradient) are fresh tensors per call: nothing a caller holds is
-    ever rewritten.  `DecoderSplattingCUDA` uses it for training calls whose SHAPES repeat (decoder.py): the inputs are
-    bound per call (`bind`: a dozen pointer fields; the step holds the tensors until the next `bind`, so they outlive
-    the backward) -- an encoder that hands over fresh tensors every step runs on the same prepared state as a loop over
-    static leaves.  Direct bins only.
+    marshalling.  Outputs (image | depth, alpha; every gradient) are fresh tensors per call -- gradients a gradient bucket
+    holds go into its views --: nothing a caller holds is ever rewritten.  `DecoderSplattingCUDA` uses it for training
+    calls whose SHAPES repeat (decoder.py): the inputs are bound per call (`bind`: a dozen pointer fields; the step holds
+    the tensors until the next `bind`, so they outlive the backward) -- an encoder that hands over fresh tensors every
+    step runs on the same prepared state as a loop over static leaves.  Direct bins only.
 
     `launch_project()` touches state only; `render()` and `backward()` write fresh outputs.  Between a
     `launch_project()` and the `backward()` that belongs to it the state must stay as it is: one step at a time.
@@ -725,8 +725,6 @@ class StaticStep:
         self.capacity, self.bin_cap, self.RT = rec_cap, bin_cap, R * T
         self.plan_info = (int(bin_cap), int(rec_cap), lib.spf_raster_pair_shards(S, G))
         self.bgx = _background(bg, S, V)
-        self.state = (self.rec, self.radii, self.rect, self.tiles, self.pairs, self.pair_idx, self.final_T, self.n_contrib)
-        self.geom = (S, V, G, K, sh_degree, H, W, 1.0, 2, (0xFFFFFFFF, bin_cap, rec_cap), layout, bool(sh_band4))
         self.scale_invariant = bool(scale_invariant)
         self.cam = _lib.SpfCamera(None, None, None, None, _ptr(self.view), _ptr(self.proj), _ptr(self.tanfov),
                                   _ptr(self.vscale), R, 1 if scale_invariant else 0, _ptr(self.view64))
@@ -741,7 +739,6 @@ class StaticStep:
         self.out = _lib.SpfOutputs(None, None, None)
         self.max_tile = int(plan.max_tile_list)
         # ---- backward ----
-        self.want = dict(want)
         self.gpair = None if forward_only else torch.empty((rec_cap, 10), **f32)     # (evaluation calls' steps: no backward)
         like = {"means": means3D, "opacities": opacities}
         if want["scales_rot"]:
@@ -752,7 +749,8 @@ class StaticStep:
                 like["harmonics_band4"] = shs_high
         if want["view"]:
             like["extrinsics"] = self.view
-        self.grad_shapes = {name: tuple(t.shape) for name, t in like.items()}
+        one = torch.empty((1,), **f32)   # each gradient's shape, dtype and device for GradBucket.take: one float expanded
+        self.grad_like = {name: one.expand(t.shape) for name, t in like.items()}
         self.vpartial = torch.empty((R, nblk, 12), **f32) if want["view"] else None
         self.gr = _lib.SpfGrads(None, None, None, _ptr(self.gpair), _ptr(self.vpartial))
         self.nblk = nblk
@@ -769,7 +767,7 @@ class StaticStep:
                     C.addressof(self.dims), C.addressof(self.inp), C.addressof(self.st), C.addressof(self.cam),
                     C.addressof(self.cam_b), C.addressof(self.gr), self.tiles, self.capacity, self.max_tile, nblk,
                     self.verdict, self.view, self.vpartial, bool(want["scales_rot"]), bool(want["shs"]),
-                    "harmonics_band4" in self.grad_shapes, bool(want["view"]))
+                    "harmonics_band4" in self.grad_like, bool(want["view"]))
         self.bind(extrinsics, intrinsics, near, far, means3D, scales, rotations, opacities, shs, shs_high)
 
     def bind(self, extrinsics, intrinsics, near, far, means3D, scales, rotations, opacities, shs, shs_high) -> None:
@@ -778,18 +776,7 @@ class StaticStep:
         aliases: an encoder's autograd graph is not kept alive through them)."""
         if self.fast is not None:
             self.fast.bind(extrinsics, intrinsics, near, far, means3D, scales, rotations, opacities, shs, shs_high)
-            self._python_bound = False
             return
-        self._bind_python(extrinsics, intrinsics, near, far, means3D, scales, rotations, opacities, shs, shs_high)
-
-    def ensure_python_binding(self) -> None:
-        """The Python-side fields of the current binding (`inputs`, `shs_high`, `near_b`, the ctypes structs): what the
-        compiled step does not need and a gradient bucket's general backward does."""
-        if not self._python_bound:
-            self._bind_python(*self.fast.held())
-
-    def _bind_python(self, extrinsics, intrinsics, near, far, means3D, scales, rotations, opacities, shs, shs_high) -> None:
-        self._python_bound = True
         (extrinsics, intrinsics, near, far, means3D, scales, rotations, opacities, shs) = (
             t if t.grad_fn is None else t.detach()
             for t in (extrinsics, intrinsics, near, far, means3D, scales, rotations, opacities, shs))
@@ -802,11 +789,8 @@ class StaticStep:
                                                                  rotations.data_ptr(), opacities.data_ptr())
         inp.shs, inp.shs_high = shs.data_ptr(), _ptr(shs_high)
         self.cam_b.near = cam.near
-        self.inputs = (means3D, scales, rotations, opacities, shs, None, self.view, self.proj, self.tanfov, self.bgx,
-                       self.vscale, self.view64)
-        self.shs_high, self.near = shs_high, near
         self.near_b = near[:, :, None, None] if self.scale_invariant else None   # depth x near (decoder_splatting_cuda.py:72-76)
-        self._held = (extrinsics, intrinsics, far)
+        self._held = (extrinsics, intrinsics, near, far, means3D, scales, rotations, opacities, shs, shs_high)
 
     def forward(self, early: bool):
         """The forward chain on the current binding: (colour, depth, alpha, failed).  `early`: wait for the projection
@@ -852,25 +836,35 @@ class StaticStep:
             depth.mul_(self.near_b)
         return color, depth, alpha
 
-    def backward(self, g_image, g_depth, g_alpha) -> dict:
-        """The whole backward chain into fresh gradient tensors; returns {name: gradient} (`extrinsics`: the poses')."""
+    GRADS = ("means", "opacities", "scales", "rotations", "harmonics", "harmonics_band4", "extrinsics")
+
+    def backward(self, g_image, g_depth, g_alpha, bucket=None) -> list:
+        """The whole backward chain on the current binding: the gradients of `GRADS` (`extrinsics`: the poses'), None
+        where none was asked for.  `g_depth` is the gradient of the [S,V,H,W] depth output (x near is undone here).
+        Gradients are fresh tensors; with a gradient bucket (shard.GradBucket) those it holds are written into its views."""
+        taken = {} if bucket is None else {name: bucket.take(name, like) for name, like in self.grad_like.items()}
+        if self.fast is not None:
+            with _spf_errors():
+                return self.fast.backward(g_image, g_depth, g_alpha, [taken.get(n) for n in self.GRADS] if taken else None)
         c = lambda g: None if g is None else g.contiguous().float()
         g_image, g_alpha = c(g_image), c(g_alpha)
         if g_depth is not None:                          # (the node's depth output is [S,V,H,W], already x near)
             g_depth = c(g_depth * self.near_b if self.scale_invariant else g_depth)
-        g = {name: torch.empty(shape, **self.f32) for name, shape in self.grad_shapes.items()}
+        g = {name: torch.empty(like.shape, **self.f32) if taken.get(name) is None else taken[name]
+             for name, like in self.grad_like.items()}
         gr = self.gr
         gr.dL_dimage, gr.dL_ddepth, gr.dL_dalpha = _ptr(g_image), _ptr(g_depth), _ptr(g_alpha)
         gr.dL_dmeans3D, gr.dL_dopacities = g["means"].data_ptr(), g["opacities"].data_ptr()
         gr.dL_dscales, gr.dL_drotations = _ptr(g.get("scales")), _ptr(g.get("rotations"))
         gr.dL_dshs, gr.dL_dshs_high = _ptr(g.get("harmonics")), _ptr(g.get("harmonics_band4"))
         lib, stream = self.lib, _stream_ptr(self.dev)
-        _lib.check(lib.spf_raster_backward(C.byref(self.dims), C.byref(self.inp), C.byref(self.st), C.byref(gr),
-                                           self.capacity, 0xFFFFFFFF, stream), "spf_raster_backward")
-        if "extrinsics" in g:
-            _lib.check(lib.spf_camera_backward_partials(C.byref(self.cam_b), _ptr(self.vpartial), self.nblk,
-                                                        _ptr(g["extrinsics"]), stream), "spf_camera_backward_partials")
-        return g
+        with torch.cuda.device(self.dev):
+            _lib.check(lib.spf_raster_backward(C.byref(self.dims), C.byref(self.inp), C.byref(self.st), C.byref(gr),
+                                               self.capacity, 0xFFFFFFFF, stream), "spf_raster_backward")
+            if "extrinsics" in g:
+                _lib.check(lib.spf_camera_backward_partials(C.byref(self.cam_b), _ptr(self.vpartial), self.nblk,
+                                                            _ptr(g["extrinsics"]), stream), "spf_camera_backward_partials")
+        return [g.get(name) for name in self.GRADS]
 
     def raise_if_failed(self) -> None:
         _raise_if_plan_failed(self.tiles[4 * self.RT + 1:], self.capacity, self.plan_info)

@@ -30,7 +30,8 @@ class GradBucket:
     [S,G,3], rotations [S,G,4], opacities [S,G], harmonics (any shape) -- as contiguous views, in this order.
 
     With ``with bucket:`` around the backward pass the rasterizer's backward writes its results straight into those
-    views (rasterizer._backward_impl takes its output buffers from the active bucket instead of allocating them), the
+    views (rasterizer._backward_impl and a prepared step's backward, rasterizer.StaticStep.backward, take their output
+    buffers from the active bucket instead of allocating them), the
     leaves' ``.grad`` alias the bucket, and ``bucket.all_reduce()`` sums the whole parameter set across the ranks with
     ONE collective on the flat buffer: no ``torch.cat`` into a fresh bucket, no copy back (what
     ``allreduce_gaussian_grads`` costs: two extra passes over G*(11+3K)*4 bytes).  ``async_op=True`` returns the

@@ -426,25 +426,29 @@ def test_evaluation_calls_whose_tensors_move_run_on_a_forward_only_step(hip_lib,
 
 
 def test_prepared_step_backward_into_a_gradient_bucket(hip_lib, step_binding):
-    """Data-parallel ranks run the backward inside `with shard.GradBucket(...)`: the prepared step then hands the general
-    backward its state and the CURRENT binding's inputs (also when the forward ran in the compiled step) -- gradients
-    land in the bucket's views, equal to the unbucketed ones bit for bit."""
+    """Data-parallel ranks run the backward inside `with shard.GradBucket(...)`: the prepared step's own backward then
+    writes the gradients the bucket holds into its views (also when the step runs in the compiled binding) and returns
+    what it returns outside a bucket -- every leaf's gradient, the poses' and a depth term's included, bit for bit.
+    (S == V: the shape where a gradient of depth x near broadcast wrongly.)"""
     from spfsplatv2_amd import shard
     spf, b, leaves, g, plan, step, w = _train_setup(seed=41)
+    assert b.extrinsics.shape[:2] == (2, 2)
     d = util.product_decoder(max_pairs=plan)
-    step(d); want = step(d)                                              # second call: prepared
+    step(d); want = step(d, with_depth=True)                             # second call: prepared
     assert len(d._prepared_steps) == 1
     for t in leaves.values():
         t.grad = None
     out = d.forward(g, leaves["extrinsics"], b.intrinsics, b.near, b.far, b.image_shape)
-    loss = (out.color * w).sum()
+    loss = (out.color * w).sum() + 0.1 * (out.depth * w[:, :, 0]).sum()
     bucket = shard.GradBucket(*(leaves[n] for n in ("means", "scales", "rotations", "opacities", "harmonics")))
     with bucket:
         loss.backward()
     lo, hi = bucket.flat.data_ptr(), bucket.flat.data_ptr() + 4 * bucket.flat.numel()
     for n in ("means", "scales", "rotations", "opacities", "harmonics"):
-        assert lo <= leaves[n].grad.data_ptr() < hi and torch.equal(leaves[n].grad, want[2][n]), n
-    assert torch.equal(leaves["extrinsics"].grad, want[2]["extrinsics"]) and torch.equal(out.color, want[0].color)
+        assert lo <= leaves[n].grad.data_ptr() < hi, n
+    assert all(torch.equal(leaves[n].grad, want[2][n]) for n in util.GRAD_NAMES), \
+        [n for n in util.GRAD_NAMES if not torch.equal(leaves[n].grad, want[2][n])]
+    assert torch.equal(out.color, want[0].color) and torch.equal(out.depth, want[0].depth)
 
 
 def test_training_graph_with_a_plan_that_fails_is_rerun_exactly(hip_lib, step_binding):
