@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define SPF_ABI_VERSION 6
+#define SPF_ABI_VERSION 7
 
 #define SPF_OK 0
 #define SPF_E_INVALID (-1)   /* bad argument (null pointer, size, unsupported degree ...) */
@@ -298,6 +298,35 @@ int spf_raster_forward_render(const SpfDims* d, const SpfInputs* in, SpfState* s
  * as in spf_raster_forward_render. */
 int spf_raster_backward(const SpfDims* d, const SpfInputs* in, const SpfState* st,
                         const SpfGrads* g, uint64_t capacity, uint32_t dense_tiles_hint, void* stream);
+
+/* Precomputed 3-D covariances (the public rasterizer's cov3Ds_precomp) in place of the scale/rotation pair, forward
+ * and backward.  Everything else -- dims, inputs, state, outputs, upstream gradients, spf_raster_forward_render between
+ * the two -- is what the calls above take.
+ *   cov3D [S,G,6]       the upper triangle of each Gaussian's Sigma in 3DGS order (xx, xy, xz, yy, yz, zz); the lower
+ *                       triangle is implied by symmetry.  Used as given: SpfDims.scale_modifier does NOT apply (as in the
+ *                       public 3DGS rasterizer); SpfInputs.view_scale does, render (s, v) sees Sigma * k^2 with
+ *                       k = view_scale[s, v] (the reference's scale-invariant rescale, cuda_splatting.py:70).
+ *   dL_dcov3D [S,G,6]   or NULL (enable_cov_grad off: no covariance gradient is produced).  Diagonal entry i receives
+ *                       G_ii, off-diagonal entry (i, j) G_ij + G_ji -- G the gradient w.r.t. the full 3x3 matrix, since
+ *                       the stored value fills both symmetric slots (autograd through Sigma = sym(cov6); 3DGS's
+ *                       computeCov2DCUDA backward).
+ *   Input domain        covariances are positive semidefinite.  The projection kernels factor Sigma = L L^T once per
+ *                       Gaussian (Cholesky in float64, rounded to float32) and use L where the scale/rotation path uses
+ *                       R diag(s): a rank-deficient Sigma (a flat splat, one zero eigenvalue) renders exactly.  A
+ *                       non-positive pivot is taken as zero together with the rest of its column, so an INDEFINITE Sigma
+ *                       neither faults nor produces NaN: it renders as L L^T of that clamped factor, and dL_dcov3D is the
+ *                       gradient at that matrix.
+ *   Rejected (SPF_E_INVALID, before any launch): in->scales or in->rotations non-NULL, g->dL_dscales or
+ *                       g->dL_drotations non-NULL, sh_layout 2 (band split) or 3 (raw rows), cov3D NULL.
+ *   spf_raster_forward_project_cov3d: `cleared_bytes` as in spf_raster_forward_project_prepared; 0 = the call clears
+ *                       for itself, like spf_raster_forward_project.
+ *   spf_raster_backward_cov3d: spf_raster_backward with the covariance gradient; the call always runs as one launch
+ *                       chain (SPF_CHUNKS does not split it). */
+int spf_raster_forward_project_cov3d(const SpfDims* d, const SpfInputs* in, const float* cov3D /* [S,G,6] */,
+                                     SpfState* st, uint64_t cleared_bytes, void* stream);
+int spf_raster_backward_cov3d(const SpfDims* d, const SpfInputs* in, const float* cov3D, const SpfState* st,
+                              const SpfGrads* g, float* dL_dcov3D /* [S,G,6] or NULL */, uint64_t capacity,
+                              uint32_t dense_tiles_hint, void* stream);
 
 /* Fused Gaussian adapter (UnifiedGaussianAdapter.forward, src/model/encoder/common/gaussian_adapter.py:122-150):
  * raw[N, 7+3K] network channels (row stride `raw_stride` floats >= 7+3K: the encoder hands over `gaussians[..., 1:]`, a view

@@ -12,7 +12,7 @@ from pathlib import Path
 
 # SPF_LIB_DIR: development only -- a profiling/experimental build kept next to the regular one (see build.py)
 LIB_PATH = Path(__file__).resolve().parent / os.environ.get("SPF_LIB_DIR", "_C") / "libspfsplat_hip.so"
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 STAGE_NAMES = ("project_fwd", "tile_scan", "bin_pairs", "tile_sort", "render_fwd", "render_bwd",
                "project_bwd", "rope2d")
@@ -71,6 +71,10 @@ SYMBOLS = {
     "spf_decoder_prepare": (C.c_int, [C.POINTER(SpfCamera), C.c_void_p, C.c_uint64, C.c_void_p]),
     "spf_raster_forward_project_prepared": (C.c_int, [C.POINTER(SpfDims), C.POINTER(SpfInputs), C.POINTER(SpfState),
                                                       C.c_uint64, C.c_void_p]),
+    "spf_raster_forward_project_cov3d": (C.c_int, [C.POINTER(SpfDims), C.POINTER(SpfInputs), C.c_void_p,
+                                                   C.POINTER(SpfState), C.c_uint64, C.c_void_p]),
+    "spf_raster_backward_cov3d": (C.c_int, [C.POINTER(SpfDims), C.POINTER(SpfInputs), C.c_void_p, C.POINTER(SpfState),
+                                            C.POINTER(SpfGrads), C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
     "spf_camera_backward_partials": (C.c_int, [C.POINTER(SpfCamera), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "spf_mse_partial_blocks": (C.c_int, []),
     "spf_mse_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),

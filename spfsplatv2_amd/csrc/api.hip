@@ -7,8 +7,10 @@
 #include "spf_common.h"
 
 namespace spf {
-hipError_t launch_project_fwd(const SpfDims&, const SpfInputs&, const SpfState&, int, int, hipStream_t);
-hipError_t launch_project_bwd(const SpfDims&, const SpfInputs&, const SpfState&, const SpfGrads&, int, uint64_t, hipStream_t);
+hipError_t launch_project_fwd(const SpfDims&, const SpfInputs&, const SpfState&, int, int, hipStream_t,
+                              const float* cov3D = nullptr);
+hipError_t launch_project_bwd(const SpfDims&, const SpfInputs&, const SpfState&, const SpfGrads&, int, uint64_t, hipStream_t,
+                              const float* cov3D = nullptr, float* dL_dcov3D = nullptr);
 hipError_t launch_tile_scan(const SpfState&, int, int, int, uint32_t, bool, hipStream_t);
 uint32_t dense_threshold();
 hipError_t launch_bin_pairs(const SpfDims&, const SpfState&, uint64_t, int, int, uint32_t, hipStream_t);
@@ -237,7 +239,9 @@ int check_dims(const SpfDims* d) {
     return SPF_OK;
 }
 
-int check_inputs(const SpfDims* d, const SpfInputs* in) {
+// `no_pair`: the scale/rotation pair is not needed -- replaced by precomputed covariances (checked by the *_cov3d entry
+// points), or not read at all (spf_raster_forward_render)
+int check_inputs(const SpfDims* d, const SpfInputs* in, bool no_pair = false) {
     if (!in) return fail(SPF_E_INVALID, "inputs is null");
     const bool raw = d->sh_layout == 3;
     if (!in->means3D || !in->opacities || !in->viewmatrix || !in->projmatrix || !in->tanfov || !in->bg)
@@ -246,7 +250,7 @@ int check_inputs(const SpfDims* d, const SpfInputs* in) {
         if (!in->raw || !in->sh_mask) return fail(SPF_E_INVALID, "sh_layout 3: raw and sh_mask are required");
         if (in->shs || in->colors) return fail(SPF_E_INVALID, "sh_layout 3: shs / colors must be null (the harmonics are in the raw rows)");
     } else {
-        if (!in->scales || !in->rotations) return fail(SPF_E_INVALID, "a required input pointer is null");
+        if (!no_pair && (!in->scales || !in->rotations)) return fail(SPF_E_INVALID, "a required input pointer is null");
         if ((in->shs == nullptr) == (in->colors == nullptr))
             return fail(SPF_E_INVALID, "exactly one of shs / colors must be given");
     }
@@ -318,10 +322,10 @@ int spf_camera_backward(const SpfCamera* cam, const float* dL_dviewmatrix, float
 
 // tiles_cleared: 0 = nothing (this call clears the counts), 1 = tile_count | tile_flags, 2 = all the tile bookkeeping
 static int forward_project(const SpfDims* d, const SpfInputs* in, SpfState* st, int tiles_cleared, void* stream_,
-                           uint64_t cleared_words = 0) {
+                           uint64_t cleared_words = 0, const float* cov3D = nullptr) {
     int rc = check_dims(d);
     if (rc) return rc;
-    rc = check_inputs(d, in);
+    rc = check_inputs(d, in, cov3D != nullptr);
     if (rc) return rc;
     if (!st || !st->rec || !st->radii || !st->rect || !st->zkey || !st->tile_count || !st->tile_start ||
         !st->tile_fill || !st->tile_flags || !st->counters || !st->blk_total || !st->blk_base)
@@ -351,7 +355,7 @@ static int forward_project(const SpfDims* d, const SpfInputs* in, SpfState* st, 
     }
     {
         StageScope t(SPF_STAGE_PROJECT, stream);
-        SPF_HIP(spf::launch_project_fwd(*d, *in, *st, tiles_x, tiles_y, stream));
+        SPF_HIP(spf::launch_project_fwd(*d, *in, *st, tiles_x, tiles_y, stream, cov3D));
     }
     if (direct) return SPF_OK;              // the projection kernel binned; tile_count is the bins' fill: no scan
     {
@@ -366,8 +370,8 @@ int spf_raster_forward_project(const SpfDims* d, const SpfInputs* in, SpfState* 
     return forward_project(d, in, st, 0, stream_);
 }
 
-int spf_raster_forward_project_prepared(const SpfDims* d, const SpfInputs* in, SpfState* st, uint64_t cleared_bytes,
-                                        void* stream_) {
+static int forward_project_cleared(const SpfDims* d, const SpfInputs* in, SpfState* st, uint64_t cleared_bytes,
+                                   void* stream_, const float* cov3D) {
     // `cleared_bytes`: how much of tile_count | tile_flags | tile_start | tile_fill | counters (one buffer, in this order)
     // the caller cleared.  All of it: one-block-per-render scan.  Only the two count arrays (the older contract): the
     // self-initialising single-block scan.  Less than that: this call clears the counts itself.
@@ -375,9 +379,35 @@ int spf_raster_forward_project_prepared(const SpfDims* d, const SpfInputs* in, S
     const uint64_t RT = (uint64_t)d->S * d->V * spf_raster_num_tiles(d->H, d->W);
     const bool laid_out = st->tile_count && st->tile_flags == st->tile_count + RT && st->tile_start == st->tile_flags + RT &&
                           st->tile_fill == st->tile_start + RT + 1 && st->counters == st->tile_fill + RT;
-    if (laid_out && cleared_bytes >= 4 * (4 * RT + 5)) return forward_project(d, in, st, 2, stream_, cleared_bytes / 4);
-    if (laid_out && cleared_bytes >= 8 * RT) return forward_project(d, in, st, 1, stream_, cleared_bytes / 4);
-    return forward_project(d, in, st, 0, stream_);
+    if (laid_out && cleared_bytes >= 4 * (4 * RT + 5)) return forward_project(d, in, st, 2, stream_, cleared_bytes / 4, cov3D);
+    if (laid_out && cleared_bytes >= 8 * RT) return forward_project(d, in, st, 1, stream_, cleared_bytes / 4, cov3D);
+    return forward_project(d, in, st, 0, stream_, 0, cov3D);
+}
+
+int spf_raster_forward_project_prepared(const SpfDims* d, const SpfInputs* in, SpfState* st, uint64_t cleared_bytes,
+                                        void* stream_) {
+    return forward_project_cleared(d, in, st, cleared_bytes, stream_, nullptr);
+}
+
+// what the covariance entry points reject before anything is launched (the scale/rotation pair, the band-split and
+// raw-row layouts, a missing covariance)
+static int check_cov3d(const SpfDims* d, const SpfInputs* in, const float* cov3D, const SpfState* st) {
+    if (!d || !in || !st) return fail(SPF_E_INVALID, "dims / inputs / state is null");
+    if (in->scales || in->rotations)
+        return fail(SPF_E_INVALID, "cov3d: scales and rotations must be null (exactly one of a scale/rotation pair or a "
+                                   "precomputed 3D covariance)");
+    if (d->sh_layout == 2 || d->sh_layout == 3)
+        return fail(SPF_E_INVALID, "cov3d: sh_layout %d is not supported with precomputed covariances (0 or 1 only)",
+                    d->sh_layout);
+    if (!cov3D) return fail(SPF_E_INVALID, "cov3d: cov3D is null");
+    return SPF_OK;
+}
+
+int spf_raster_forward_project_cov3d(const SpfDims* d, const SpfInputs* in, const float* cov3D, SpfState* st,
+                                     uint64_t cleared_bytes, void* stream_) {
+    const int rc = check_cov3d(d, in, cov3D, st);
+    if (rc) return rc;
+    return forward_project_cleared(d, in, st, cleared_bytes, stream_, cov3D);
 }
 
 int spf_decoder_prepare(const SpfCamera* cam, void* zero, uint64_t zero_bytes, void* stream_) {
@@ -418,7 +448,7 @@ int spf_raster_forward_render(const SpfDims* d, const SpfInputs* in, SpfState* s
     (void)dense_tiles_hint;       // (ignored: one kernel composites sparse and dense tiles -- see the header)
     int rc = check_dims(d);
     if (rc) return rc;
-    rc = check_inputs(d, in);
+    rc = check_inputs(d, in, true);          // (the compositing stage never reads the scale/rotation pair)
     if (rc) return rc;
     if (!st || !st->rec || !st->rect || !st->zkey || !st->tile_start || !st->tile_fill || !st->tile_flags ||
         !st->counters || !st->tile_count ||
@@ -486,12 +516,11 @@ int spf_raster_forward_render(const SpfDims* d, const SpfInputs* in, SpfState* s
     return rc;
 }
 
-int spf_raster_backward(const SpfDims* d, const SpfInputs* in, const SpfState* st, const SpfGrads* g,
-                        uint64_t capacity, uint32_t dense_tiles_hint, void* stream_) {
-    (void)dense_tiles_hint;
+static int raster_backward(const SpfDims* d, const SpfInputs* in, const SpfState* st, const SpfGrads* g,
+                           uint64_t capacity, void* stream_, const float* cov3D, float* dL_dcov3D) {
     int rc = check_dims(d);
     if (rc) return rc;
-    rc = check_inputs(d, in);
+    rc = check_inputs(d, in, cov3D != nullptr);
     if (rc) return rc;
     if (!st || !st->rec || !st->radii || !st->rect || !st->tile_start || !st->tile_flags || !st->pairs ||
         !st->final_T || !st->n_contrib || !st->pair_off || !st->tile_count)
@@ -511,7 +540,8 @@ int spf_raster_backward(const SpfDims* d, const SpfInputs* in, const SpfState* s
     // (every pair record is written exactly once by its tile: no memset of gpair)
     int bounds[kMaxChunks + 1];
     bool by_scene = false;
-    int C = d->bin_cap > 0 ? 1 : plan_chunks(d->S, d->V, T, bounds, &by_scene);
+    // (covariance calls run as one chain: make_chunk offsets the scale/rotation pair, not a [S,G,6] covariance)
+    int C = (d->bin_cap > 0 || cov3D) ? 1 : plan_chunks(d->S, d->V, T, bounds, &by_scene);
     LaneSet* lanes = (C > 1 && by_scene) ? lane_set() : nullptr;     // the projection backward owns whole scenes
     if (!lanes) { C = 1; bounds[0] = 0; bounds[1] = d->S * d->V; }
     auto chunk = [&](int c) -> int {                                        // (see spf_raster_forward_render)
@@ -529,7 +559,7 @@ int spf_raster_backward(const SpfDims* d, const SpfInputs* in, const SpfState* s
         {
             StageScope t(SPF_STAGE_PROJECT_BWD, cs);
             SPF_HIP(spf::launch_project_bwd(ch.d, ch.in, ch.st, ch.g, spf_raster_view_partial_blocks(d->G), capacity,
-                                            cs));
+                                            cs, cov3D, dL_dcov3D));
         }
         return SPF_OK;
     };
@@ -540,6 +570,24 @@ int spf_raster_backward(const SpfDims* d, const SpfInputs* in, const SpfState* s
             return fail(SPF_E_LAUNCH, "joining the auxiliary lane: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
     }
     return rc;
+}
+
+int spf_raster_backward(const SpfDims* d, const SpfInputs* in, const SpfState* st, const SpfGrads* g,
+                        uint64_t capacity, uint32_t dense_tiles_hint, void* stream_) {
+    (void)dense_tiles_hint;
+    return raster_backward(d, in, st, g, capacity, stream_, nullptr, nullptr);
+}
+
+int spf_raster_backward_cov3d(const SpfDims* d, const SpfInputs* in, const float* cov3D, const SpfState* st,
+                              const SpfGrads* g, float* dL_dcov3D, uint64_t capacity, uint32_t dense_tiles_hint,
+                              void* stream_) {
+    (void)dense_tiles_hint;
+    int rc = check_cov3d(d, in, cov3D, st);
+    if (rc) return rc;
+    if (g && (g->dL_dscales || g->dL_drotations))
+        return fail(SPF_E_INVALID, "cov3d: dL_dscales and dL_drotations must be null (the covariance gradient goes to "
+                                   "dL_dcov3D)");
+    return raster_backward(d, in, st, g, capacity, stream_, cov3D, dL_dcov3D);
 }
 
 int spf_adapter_forward(const float* raw, int64_t raw_stride, int64_t N, int32_t K, const float* sh_mask, float eps,

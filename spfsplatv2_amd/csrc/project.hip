@@ -37,6 +37,28 @@ __device__ __forceinline__ void scale_columns(const float R[9], float sx, float 
     for (int j = 0; j < 3; ++j) { N[3 * j] = R[3 * j] * sx; N[3 * j + 1] = R[3 * j + 1] * sy; N[3 * j + 2] = R[3 * j + 2] * sz; }
 }
 
+// Precomputed covariances (COV instantiations, spf_raster_*_cov3d): the six floats (xx, xy, xz, yy, yz, zz) of Sigma are
+// factored ONCE per Gaussian into the lower-triangular L with L L^T = Sigma, and L stands in for N: everything downstream
+// (B = M (sc L), the Cauchy-Binet determinant, radius, rect, record) is the scale/rotation path's code unchanged.
+// Cholesky in float64, rounded once to float32 (L carries half the dynamic range of Sigma; a needle's pivots are
+// differences of nearly equal products).  A non-positive pivot is taken as zero, with the rest of its column: a flat
+// splat (one zero eigenvalue) factors exactly, and an indefinite Sigma renders as the L L^T of that clamped factor.
+__device__ __forceinline__ void cov_factor(const float* __restrict__ c6, float L[9]) {
+    const double a = c6[0], b = c6[1], c = c6[2], d = c6[3], e = c6[4], f = c6[5];
+    const double l00 = a > 0.0 ? __builtin_sqrt(a) : 0.0;
+    const double i0 = l00 > 0.0 ? 1.0 / l00 : 0.0;
+    const double l10 = b * i0, l20 = c * i0;
+    const double p1 = d - l10 * l10;
+    const double l11 = p1 > 0.0 ? __builtin_sqrt(p1) : 0.0;
+    const double i1 = l11 > 0.0 ? 1.0 / l11 : 0.0;
+    const double l21 = (e - l20 * l10) * i1;
+    const double p2 = f - l20 * l20 - l21 * l21;
+    const double l22 = p2 > 0.0 ? __builtin_sqrt(p2) : 0.0;
+    L[0] = (float)l00; L[1] = 0.f;         L[2] = 0.f;
+    L[3] = (float)l10; L[4] = (float)l11; L[5] = 0.f;
+    L[6] = (float)l20; L[7] = (float)l21; L[8] = (float)l22;
+}
+
 // Everything the forward and the backward need about one (view, Gaussian) projection.
 struct Proj {
     float tx, ty, tz;          // view-space position
@@ -505,7 +527,10 @@ __host__ __device__ inline int hist_view_group(int V, int T, bool direct = false
 // numbers its (Gaussian, tile) pairs from a sharded global cursor, and every thread writes its keys
 // (depth bits << 32 | Gaussian) -- what spf_tile_scan_* + spf_bin_pairs_* did in two more launches and a second pass over
 // rect / depth.  tile_count ends up as the bins' fill; nothing needs a scan.
-template <int DEG, int NATIVE>
+// COV (sh_layout 0 / 1 only): precomputed covariances instead of the scale/rotation pair -- in.scales then holds the
+// [S,G,6] packed Sigma of each Gaussian (the launcher of spf_raster_forward_project_cov3d puts it there; scale_modifier
+// is not applied), see cov_factor.
+template <int DEG, int NATIVE, bool COV = false>
 // (raw rows at degree 3 sit five registers above the 168 of three waves per SIMD: asked for, the compiler finds them)
 #ifndef SPF_PFWD_RAW_BPC
 #define SPF_PFWD_RAW_BPC 3
@@ -541,6 +566,7 @@ __global__ __launch_bounds__(kBlock, (NATIVE == 3 && DEG == 3) ? SPF_PFWD_RAW_BP
     const kfloat_p mk = kRaw ? as_const(in.sh_mask) : nullptr;
     float sx, sy, sz;
     float4 q;
+    if constexpr (!COV) {
     if (kRaw) {
         sx = fminf(0.001f * softplus_torch(raw_row[0]), 0.3f) * d.scale_modifier;
         sy = fminf(0.001f * softplus_torch(raw_row[1]), 0.3f) * d.scale_modifier;
@@ -553,9 +579,12 @@ __global__ __launch_bounds__(kBlock, (NATIVE == 3 && DEG == 3) ? SPF_PFWD_RAW_BP
         sz = in.scales[3 * sg + 2] * d.scale_modifier;
         q = *reinterpret_cast<const float4*>(in.rotations + 4 * sg);
     }
+    }
     const float opac = in.opacities[sg];
     float N0[9];
-    {
+    if constexpr (COV) {
+        cov_factor(in.scales + 6 * sg, N0);                          // (sg: Gaussian 0 of the scene for dead lanes)
+    } else {
         float R[9];
         quat_rot(q, R);
         scale_columns(R, sx, sy, sz, N0);
@@ -891,7 +920,9 @@ __host__ __device__ inline bool sh_stage_out(int V, int K, bool raw = false) {
 
 // (degree >= 2: 9..25 coefficients per channel.  Left alone the scheduler hoists every coefficient load to the top of
 // the SH section -- 300+ VGPRs, one wave per SIMD; asking for two blocks per CU caps it at 256 VGPRs)
-template <int DEG, int NATIVE>
+// COV: as in the forward, in.scales holds the packed Sigma [S,G,6]; gr.dL_dscales (may be NULL) receives dL/dSigma in the
+// same packed form (the six accumulators below replace the nine of dL/dN, and the scale/rotation tail is not run).
+template <int DEG, int NATIVE, bool COV = false>
 __global__ __launch_bounds__(kBlock, ((DEG == 2 || DEG == 3) ? 2 : (DEG == 4 ? SPF_PBWD_DEG4_BPC : SPF_PBWD_BPC))) void spf_project_bwd_kernel(SpfDims d, SpfInputs in, SpfState st,
                                                                   SpfGrads gr, int nblk, uint64_t capacity) {
     (void)capacity;
@@ -924,6 +955,10 @@ __global__ __launch_bounds__(kBlock, ((DEG == 2 || DEG == 3) ? 2 : (DEG == 4 ? S
             for (int k = 0; k < 3 * kk; ++k) gr.dL_dshs[sg * (size_t)kk * 3 + k] = nan;
             if (NATIVE == 2) for (int k = 0; k < 27; ++k) gr.dL_dshs_high[sg * 27 + k] = nan;
         }
+        if constexpr (COV) {
+            if (gr.dL_dscales) for (int k = 0; k < 6; ++k) gr.dL_dscales[6 * sg + k] = nan;
+            return;
+        }
         if (gr.dL_dscales) for (int k = 0; k < 3; ++k) gr.dL_dscales[3 * sg + k] = nan;
         if (gr.dL_drotations) for (int k = 0; k < 4; ++k) gr.dL_drotations[4 * sg + k] = nan;
         return;
@@ -954,7 +989,7 @@ __global__ __launch_bounds__(kBlock, ((DEG == 2 || DEG == 3) ? 2 : (DEG == 4 ? S
             const float q0 = raw_row[3], q1 = raw_row[4], q2 = raw_row[5], q3 = raw_row[6];
             const float inv = 1.0f / (sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3) + d.adapter_eps);
             q = make_float4(q0 * inv, q1 * inv, q2 * inv, q3 * inv);
-        } else {
+        } else if constexpr (!COV) {
             sx = in.scales[3 * sg] * d.scale_modifier; sy = in.scales[3 * sg + 1] * d.scale_modifier;
             sz = in.scales[3 * sg + 2] * d.scale_modifier;
             q = *reinterpret_cast<const float4*>(in.rotations + 4 * sg);
@@ -963,7 +998,10 @@ __global__ __launch_bounds__(kBlock, ((DEG == 2 || DEG == 3) ? 2 : (DEG == 4 ? S
     }
     (void)opac;
     float N0[9];
-    {
+    if constexpr (COV) {
+        // the forward's factor, bit for bit (same function, same inputs): B and its gradient are formed from it
+        cov_factor(in.scales + 6 * sg, N0);                          // (sg: Gaussian 0 of the scene for dead lanes)
+    } else {
         float R[9];
         quat_rot(q, R);
         scale_columns(R, sx, sy, sz, N0);
@@ -974,6 +1012,7 @@ __global__ __launch_bounds__(kBlock, ((DEG == 2 || DEG == 3) ? 2 : (DEG == 4 ? S
     float dN0[9];                            // dL/dN, N = R diag(s) (summed over the views)
 #pragma unroll
     for (int k = 0; k < 9; ++k) dN0[k] = 0.f;
+    float dcov[COV ? 6 : 1] = {};            // COV: dL/dSigma, packed (xx, xy, xz, yy, yz, zz) (summed over the views)
     float dopac = 0.f;
     float dcol[3] = {0.f, 0.f, 0.f};        // colours given directly
 
@@ -1155,8 +1194,21 @@ __global__ __launch_bounds__(kBlock, ((DEG == 2 || DEG == 3) ? 2 : (DEG == 4 ? S
             for (int j = 0; j < 3; ++j) {
                 dm0[j] = db0[0] * N0[3 * j] + db0[1] * N0[3 * j + 1] + db0[2] * N0[3 * j + 2];
                 dm1[j] = db1[0] * N0[3 * j] + db1[1] * N0[3 * j + 1] + db1[2] * N0[3 * j + 2];
+                if constexpr (!COV) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) dN0[3 * j + k] += m0[j] * db0[k] + m1[j] * db1[k];
+                }
+            }
+            if constexpr (COV) {
+                // a = sc^2 m0' S m0 + 0.3, b = sc^2 m0' S m1, c = sc^2 m1' S m1 + 0.3; an off-diagonal entry of the packed
+                // Sigma fills both symmetric slots
+                const float s2 = sc * sc, ga = s2 * da, gb = s2 * db, gc = s2 * dc;
+                dcov[0] += ga * m0[0] * m0[0] + gb * m0[0] * m1[0] + gc * m1[0] * m1[0];
+                dcov[3] += ga * m0[1] * m0[1] + gb * m0[1] * m1[1] + gc * m1[1] * m1[1];
+                dcov[5] += ga * m0[2] * m0[2] + gb * m0[2] * m1[2] + gc * m1[2] * m1[2];
+                dcov[1] += 2.f * ga * m0[0] * m0[1] + gb * (m0[0] * m1[1] + m1[0] * m0[1]) + 2.f * gc * m1[0] * m1[1];
+                dcov[2] += 2.f * ga * m0[0] * m0[2] + gb * (m0[0] * m1[2] + m1[0] * m0[2]) + 2.f * gc * m1[0] * m1[2];
+                dcov[4] += 2.f * ga * m0[1] * m0[2] + gb * (m0[1] * m1[2] + m1[1] * m0[2]) + 2.f * gc * m1[1] * m1[2];
             }
             // M = J Wcv, Wcv[i][j] = Vm[4j+i]:  m0[j] = J00 Vm[4j] + J02 Vm[4j+2], m1[j] = J11 Vm[4j+1] + J12 Vm[4j+2]
             float dJ00 = 0.f, dJ02 = 0.f, dJ11 = 0.f, dJ12 = 0.f;
@@ -1320,6 +1372,14 @@ __global__ __launch_bounds__(kBlock, ((DEG == 2 || DEG == 3) ? 2 : (DEG == 4 ? S
         }
         return;
     }
+    if constexpr (COV) {
+        if (gr.dL_dscales) {
+            float* __restrict__ o = gr.dL_dscales + 6 * sg;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) o[k] = dcov[k];
+        }
+        return;
+    }
     if (gr.dL_dscales && gr.dL_drotations) {
         // N[i][k] = R[i][k] s_k.  R is rebuilt from the quaternion here rather than carried through the view loop (nine
         // registers; the compiler would otherwise keep the copy it made for N0 alive: hence the opaque quaternion)
@@ -1389,12 +1449,12 @@ static inline int sh_eval_degree(const SpfDims& d) {
     const int cap = d.sh_band4 ? 4 : 3;
     return d.sh_degree > cap ? cap : d.sh_degree;
 }
-template <int DEG, int NATIVE>
+template <int DEG, int NATIVE, bool COV = false>
 static void project_fwd_t(dim3 grid, size_t sm, hipStream_t stream, const SpfDims& d, const SpfInputs& in,
                           const SpfState& st, int tiles_x, int tiles_y, int lds) {
-    spf_project_fwd_kernel<DEG, NATIVE><<<grid, dim3(kBlock), sm, stream>>>(d, in, st, tiles_x, tiles_y, lds);
+    spf_project_fwd_kernel<DEG, NATIVE, COV><<<grid, dim3(kBlock), sm, stream>>>(d, in, st, tiles_x, tiles_y, lds);
 }
-template <int DEG, int NATIVE>
+template <int DEG, int NATIVE, bool COV = false>
 static void project_bwd_t(dim3 grid, hipStream_t stream, const SpfDims& d, const SpfInputs& in, const SpfState& st,
                           const SpfGrads& g, int nblk, uint64_t capacity) {
     size_t lds = (size_t)(d.V < kViewChunk ? d.V : kViewChunk) * 48 * sizeof(float);
@@ -1407,13 +1467,13 @@ static void project_bwd_t(dim3 grid, hipStream_t stream, const SpfDims& d, const
             static std::atomic<bool> attr_set[64];      // (per instantiation; idempotent attribute, see binning.hip)
             int dev = 0;
             if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spf_project_bwd_kernel<DEG, NATIVE>),
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spf_project_bwd_kernel<DEG, NATIVE, COV>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
                 if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
             }
         }
     }
-    spf_project_bwd_kernel<DEG, NATIVE><<<grid, dim3(kBlock), lds, stream>>>(d, in, st, g, nblk, capacity);
+    spf_project_bwd_kernel<DEG, NATIVE, COV><<<grid, dim3(kBlock), lds, stream>>>(d, in, st, g, nblk, capacity);
 }
 // The band-split layout (sh_layout 2: planes [S,G,3,16] | [S,G,3,9]) below degree 4 IS the native layout with K = 16 on
 // plane 0 -- 16-byte aligned coefficient rows, and the band-4 plane is neither read nor (backward) written.
@@ -1445,9 +1505,31 @@ static inline SpfDims dims_for_kernels(const SpfDims& d, int deg) {
         case 8: FN<4, false>(__VA_ARGS__); break;                        \
         default: FN<4, true>(__VA_ARGS__); break;                        \
     }
+// precomputed covariances: sh_layout 0 / 1 (api.hip rejects 2 and 3 before any launch)
+#define SPF_DISPATCH_DEG_COV(FN, ...)                                    \
+    switch (deg * 2 + (native ? 1 : 0)) {                                \
+        case -2: case -1: FN<-1, false, true>(__VA_ARGS__); break;       \
+        case 0: FN<0, false, true>(__VA_ARGS__); break;                  \
+        case 1: FN<0, true, true>(__VA_ARGS__); break;                   \
+        case 2: FN<1, false, true>(__VA_ARGS__); break;                  \
+        case 3: FN<1, true, true>(__VA_ARGS__); break;                   \
+        case 4: FN<2, false, true>(__VA_ARGS__); break;                  \
+        case 5: FN<2, true, true>(__VA_ARGS__); break;                   \
+        case 6: FN<3, false, true>(__VA_ARGS__); break;                  \
+        case 7: FN<3, true, true>(__VA_ARGS__); break;                   \
+        case 8: FN<4, false, true>(__VA_ARGS__); break;                  \
+        default: FN<4, true, true>(__VA_ARGS__); break;                  \
+    }
 
-hipError_t launch_project_fwd(const SpfDims& d_in, const SpfInputs& in, const SpfState& st, int tiles_x, int tiles_y,
-                              hipStream_t stream) {
+// `cov3D` != NULL: the covariance instantiations, with in.scales pointing at it (see spf_project_fwd_kernel)
+hipError_t launch_project_fwd(const SpfDims& d_in, const SpfInputs& in_, const SpfState& st, int tiles_x, int tiles_y,
+                              hipStream_t stream, const float* cov3D) {
+    SpfInputs in = in_;
+    if (cov3D) {
+        if (d_in.sh_layout != 0 && d_in.sh_layout != 1) return hipErrorInvalidValue;   // (api.hip checks first)
+        in.scales = cov3D;
+        in.rotations = nullptr;
+    }
     const int deg = in.colors ? -1 : sh_eval_degree(d_in);
     const SpfDims d = dims_for_kernels(d_in, deg);
     dim3 grid((d.G + kBlock - 1) / kBlock, d.S);
@@ -1463,17 +1545,35 @@ hipError_t launch_project_fwd(const SpfDims& d_in, const SpfInputs& in, const Sp
                 (size_t)kBlock * kRec * sizeof(float);
     if (direct) sm += sizeof(uint32_t) * ((size_t)VG * T + 2 * (size_t)VG * kBlock + (((size_t)VG + 1 + 3) & ~(size_t)3));
     if (sm > 64 * 1024) return hipErrorInvalidValue;     // (V > ~3,000 views per scene without LDS histograms)
-    SPF_DISPATCH_DEG(project_fwd_t, grid, sm, stream, d, in, st, tiles_x, tiles_y, lds)
+    if (cov3D) {
+        SPF_DISPATCH_DEG_COV(project_fwd_t, grid, sm, stream, d, in, st, tiles_x, tiles_y, lds)
+    } else {
+        SPF_DISPATCH_DEG(project_fwd_t, grid, sm, stream, d, in, st, tiles_x, tiles_y, lds)
+    }
     return hipGetLastError();
 }
 
-hipError_t launch_project_bwd(const SpfDims& d_in, const SpfInputs& in, const SpfState& st, const SpfGrads& g,
-                              int nblk, uint64_t capacity, hipStream_t stream) {
+// `cov3D` != NULL: the covariance instantiations; in.scales -> cov3D and g.dL_dscales -> dL_dcov3D (may be NULL)
+hipError_t launch_project_bwd(const SpfDims& d_in, const SpfInputs& in_, const SpfState& st, const SpfGrads& g_,
+                              int nblk, uint64_t capacity, hipStream_t stream, const float* cov3D, float* dL_dcov3D) {
+    SpfInputs in = in_;
+    SpfGrads g = g_;
+    if (cov3D) {
+        if (d_in.sh_layout != 0 && d_in.sh_layout != 1) return hipErrorInvalidValue;   // (api.hip checks first)
+        in.scales = cov3D;
+        in.rotations = nullptr;
+        g.dL_dscales = dL_dcov3D;
+        g.dL_drotations = nullptr;
+    }
     const int deg = in.colors ? -1 : sh_eval_degree(d_in);
     const SpfDims d = dims_for_kernels(d_in, deg);
     dim3 grid(nblk, d.S);
     const bool native = d.sh_layout != 0;
-    SPF_DISPATCH_DEG(project_bwd_t, grid, stream, d, in, st, g, nblk, capacity)
+    if (cov3D) {
+        SPF_DISPATCH_DEG_COV(project_bwd_t, grid, stream, d, in, st, g, nblk, capacity)
+    } else {
+        SPF_DISPATCH_DEG(project_bwd_t, grid, stream, d, in, st, g, nblk, capacity)
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (g.dL_dviewmatrix) {
@@ -1483,5 +1583,6 @@ hipError_t launch_project_bwd(const SpfDims& d_in, const SpfInputs& in, const Sp
     return e;
 }
 #undef SPF_DISPATCH_DEG
+#undef SPF_DISPATCH_DEG_COV
 
 }  // namespace spf

@@ -60,7 +60,8 @@ def _auto_plan_from_env() -> Optional[float]:
 @dataclass
 class Gaussians:
     means: Tensor        # [b, g, 3]
-    covariances: Tensor  # [b, g, 3, 3]   (carried, never read by the rasterizer: cuda_splatting.py:136)
+    covariances: Tensor  # [b, g, 3, 3]   (read only by a decoder with `use_covariances`; the reference never passes it
+    #                                       to its rasterizer, cuda_splatting.py:136)
     rotations: Tensor    # [b, g, 4]
     scales: Tensor       # [b, g, 3]
     harmonics: Tensor    # [b, g, 3, d_sh]   ([b, g, 3, 16] when `harmonics_band4` is given)
@@ -127,7 +128,7 @@ def render_views(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tens
                  scale_invariant: bool = True, use_sh: bool = True, enable_cov_grad: bool = False,
                  enable_sh_grad: bool = False, max_pairs=None, sh_band4: Optional[bool] = None,
                  return_radii: bool = False, record=None, gaussian_sh_band4: Optional[Tensor] = None,
-                 gaussian_raw=None):
+                 gaussian_raw=None, *, use_covariances: bool = False, gaussian_covariances: Optional[Tensor] = None):
     """Batched form of ``render_cuda``: b scenes x v views sharing each scene's Gaussians.
 
     extrinsics [b,v,4,4] (camera-to-world), intrinsics [b,v,3,3] (normalised), near/far [b,v],
@@ -137,9 +138,19 @@ def render_views(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tens
     ``return_radii``).  ``sh_band4``: with d_sh = 25 (sh_degree 4, the reference's default) also evaluate SH band 4;
     None = the ``SPF_SH_BAND4`` environment variable, default off (see ``rasterizer.sh_band4_default``).
     ``gaussian_sh_band4`` [b,g,3,9]: band 4 of BAND-SPLIT harmonics, ``gaussian_sh_coefficients`` then being [b,g,3,16]
-    (``Gaussians.harmonics_band4``).
+    (``Gaussians.harmonics_band4``).  ``use_covariances``: render ``gaussian_covariances`` [b,g,3,3] (or [b,g,6] packed)
+    instead of the scale/rotation pair, which is then ignored (``rasterizer.rasterize_batch``'s ``cov3D``).
     """
     h, w = image_shape
+    if use_covariances:
+        if gaussian_raw is not None:
+            raise RuntimeError("use_covariances: the adapter fused into the decoder (Gaussians.raw) has no covariances -- "
+                               "run the adapter on its own (fuse_into_decoder=False)")
+        if gaussian_covariances is None:
+            raise RuntimeError("use_covariances needs gaussian_covariances")
+        gaussian_scales = gaussian_rotations = None
+    else:
+        gaussian_covariances = None
     if gaussian_raw is not None:
         # the adapter fused into the projection kernels (`Gaussians.raw`): scales / rotations / harmonics are not looked at
         n = (gaussian_raw.raw.shape[-1] - 7) // 3
@@ -158,7 +169,8 @@ def render_views(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tens
         extrinsics, intrinsics, near, far, gaussian_means, gaussian_scales, gaussian_rotations, gaussian_opacities,
         gaussian_sh_coefficients if use_sh else None, None if use_sh else gaussian_sh_coefficients[..., 0],
         background_color, h, w, degree, scale_invariant, enable_cov_grad, enable_sh_grad, max_pairs=max_pairs,
-        sh_layout="g3k", sh_band4=sh_band4, record=record, shs_high=gaussian_sh_band4 if use_sh else None)
+        sh_layout="g3k", sh_band4=sh_band4, record=record, shs_high=gaussian_sh_band4 if use_sh else None,
+        **({} if gaussian_covariances is None else dict(cov3D=gaussian_covariances)))
     return (color, depth, alpha, _radii) if return_radii else (color, depth, alpha)
 
 
@@ -184,14 +196,16 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
                 background_color: Tensor, gaussian_means: Tensor, gaussian_covariances: Tensor,
                 gaussian_sh_coefficients: Tensor, gaussian_opacities: Tensor, gaussian_rotations: Tensor,
                 gaussian_scales: Tensor, scale_invariant: bool = True, use_sh: bool = True,
-                enable_cov_grad: bool = False, enable_sh_grad: bool = False):
+                enable_cov_grad: bool = False, enable_sh_grad: bool = False, *, use_covariances: bool = False):
     """Same signature and result as the reference's ``render_cuda`` (flat batch: item i renders its own
-    Gaussian set ``gaussian_*[i]`` from camera i).  Returns (images [B,3,h,w], depths [B,1,h,w])."""
-    del gaussian_covariances  # dead in the reference too (cuda_splatting.py:136)
+    Gaussian set ``gaussian_*[i]`` from camera i).  Returns (images [B,3,h,w], depths [B,1,h,w]).
+    ``gaussian_covariances`` is dead, as in the reference (cuda_splatting.py:136), unless ``use_covariances``: then it is
+    rendered and the scales and rotations are ignored."""
     color, depth, _ = render_views(
         extrinsics[:, None], intrinsics[:, None], near[:, None], far[:, None], image_shape,
         background_color[:, None], gaussian_means, gaussian_sh_coefficients, gaussian_opacities,
-        gaussian_rotations, gaussian_scales, scale_invariant, use_sh, enable_cov_grad, enable_sh_grad)
+        gaussian_rotations, gaussian_scales, scale_invariant, use_sh, enable_cov_grad, enable_sh_grad,
+        use_covariances=use_covariances, gaussian_covariances=gaussian_covariances if use_covariances else None)
     return color[:, 0], depth[:, 0]
 
 
@@ -200,9 +214,15 @@ def render_cuda_orthographic(extrinsics: Tensor, width: Tensor, height: Tensor, 
                              gaussian_covariances: Tensor, gaussian_sh_coefficients: Tensor,
                              gaussian_opacities: Tensor, gaussian_rotations: Tensor, gaussian_scales: Tensor,
                              fov_degrees: float = 0.1, use_sh: bool = True, dump: dict | None = None,
-                             enable_cov_grad: bool = False, enable_sh_grad: bool = False) -> Tensor:
-    """Fake orthographic render (tiny FOV, camera moved back); returns images [B,3,h,w]."""
-    del gaussian_covariances
+                             enable_cov_grad: bool = False, enable_sh_grad: bool = False, *,
+                             use_covariances: bool = False) -> Tensor:
+    """Fake orthographic render (tiny FOV, camera moved back); returns images [B,3,h,w].  ``use_covariances``: render
+    ``gaussian_covariances`` instead of the scale/rotation pair (otherwise they are dead, as in the reference)."""
+    cov = gaussian_covariances if use_covariances else None
+    if use_covariances:
+        if cov is None:
+            raise RuntimeError("use_covariances needs gaussian_covariances")
+        gaussian_scales = gaussian_rotations = None
     h, w = image_shape
     assert use_sh or gaussian_sh_coefficients.shape[-1] == 1
     n = gaussian_sh_coefficients.shape[-1]
@@ -213,7 +233,7 @@ def render_cuda_orthographic(extrinsics: Tensor, width: Tensor, height: Tensor, 
         gaussian_means, gaussian_scales, gaussian_rotations, gaussian_opacities,
         shs if use_sh else None, None if use_sh else shs[:, :, 0, :],
         view[:, None], proj[:, None], tanfov, background_color[:, None],
-        h, w, degree, 1.0, enable_cov_grad, enable_sh_grad)
+        h, w, degree, 1.0, enable_cov_grad, enable_sh_grad, **({} if cov is None else dict(cov3D=cov)))
     return color[:, 0]
 
 
@@ -275,6 +295,9 @@ class DecoderSplattingCUDACfg:
     make_scale_invariant: bool
     enable_cov_grad: bool
     enable_sh_grad: bool
+    # (not a field of the reference's config) render `Gaussians.covariances` instead of the scale/rotation pair (the
+    # reference's commented-out cov3D_precomp, cuda_splatting.py:136); such calls are never prepared or graph-captured
+    use_covariances: bool = False
 
 
 _data_ptr = torch.Tensor.data_ptr
@@ -363,6 +386,7 @@ class DecoderSplattingCUDA(Decoder[DecoderSplattingCUDACfg]):
         self.make_scale_invariant = cfg.make_scale_invariant
         self.enable_cov_grad = cfg.enable_cov_grad
         self.enable_sh_grad = cfg.enable_sh_grad
+        self.use_covariances = bool(getattr(cfg, "use_covariances", False))
         self.register_buffer("background_color", torch.tensor(cfg.background_color, dtype=torch.float32),
                              persistent=False)
         # `max_pairs` (property): None, or a ``spfsplatv2_amd.plan_pair_budget(...)`` the CALLER sets after one exact call --
@@ -509,7 +533,7 @@ class DecoderSplattingCUDA(Decoder[DecoderSplattingCUDACfg]):
         requires grad) and evaluation calls (nothing will be differentiated: forward-only steps, for the calls the graph
         cache cannot serve because their tensors move) have keys of their own."""
         plan = self.max_pairs
-        if not (self.prepare_steps and isinstance(plan, PairBudget) and plan.max_tile_list > 0):
+        if not (self.prepare_steps and isinstance(plan, PairBudget) and plan.max_tile_list > 0) or self.use_covariances:
             return None
         if torch.cuda.is_current_stream_capturing():
             return None
@@ -620,7 +644,8 @@ class DecoderSplattingCUDA(Decoder[DecoderSplattingCUDACfg]):
             scale_invariant=self.make_scale_invariant, enable_cov_grad=self.enable_cov_grad,
             enable_sh_grad=self.enable_sh_grad, max_pairs=max_pairs, sh_band4=self.sh_band4, return_radii=True,
             record=record, gaussian_sh_band4=getattr(gaussians, "harmonics_band4", None),
-            gaussian_raw=getattr(gaussians, "raw", None))
+            gaussian_raw=getattr(gaussians, "raw", None), use_covariances=self.use_covariances,
+            gaussian_covariances=gaussians.covariances if self.use_covariances else None)
         depth = depth[:, :, 0]                                   # "(b v) 1 h w -> b v h w"
         if self.make_scale_invariant:
             depth = depth * near[:, :, None, None]               # decoder_splatting_cuda.py:72-76
@@ -651,12 +676,22 @@ class DecoderSplattingCUDA(Decoder[DecoderSplattingCUDACfg]):
 
     def _render(self, gaussians, extrinsics, intrinsics, near, far, image_shape, want_extra: bool):
         fused = getattr(gaussians, "raw", None)
+        if self.use_covariances:
+            if fused is not None:
+                raise RuntimeError("this decoder renders Gaussians.covariances (use_covariances), but the adapter is fused "
+                                   "into it (Gaussians.raw carries no covariances): use UnifiedGaussianAdapter with "
+                                   "fuse_into_decoder=False")
+            if gaussians.covariances is None:
+                raise RuntimeError("this decoder renders Gaussians.covariances (use_covariances), which is None")
         if fused is not None:
             if not (self.enable_cov_grad and self.enable_sh_grad) and torch.is_grad_enabled() and fused.raw.requires_grad:
                 raise RuntimeError("Gaussians.raw (adapter fused into the decoder) chains the backward to ALL raw channels: "
                                    "it needs enable_cov_grad and enable_sh_grad")
             # (same positions as below for what the keys look at: [4] means, [5] stands in for the harmonics)
             tensors = (extrinsics, intrinsics, near, far, gaussians.means, fused.raw, gaussians.opacities)
+        elif self.use_covariances:
+            tensors = (extrinsics, intrinsics, near, far, gaussians.means, gaussians.harmonics, gaussians.opacities,
+                       gaussians.covariances)
         else:
             tensors = (extrinsics, intrinsics, near, far, gaussians.means, gaussians.harmonics, gaussians.opacities,
                        gaussians.rotations, gaussians.scales)
@@ -712,7 +747,9 @@ class DecoderSplattingCUDA(Decoder[DecoderSplattingCUDACfg]):
         return result
 
     def _render_planned(self, tensors, gaussians, extrinsics, intrinsics, near, far, image_shape, want_extra: bool):
-        if getattr(gaussians, "raw", None) is not None:           # (fused adapter: the general launcher, planned or exact)
+        # (fused adapter, precomputed covariances: the general launcher, planned or exact -- neither is prepared nor
+        #  captured)
+        if getattr(gaussians, "raw", None) is not None or self.use_covariances:
             return self._render_general(gaussians, extrinsics, intrinsics, near, far, image_shape)
         tkey = self._prepare_key(tensors, image_shape)
         trains = tkey is not None and any(tkey[1])

@@ -211,6 +211,23 @@ def raw_rows(raw: Tensor, d_in: int) -> Tensor:
     return raw.reshape(-1, d_in).contiguous().float()
 
 
+COV_EXCLUSIVE = "Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!"
+
+
+def _cov6(cov3D: Tensor, S: int, G: int) -> Tensor:
+    """Precomputed covariances as the [S,G,6] packed upper triangle (xx, xy, xz, yy, yz, zz) the kernels read.  A full
+    [S,G,3,3] matrix is packed as cov[..., row, col] with (row, col) = triu_indices(3, 3): the lower triangle is never
+    read, and autograd puts each off-diagonal gradient on the upper entry.  (Six basic-index slices, not an index
+    tensor: a host index tensor is copied to the device -- a synchronising copy, forward and backward -- which a planned
+    call must not make and a graph capture does not allow.)"""
+    if not isinstance(cov3D, Tensor):
+        raise TypeError("cov3D must be a torch.Tensor")
+    if tuple(cov3D.shape) == (S, G, 3, 3):
+        cov3D = torch.stack([cov3D[..., 0, 0], cov3D[..., 0, 1], cov3D[..., 0, 2], cov3D[..., 1, 1], cov3D[..., 1, 2],
+                             cov3D[..., 2, 2]], dim=-1)
+    return _f32c(cov3D, "cov3D", (S, G, 6))
+
+
 def _stream_ptr(device) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
@@ -245,17 +262,18 @@ def _early_verdict(dev: torch.device):
 def _forward_impl(means3D, scales, rotations, opacities, shs, colors, viewmatrix, projmatrix, tanfov, bg,
                   view_scale, H, W, sh_degree, scale_modifier, max_pairs, sh_layout=0, camera=None, sh_band4=False,
                   record=None, nothing_needs_grad=False, view64=None, shs_high=None, raw=None, sh_mask=None,
-                  adapter_eps=0.0):
+                  adapter_eps=0.0, cov3D=None):
     """Launch the forward chain.  Returns (outputs, saved state tensors).  `camera` (an SpfCamera whose outputs are
     viewmatrix / projmatrix / tanfov / view_scale): the decoder fast path -- camera set-up and the clearing of the tile
-    counters are one kernel."""
+    counters are one kernel.  `cov3D` [S,G,6] (scales / rotations None): precomputed covariances, through the ctypes
+    path always (the compiled binding does not take them)."""
     lib = _lib.load()
     S, G, _ = means3D.shape
     V = viewmatrix.shape[1]
     R = S * V
     dev = means3D.device
     rec_out = _last if record is None else record
-    fast = _lib.fast() if camera is None else None
+    fast = _lib.fast() if (camera is None and cov3D is None) else None
     if fast is not None:
         # the same chain through the compiled binding (csrc/torch_binding.cpp): allocation, structs, launches and the
         # exact-mode read-back in C++ -- what a per-view caller of the drop-in surface pays b*v times per step
@@ -315,7 +333,17 @@ def _forward_impl(means3D, scales, rotations, opacities, shs, colors, viewmatrix
                        verdict_host=vh if bin_cap else None)
     rec_out["verdict_mirrored"] = bool(bin_cap and vh is not None)
     stream = _stream_ptr(dev)
-    if camera is not None and tiles.data_ptr() % 16 == 0:
+    if cov3D is not None:
+        cleared = 0
+        if camera is not None and tiles.data_ptr() % 16 == 0:
+            _lib.check(lib.spf_decoder_prepare(C.byref(camera), _ptr(tiles), 4 * tiles.numel(), stream),
+                       "spf_decoder_prepare")
+            cleared = 4 * tiles.numel()
+        elif camera is not None:
+            _lib.check(lib.spf_camera_forward(C.byref(camera), stream), "spf_camera_forward")
+        _lib.check(lib.spf_raster_forward_project_cov3d(C.byref(dims), C.byref(inp), _ptr(cov3D), C.byref(st), cleared,
+                                                        stream), "spf_raster_forward_project_cov3d")
+    elif camera is not None and tiles.data_ptr() % 16 == 0:
         # camera set-up and the clearing of ALL the tile bookkeeping in one kernel (the scan then needs no single-block
         # pass: see spf_tile_scan_render_kernel)
         _lib.check(lib.spf_decoder_prepare(C.byref(camera), _ptr(tiles), 4 * tiles.numel(), stream),
@@ -487,11 +515,14 @@ def _plan_mode(max_pairs) -> int:
 
 
 @_on_device_of_first_arg
-def _backward_impl(inputs, state, geom, grads_out, want, shs_high=None, raw=None, sh_mask=None, adapter_eps=0.0):
-    """Launch the backward chain.  `want`: dict of booleans (scales_rot, shs, colors, view, means2D).  `shs_high`: the
-    band-4 plane of the band-split harmonics (sh_layout 2); its gradient is appended to the result -- None unless band 4
+def _backward_impl(inputs, state, geom, grads_out, want, shs_high=None, raw=None, sh_mask=None, adapter_eps=0.0,
+                   cov3D=None):
+    """Launch the backward chain.  `want`: dict of booleans (scales_rot, shs, colors, view, means2D[, cov]).  `shs_high`:
+    the band-4 plane of the band-split harmonics (sh_layout 2); its gradient is appended to the result -- None unless band 4
     was evaluated (a degree-3 evaluation neither reads the plane nor writes its gradient).  `raw` [S*G, 7+3K] (sh_layout
-    3): scales / rotations / shs are None and the result carries dL/draw [S*G, 7+3K] as its LAST element."""
+    3): scales / rotations / shs are None and the result carries dL/draw [S*G, 7+3K] as its LAST element.  `cov3D`
+    [S,G,6]: precomputed covariances (scales / rotations None); the result carries dL/dcov3D [S,G,6] (None unless
+    want["cov"]) as its LAST element."""
     lib = _lib.load()
     means3D, scales, rotations, opacities, shs, colors, viewmatrix, projmatrix, tanfov, bg, view_scale, view64 = inputs
     rec, radii, rect, tiles, pairs, pair_idx, final_T, n_contrib = state
@@ -506,7 +537,11 @@ def _backward_impl(inputs, state, geom, grads_out, want, shs_high=None, raw=None
                               (bin_cap, capacity, lib.spf_raster_pair_shards(S, G)) if bin_cap else None)
     from .shard import active_bucket
     bucket = active_bucket()
-    fast = _lib.fast() if (bucket is None and shs_high is None and raw is None) else None   # (a gradient bucket supplies the output buffers, the split layout a second plane, raw rows another input: ctypes path)
+    if cov3D is not None and bucket is not None:
+        # (GradBucket.NAMES has no slot for a covariance: its gradient must not land in another tensor's place)
+        raise RuntimeError("a shard.GradBucket is active, but this backward renders precomputed covariances: gradient "
+                           "buckets hold no covariance gradient -- run covariance calls outside the bucket")
+    fast = _lib.fast() if (bucket is None and shs_high is None and raw is None and cov3D is None) else None   # (a gradient bucket supplies the output buffers, the split layout a second plane, raw rows another input: ctypes path)
     if fast is not None:
         wv = want["view"]
         with _spf_errors():
@@ -532,6 +567,7 @@ def _backward_impl(inputs, state, geom, grads_out, want, shs_high=None, raw=None
     d_scales = out("scales", scales) if (want["scales_rot"] and raw is None) else None
     d_rot = out("rotations", rotations) if (want["scales_rot"] and raw is None) else None
     d_raw = torch.empty((raw.shape[0], raw.shape[1]), **f32) if raw is not None else None
+    d_cov = torch.empty_like(cov3D) if (cov3D is not None and want.get("cov")) else None
     d_shs = out("harmonics", shs) if (shs is not None and want["shs"]) else None
     d_shs_high = None
     if d_shs is not None and sh_layout == 2 and sh_band4 and sh_degree == 4:
@@ -549,9 +585,16 @@ def _backward_impl(inputs, state, geom, grads_out, want, shs_high=None, raw=None
     gr = _lib.SpfGrads(_ptr(g_image), _ptr(g_depth), _ptr(g_alpha), _ptr(gpair), _ptr(vpartial),
                        _ptr(d_means), _ptr(d_scales), _ptr(d_rot), _ptr(d_opac), _ptr(d_shs), _ptr(d_col),
                        _ptr(d_view), _ptr(d_m2d), _ptr(d_shs_high), _ptr(d_raw))
-    _lib.check(lib.spf_raster_backward(C.byref(dims), C.byref(inp), C.byref(st), C.byref(gr), capacity, dense,
-                                       _stream_ptr(dev)), "spf_raster_backward")
+    if cov3D is not None:
+        _lib.check(lib.spf_raster_backward_cov3d(C.byref(dims), C.byref(inp), _ptr(cov3D), C.byref(st), C.byref(gr),
+                                                 _ptr(d_cov), capacity, dense, _stream_ptr(dev)),
+                   "spf_raster_backward_cov3d")
+    else:
+        _lib.check(lib.spf_raster_backward(C.byref(dims), C.byref(inp), C.byref(st), C.byref(gr), capacity, dense,
+                                           _stream_ptr(dev)), "spf_raster_backward")
     res = (d_means, d_scales, d_rot, d_opac, d_shs, d_col, (vpartial if want["view"] == "partials" else d_view), d_m2d)
+    if cov3D is not None:
+        return res + (d_cov,)
     if raw is not None:
         return res + (d_raw,)
     return res if shs_high is None else res + (d_shs_high,)
@@ -561,21 +604,22 @@ class _RasterizeBatch(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, scales, rotations, opacities, shs, colors, viewmatrix, projmatrix, tanfov, bg,
                 view_scale, H, W, sh_degree, scale_modifier, enable_cov_grad, enable_sh_grad, means2D, max_pairs,
-                sh_band4, record, grad_mode):
+                sh_band4, record, grad_mode, cov3D=None):
         # `grad_mode`: torch.is_grad_enabled() AT THE CALL SITE (inside Function.forward it is always False, and
         # ctx.needs_input_grad stays True under no_grad): a backward will come only if both say so
         ctx.set_materialize_grads(False)
         outs, state, dense = _forward_impl(means3D, scales, rotations, opacities, shs, colors, viewmatrix,
                                            projmatrix, tanfov, bg, view_scale, H, W, sh_degree, scale_modifier,
                                            max_pairs, sh_band4=sh_band4, record=record,
-                                           nothing_needs_grad=not (grad_mode and any(ctx.needs_input_grad)))
+                                           nothing_needs_grad=not (grad_mode and any(ctx.needs_input_grad)),
+                                           cov3D=cov3D)
         S, G, _ = means3D.shape
         ctx.geom = (S, viewmatrix.shape[1], G, 0 if shs is None else shs.shape[2], sh_degree, H, W,
                     float(scale_modifier), _plan_mode(max_pairs), dense, 0, bool(sh_band4))
         ctx.flags = (bool(enable_cov_grad), bool(enable_sh_grad))
         ctx.means2D_shape = None if means2D is None else tuple(means2D.shape)
         ctx.save_for_backward(means3D, scales, rotations, opacities, shs, colors, viewmatrix, projmatrix,
-                              tanfov, bg, view_scale, None, *state)
+                              tanfov, bg, view_scale, None, *state, cov3D)
         ctx.mark_non_differentiable(outs[3])
         return outs
 
@@ -584,14 +628,16 @@ class _RasterizeBatch(torch.autograd.Function):
         saved = ctx.saved_tensors
         need = ctx.needs_input_grad
         enable_cov_grad, enable_sh_grad = ctx.flags
+        cov3D = saved[20]
         want = dict(scales_rot=enable_cov_grad and (need[1] or need[2]), shs=enable_sh_grad and need[4],
-                    colors=need[5], view=need[6], means2D=ctx.means2D_shape is not None and need[17])
-        d_means, d_scales, d_rot, d_opac, d_shs, d_col, d_view, d_m2d = _backward_impl(
-            saved[:12], saved[12:], ctx.geom, (g_image, g_depth, g_alpha), want)
+                    colors=need[5], view=need[6], means2D=ctx.means2D_shape is not None and need[17],
+                    cov=enable_cov_grad and len(need) > 22 and need[22])
+        d_means, d_scales, d_rot, d_opac, d_shs, d_col, d_view, d_m2d, *d_cov = _backward_impl(
+            saved[:12], saved[12:20], ctx.geom, (g_image, g_depth, g_alpha), want, cov3D=cov3D)
         if d_m2d is not None:
             d_m2d = d_m2d.view(ctx.means2D_shape)
         return (d_means, d_scales, d_rot, d_opac, d_shs, d_col, d_view, None, None, None, None,
-                None, None, None, None, None, None, d_m2d, None, None, None, None)
+                None, None, None, None, None, None, d_m2d, None, None, None, None, d_cov[0] if d_cov else None)
 
 
 class _DecoderRender(torch.autograd.Function):
@@ -601,7 +647,7 @@ class _DecoderRender(torch.autograd.Function):
     @staticmethod
     def forward(ctx, extrinsics, intrinsics, near, far, means3D, scales, rotations, opacities, shs, colors, bg,
                 H, W, sh_degree, scale_invariant, enable_cov_grad, enable_sh_grad, max_pairs, sh_layout, sh_band4,
-                record, grad_mode, shs_high=None, raw=None, sh_mask=None, adapter_eps=0.0):
+                record, grad_mode, shs_high=None, raw=None, sh_mask=None, adapter_eps=0.0, cov3D=None):
         ctx.set_materialize_grads(False)
         lib = _lib.load()
         S, V = extrinsics.shape[:2]
@@ -627,7 +673,7 @@ class _DecoderRender(torch.autograd.Function):
                                            sh_band4=sh_band4, record=record,
                                            nothing_needs_grad=not (grad_mode and any(ctx.needs_input_grad)),
                                            view64=view64, shs_high=shs_high, raw=rows, sh_mask=sh_mask,
-                                           adapter_eps=adapter_eps)
+                                           adapter_eps=adapter_eps, cov3D=cov3D)
         G = means3D.shape[1]
         K = 0 if shs is None else (25 if sh_layout == 2 else shs.shape[3 if sh_layout else 2])
         if rows is not None:
@@ -636,7 +682,7 @@ class _DecoderRender(torch.autograd.Function):
         ctx.geom = (S, V, G, K, sh_degree, H, W, 1.0, _plan_mode(max_pairs), dense, int(sh_layout), bool(sh_band4))
         ctx.flags = (bool(enable_cov_grad), bool(enable_sh_grad), bool(scale_invariant))
         ctx.save_for_backward(means3D, scales, rotations, opacities, shs, colors, view, proj, tanfov, bg, vscale,
-                              view64, *state, near, shs_high, rows, sh_mask)
+                              view64, *state, near, shs_high, rows, sh_mask, cov3D)
         ctx.mark_non_differentiable(outs[3])
         return outs
 
@@ -647,16 +693,19 @@ class _DecoderRender(torch.autograd.Function):
         need = ctx.needs_input_grad
         enable_cov_grad, enable_sh_grad, scale_invariant = ctx.flags
         want = dict(scales_rot=enable_cov_grad and (need[5] or need[6]), shs=enable_sh_grad and need[8],
-                    colors=need[9], view="partials" if need[0] else False, means2D=False)
-        shs_high, rows, sh_mask = saved[21], saved[22], saved[23]
+                    colors=need[9], view="partials" if need[0] else False, means2D=False,
+                    cov=enable_cov_grad and len(need) > 26 and need[26])
+        shs_high, rows, sh_mask, cov3D = saved[21], saved[22], saved[23], saved[24]
         if rows is not None:
             want = dict(want, scales_rot=True, shs=True)
         d_means, d_scales, d_rot, d_opac, d_shs, d_col, vpartial, _, *d_high = _backward_impl(
             saved[:12], saved[12:20], ctx.geom, (g_image, g_depth, g_alpha), want, shs_high=shs_high, raw=rows,
-            sh_mask=sh_mask, adapter_eps=ctx.adapter_eps)
-        d_raw = None
+            sh_mask=sh_mask, adapter_eps=ctx.adapter_eps, cov3D=cov3D)
+        d_raw = d_cov = None
         if rows is not None:
             d_raw, d_high = d_high[0].view(ctx.raw_shape), []
+        elif cov3D is not None:
+            d_cov, d_high = d_high[0], []
         d_ext = None
         if need[0]:
             view, near = saved[6], saved[20]
@@ -669,7 +718,7 @@ class _DecoderRender(torch.autograd.Function):
                            "spf_camera_backward_partials")
         return (d_ext, None, None, None, d_means, d_scales, d_rot, d_opac, d_shs, d_col, None,
                 None, None, None, None, None, None, None, None, None, None, None, d_high[0] if d_high else None,
-                d_raw, None, None)
+                d_raw, None, None, d_cov)
 
 
 class StaticStep:
@@ -896,7 +945,7 @@ def render_batch(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tens
                  enable_cov_grad: bool = True, enable_sh_grad: bool = True, max_pairs=None,
                  sh_layout: str = "gk3", sh_band4: Optional[bool] = None, record: Optional[CallRecord] = None,
                  shs_high: Optional[Tensor] = None, raw: Optional[Tensor] = None, sh_mask: Optional[Tensor] = None,
-                 adapter_eps: float = 1e-8):
+                 adapter_eps: float = 1e-8, cov3D: Optional[Tensor] = None):
     """Poses in, images out: camera set-up (render_cuda's preamble) and rasterization in one autograd node.
 
     extrinsics [S,V,4,4] camera-to-world, intrinsics [S,V,3,3] normalised, near/far [S,V]; Gaussians as in
@@ -906,8 +955,15 @@ def render_batch(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tens
     (``UnifiedGaussianAdapter(..., split_harmonics=True)``) -- a degree-3 evaluation then never touches band 4's bytes,
     forward or backward.  ``sh_band4``: evaluate
     band 4 when ``sh_degree`` is 4 (None = ``sh_band4_default()``).  ``record``: a ``CallRecord`` that receives this
-    call's statistics / plan counters.  Returns image [S,V,3,H,W], depth [S,V,1,H,W] (rasterizer units),
-    alpha [S,V,1,H,W], radii [S,V,G]."""
+    call's statistics / plan counters.  ``cov3D`` ([S,G,6] or [S,G,3,3], with ``scales`` and ``rotations`` None):
+    precomputed covariances, as in ``rasterize_batch`` (with ``scale_invariant`` render (s,v) sees ``Sigma * k^2``).
+    Returns image [S,V,3,H,W], depth [S,V,1,H,W] (rasterizer units), alpha [S,V,1,H,W], radii [S,V,G]."""
+    if cov3D is not None:
+        if scales is not None or rotations is not None:
+            raise RuntimeError(COV_EXCLUSIVE)
+        if raw is not None or shs_high is not None:
+            raise RuntimeError("precomputed covariances (cov3D) are not supported with raw rows or band-split harmonics "
+                               "(shs_high)")
     if raw is not None:
         return _render_batch_raw(extrinsics, intrinsics, near, far, means3D, opacities, raw, sh_mask, adapter_eps, bg,
                                  image_height, image_width, sh_degree, scale_invariant, max_pairs, sh_band4, record)
@@ -920,8 +976,11 @@ def render_batch(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tens
     near = _f32c(near, "near", (S, V))
     far = _f32c(far, "far", (S, V))
     means3D = _f32c(means3D, "means3D", (S, G, 3))
-    scales = _f32c(scales, "scales", (S, G, 3))
-    rotations = _f32c(rotations, "rotations", (S, G, 4))
+    if cov3D is not None:
+        cov3D = _cov6(cov3D, S, G)
+    else:
+        scales = _f32c(scales, "scales", (S, G, 3))
+        rotations = _f32c(rotations, "rotations", (S, G, 4))
     opacities = _f32c(opacities.reshape(S, G), "opacities", (S, G))
     if sh_layout not in ("gk3", "g3k"):
         raise RuntimeError(f"sh_layout must be 'gk3' or 'g3k', got {sh_layout!r}")
@@ -949,7 +1008,7 @@ def render_batch(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tens
     return _DecoderRender.apply(extrinsics, intrinsics, near, far, means3D, scales, rotations, opacities, shs,
                                 colors_precomp, bg, int(image_height), int(image_width), int(sh_degree),
                                 bool(scale_invariant), enable_cov_grad, enable_sh_grad, max_pairs, layout,
-                                bool(sh_band4), record, torch.is_grad_enabled(), shs_high)
+                                bool(sh_band4), record, torch.is_grad_enabled(), shs_high, None, None, 0.0, cov3D)
 
 
 def _render_batch_raw(extrinsics, intrinsics, near, far, means3D, opacities, raw, sh_mask, adapter_eps, bg, image_height,
@@ -996,7 +1055,7 @@ def rasterize_batch(means3D: Tensor, scales: Tensor, rotations: Tensor, opacitie
                     enable_cov_grad: bool = True, enable_sh_grad: bool = True,
                     means2D: Optional[Tensor] = None, max_pairs=None,
                     view_scale: Optional[Tensor] = None, sh_band4: Optional[bool] = None,
-                    record: Optional[CallRecord] = None):
+                    record: Optional[CallRecord] = None, cov3D: Optional[Tensor] = None):
     """Render S scenes x V views.
 
     means3D [S,G,3], scales [S,G,3], rotations [S,G,4] (r,x,y,z; used as given), opacities [S,G] or
@@ -1016,9 +1075,18 @@ def rasterize_batch(means3D: Tensor, scales: Tensor, rotations: Tensor, opacitie
     an integer or a ``PairBudget`` (see ``plan_pair_budget``) = planned mode, no read-back in the forward pass: the
     plan is verified on the device and a failed plan raises in backward (``check="backward"``) or is reported by
     ``last_plan_flags()`` (``check="deferred"``, fully sync-free and graph-capturable).
+
+    ``cov3D`` ([S,G,6] packed (xx, xy, xz, yy, yz, zz), or [S,G,3,3] of which the upper triangle is read; ``scales``
+    and ``rotations`` None): precomputed 3-D covariances instead of the scale/rotation pair (the public rasterizer's
+    ``cov3D_precomp``).  Used as given -- ``scale_modifier`` does not apply -- and scaled to ``Sigma * k^2`` by
+    ``view_scale``.  Its gradient has the packed input's shape (an off-diagonal entry receives G_ij + G_ji); none with
+    ``enable_cov_grad=False``.  Positive semidefinite input is the contract (rank-deficient is fine); an indefinite
+    matrix renders as L L^T of its Cholesky factor with non-positive pivots clamped to zero (include/spfsplat_hip.h).
     """
     if (shs is None) == (colors_precomp is None):
         raise RuntimeError("provide exactly one of shs / colors_precomp")
+    if cov3D is not None and (scales is not None or rotations is not None):
+        raise RuntimeError(COV_EXCLUSIVE)
     if means3D.dim() != 3 or means3D.shape[-1] != 3:
         raise RuntimeError(f"means3D must be [S,G,3], got {tuple(means3D.shape)}")
     S, G, _ = means3D.shape
@@ -1029,8 +1097,11 @@ def rasterize_batch(means3D: Tensor, scales: Tensor, rotations: Tensor, opacitie
         raise RuntimeError(f"viewmatrix must be [S,V,4,4], got {tuple(viewmatrix.shape)}")
     V = viewmatrix.shape[1]
     means3D = _f32c(means3D, "means3D", (S, G, 3))
-    scales = _f32c(scales, "scales", (S, G, 3))
-    rotations = _f32c(rotations, "rotations", (S, G, 4))
+    if cov3D is not None:
+        cov3D = _cov6(cov3D, S, G)
+    else:
+        scales = _f32c(scales, "scales", (S, G, 3))
+        rotations = _f32c(rotations, "rotations", (S, G, 4))
     opacities = _f32c(opacities.reshape(S, G), "opacities", (S, G))
     if shs is not None:
         if shs.dim() != 4 or shs.shape[-1] != 3:
@@ -1054,7 +1125,7 @@ def rasterize_batch(means3D: Tensor, scales: Tensor, rotations: Tensor, opacitie
     return _RasterizeBatch.apply(means3D, scales, rotations, opacities, shs, colors_precomp, viewmatrix,
                                  projmatrix, tanfov, bg, view_scale, int(image_height), int(image_width),
                                  int(sh_degree), float(scale_modifier), enable_cov_grad, enable_sh_grad, means2D,
-                                 max_pairs, bool(sh_band4), record, torch.is_grad_enabled())
+                                 max_pairs, bool(sh_band4), record, torch.is_grad_enabled(), cov3D)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1115,22 +1186,32 @@ class GaussianRasterizer(torch.nn.Module):
         if (shs is None) == (colors_precomp is None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if cov3Ds_precomp is not None:
-            raise NotImplementedError("cov3Ds_precomp is not supported (the reference never passes it, "
-                                      "cuda_splatting.py:136)")
-        if scales is None or rotations is None:
+            # precomputed covariances [G,6] or [G,3,3] (the reference's call is commented out, cuda_splatting.py:136)
+            if scales is not None or rotations is not None:
+                raise Exception(COV_EXCLUSIVE)
+            if s.render_norm or os.environ.get("SPF_RENDER_NORM", "0") == "1":
+                raise Exception("render_norm is defined from scales and rotations: it is not available with "
+                                "cov3Ds_precomp")
+        elif scales is None and rotations is None:
+            raise Exception(COV_EXCLUSIVE)
+        elif scales is None or rotations is None:
             raise Exception("Please provide scales and rotations")
         if viewmatrix is None:
             raise Exception("viewmatrix is a forward argument of this rasterizer (cuda_splatting.py:137)")
         dev = means3D.device
+        if not means3D.is_cuda:            # (before the settings' tan fov is staged on the tensors' device)
+            raise RuntimeError(f"means3D is on {dev}: the rasterizer only runs on a HIP device (there is no CPU fallback)")
         tanfov = _tanfov_tensor(float(s.tanfovx), float(s.tanfovy), dev)
 
         def render(shs_, colors_, bg, m2d=None):
             return rasterize_batch(
-                means3D[None], scales[None], rotations[None], opacities.reshape(1, -1),
+                means3D[None], None if scales is None else scales[None], None if rotations is None else rotations[None],
+                opacities.reshape(1, -1),
                 None if shs_ is None else shs_[None], None if colors_ is None else colors_[None],
                 viewmatrix[None, None], s.projmatrix[None, None], tanfov, bg.reshape(1, 1, 3),
                 s.image_height, s.image_width, s.sh_degree, s.scale_modifier,
-                s.enable_cov_grad, s.enable_sh_grad, means2D=m2d, sh_band4=s.sh_band4)
+                s.enable_cov_grad, s.enable_sh_grad, means2D=m2d, sh_band4=s.sh_band4,
+                cov3D=None if cov3Ds_precomp is None else cov3Ds_precomp[None])
 
         def blend(attrs: Tensor) -> Tensor:            # [G,C] -> [C,H,W], three channels per pass, no background
             out = []
