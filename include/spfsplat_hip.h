@@ -25,6 +25,8 @@
  *                           src/model/encoder/backbone/vggt/layers/rope.py:62-188, same rotation out of place)
  *                           src/model/encoder/backbone/croco/curope/curope.cpp:49-65 and
  *                           curope/kernels.cu:84-108 (in place, forward and backward).
+ *   spf_reproj_*            LossReproj.forward (src/loss/loss_reproj.py:53-101, project_to_cam in
+ *                           src/misc/cam_utils.py:289-307) and its autograd backward, for all context views at once.
  *
  * Return value of every int function: 0 = success, otherwise a negative SPF_E_* code;
  * spf_last_error() returns a host string describing the most recent failure on this thread.
@@ -359,6 +361,45 @@ int spf_mse_backward(const float* prediction, const float* image, int64_t n, flo
 int spf_mse_forward_grad(const float* prediction, const float* image, int64_t n, float weight, float* partial,
                          float* loss, float* dL_dprediction_unit, void* stream);
 int spf_mse_scale_grad(float* dL_dprediction, int64_t n, const float* dL_dloss, void* stream);
+
+/* Reprojection loss (LossReproj.forward, src/loss/loss_reproj.py:53-101, with project_to_cam,
+ * src/misc/cam_utils.py:289-307) for B x V images at once; view v is normalised by its own valid count over the B images,
+ * which is what V separate calls of the reference return.  Per point n = i W + j of image (b, v):
+ *   cam = W[:3,:3] p + W[:3,3] with W = inverse(pose) (a general 4x4 inverse, float64, rounded to float32);
+ *   q = K' cam with K' = K, row 0 scaled by W and row 1 by H; px = q.xy / max(q.z, 1e-6);
+ *   e = |px - (j, i)|; valid iff !(e > hard_clamp) (NaN is valid and propagates);
+ *   loss[v] = weight * sum_valid term(e) / n_valid, 0 (and zero gradients) when no point is valid.
+ * term: SPF_REPROJ_TANH lw tanh(e / lw) ("tanh": lw = soft_clamp; "dyntanh": lw from the schedule, on the host);
+ *       SPF_REPROJ_L1 e where !(e > soft_clamp); SPF_REPROJ_L1_SQRT that + sqrt(soft_clamp e) where e > soft_clamp;
+ *       SPF_REPROJ_L1_LOG that + log(1 + soft_clamp e) where e > soft_clamp (the reference's `else`: any other mode).
+ * pts3d is read in place: element strides stride_b, stride_v (>= 0) for its first two dimensions; each image's H*W*3
+ * floats are contiguous (16-byte aligned images are read with 16-byte loads).  poses [B,V,4,4] (camera -> world) and
+ * intrinsics [B,V,3,3] (normalised) are contiguous.  A singular pose gives non-finite results (torch.inverse raises).
+ * No atomics, no allocation, no synchronisation; results are run-to-run identical, and view v's results do not depend on
+ * V (the batched call equals the per-view calls bitwise). */
+#define SPF_REPROJ_TANH 0
+#define SPF_REPROJ_L1 1
+#define SPF_REPROJ_L1_SQRT 2
+#define SPF_REPROJ_L1_LOG 3
+typedef struct SpfReproj {
+    const float* pts3d;
+    int64_t stride_b, stride_v;
+    const float* poses;
+    const float* intrinsics;
+    int32_t B, V, H, W;
+    int32_t mode;                 /* SPF_REPROJ_* */
+    float weight, lw, hard_clamp, soft_clamp;
+} SpfReproj;
+/* Scratch sizing: the number of (1024-point chunk, image) slots, B * V * ceil(H W / 1024), or -1 for bad sizes.  The
+ * forward needs 2 * slots 32-bit words of `partial`, the backward 24 * slots floats of `gpartial` (16-byte aligned). */
+int64_t spf_reproj_partial_blocks(int32_t B, int32_t V, int32_t H, int32_t W);
+/* Forward (two launches): loss[V], and scale[V] = weight / n_valid (0 when none) for the backward. */
+int spf_reproj_forward(const SpfReproj* args, void* partial, float* loss, float* scale, void* stream);
+/* Backward (one or two launches): dL_dloss[V] and scale[V] are read on the device.  dL_dpts3d [B,V,H,W,3] contiguous, or
+ * NULL when pts3d needs no gradient; dL_dposes [B,V,4,4] and dL_dintrinsics [B,V,3,3] contiguous, either may be NULL;
+ * gpartial is needed (and only then) when one of them is given. */
+int spf_reproj_backward(const SpfReproj* args, const float* scale, const float* dL_dloss, float* dL_dpts3d,
+                        float* gpartial, float* dL_dposes, float* dL_dintrinsics, void* stream);
 
 /* In-place 2-D rotary embedding.  tokens[B,N,H,D] with element strides (stride_b, stride_n, stride_h) and
  * stride(D) == 1; dtype: 0 = float32, 1 = float16, 2 = bfloat16.  positions[B / pos_div, N, 2] int64 contiguous

@@ -50,6 +50,13 @@ class SpfCamera(C.Structure):
                                                                     ("viewmatrix64", C.c_void_p)]
 
 
+class SpfReproj(C.Structure):
+    _fields_ = [("pts3d", C.c_void_p), ("stride_b", C.c_int64), ("stride_v", C.c_int64), ("poses", C.c_void_p),
+                ("intrinsics", C.c_void_p), ("B", C.c_int32), ("V", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("mode", C.c_int32), ("weight", C.c_float), ("lw", C.c_float), ("hard_clamp", C.c_float),
+                ("soft_clamp", C.c_float)]
+
+
 # Every symbol include/spfsplat_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "spf_abi_version": (C.c_int, []),
@@ -82,6 +89,10 @@ SYMBOLS = {
     "spf_mse_forward_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
     "spf_mse_scale_grad": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "spf_reproj_partial_blocks": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "spf_reproj_forward": (C.c_int, [C.POINTER(SpfReproj), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_reproj_backward": (C.c_int, [C.POINTER(SpfReproj), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
     "spf_adapter_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_adapter_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_void_p,

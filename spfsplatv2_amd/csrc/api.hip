@@ -28,6 +28,9 @@ int mse_partial_blocks();
 hipError_t launch_mse_fwd(const float*, const float*, int64_t, float, float*, float*, float, float*, hipStream_t);
 hipError_t launch_mse_scale(float*, int64_t, const float*, hipStream_t);
 hipError_t launch_mse_bwd(const float*, const float*, int64_t, float, const float*, float*, hipStream_t);
+int64_t reproj_slots(int, int, int, int, int*);
+hipError_t launch_reproj_fwd(const SpfReproj&, void*, float*, float*, hipStream_t);
+hipError_t launch_reproj_bwd(const SpfReproj&, const float*, const float*, float*, float*, float*, float*, hipStream_t);
 hipError_t launch_camera_fwd(const SpfCamera&, hipStream_t);
 hipError_t launch_camera_bwd(const SpfCamera&, const float*, float*, hipStream_t);
 hipError_t launch_camera_fwd_zero(const SpfCamera&, void*, uint64_t, hipStream_t);
@@ -660,6 +663,56 @@ int spf_mse_backward(const float* prediction, const float* image, int64_t n, flo
         return fail(SPF_E_INVALID, "mse: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_mse_bwd(prediction, image, n, 2.0f * weight / (float)n, dL_dloss, dL_dprediction,
                                 static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int64_t spf_reproj_partial_blocks(int32_t B, int32_t V, int32_t H, int32_t W) {
+    if (B < 1 || V < 1 || H < 1 || W < 1) return -1;
+    return spf::reproj_slots(B, V, H, W, nullptr);
+}
+
+static int check_reproj(const SpfReproj* a) {
+    if (!a) return fail(SPF_E_INVALID, "reproj: args is null");
+    if (!a->pts3d || !a->poses || !a->intrinsics) return fail(SPF_E_INVALID, "reproj: null pointer");
+    if (a->B < 1 || a->V < 1 || a->H < 1 || a->W < 1)
+        return fail(SPF_E_INVALID, "reproj: B, V, H, W must be positive (got %d %d %d %d)", a->B, a->V, a->H, a->W);
+    // (one image's 3 H W floats are indexed with 32-bit point numbers; per-view counts are 32-bit)
+    if ((int64_t)a->H * a->W * 3 >= ((int64_t)1 << 31) || (int64_t)a->B * a->H * a->W >= ((int64_t)1 << 31))
+        return fail(SPF_E_INVALID, "reproj: %d x %d x %d points is too large", a->B, a->H, a->W);
+    if ((int64_t)a->B * a->V >= ((int64_t)1 << 31) / 1024) return fail(SPF_E_INVALID, "reproj: B * V is too large");
+    if (a->mode < SPF_REPROJ_TANH || a->mode > SPF_REPROJ_L1_LOG)
+        return fail(SPF_E_INVALID, "reproj: mode %d outside 0..3", a->mode);
+    if (a->stride_b < 0 || a->stride_v < 0)
+        return fail(SPF_E_INVALID, "reproj: negative pts3d strides (%lld, %lld) are not supported",
+                    (long long)a->stride_b, (long long)a->stride_v);
+    if ((reinterpret_cast<uintptr_t>(a->pts3d) | reinterpret_cast<uintptr_t>(a->poses) |
+         reinterpret_cast<uintptr_t>(a->intrinsics)) & 3)
+        return fail(SPF_E_INVALID, "reproj: tensors must be 4-byte aligned");
+    return SPF_OK;
+}
+
+int spf_reproj_forward(const SpfReproj* args, void* partial, float* loss, float* scale, void* stream_) {
+    if (int rc = check_reproj(args)) return rc;
+    if (!partial || !loss || !scale) return fail(SPF_E_INVALID, "reproj: null pointer");
+    if (reinterpret_cast<uintptr_t>(partial) & 3) return fail(SPF_E_INVALID, "reproj: partial must be 4-byte aligned");
+    SPF_HIP(spf::launch_reproj_fwd(*args, partial, loss, scale, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_reproj_backward(const SpfReproj* args, const float* scale, const float* dL_dloss, float* dL_dpts3d,
+                        float* gpartial, float* dL_dposes, float* dL_dintrinsics, void* stream_) {
+    if (int rc = check_reproj(args)) return rc;
+    if (!scale || !dL_dloss) return fail(SPF_E_INVALID, "reproj: null pointer");
+    const bool cam = dL_dposes || dL_dintrinsics;
+    if (!dL_dpts3d && !cam) return fail(SPF_E_INVALID, "reproj: no gradient requested");
+    if (cam != (gpartial != nullptr))
+        return fail(SPF_E_INVALID, "reproj: gpartial is needed exactly when dL_dposes or dL_dintrinsics is given");
+    if (gpartial && (reinterpret_cast<uintptr_t>(gpartial) & 15))
+        return fail(SPF_E_INVALID, "reproj: gpartial must be 16-byte aligned");
+    if (dL_dpts3d && (reinterpret_cast<uintptr_t>(dL_dpts3d) & 3))
+        return fail(SPF_E_INVALID, "reproj: dL_dpts3d must be 4-byte aligned");
+    SPF_HIP(spf::launch_reproj_bwd(*args, scale, dL_dloss, dL_dpts3d, gpartial, dL_dposes, dL_dintrinsics,
+                                   static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
 

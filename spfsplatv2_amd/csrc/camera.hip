@@ -9,39 +9,6 @@
 
 namespace spf {
 
-template <typename T>
-__device__ __forceinline__ T det3(T a, T b, T c, T d, T e, T f, T g, T h, T i) {
-    return a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
-}
-
-// General 4x4 inverse by cofactors (row-major).  Returns false if singular.  Evaluated in float64 by the forward
-// (one lane per render: the cost is nil, and the float32 cofactor sums were only good to ~1e-6 of the translation).
-template <typename T>
-__device__ __forceinline__ bool inv4(const T* m, T* o) {
-    T c[16];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int col = 0; col < 4; ++col) {
-            T s[9];
-            int k = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (i != r && j != col) s[k++] = m[4 * i + j];
-            const T minor = det3<T>(s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8]);
-            c[4 * r + col] = ((r + col) & 1) ? -minor : minor;
-        }
-    const T det = m[0] * c[0] + m[1] * c[1] + m[2] * c[2] + m[3] * c[3];
-    const T id = T(1) / det;
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int col = 0; col < 4; ++col) o[4 * r + col] = c[4 * col + r] * id;  // adjugate = cofactor^T
-    return det != T(0);
-}
-
 // (float64 like the pose: tan(fov/2) scales every pixel coordinate, and a splat whose centre lies thousands of pixels
 //  outside the image -- its footprint may still cross it -- moved by 1e-3 px with the float32 acos / tan chain)
 __device__ __forceinline__ void inv3(const double* m, double* o) {

@@ -8,6 +8,10 @@ here                   reference (/root/reference/src/loss/)
 ``Loss``               loss.py:17-40 (the config wrapper convention: one dataclass field = the loss's name)
 ``LossMse``            loss_mse.py:36-51: ``weight * ((prediction - image) ** 2).mean()``, 0 before ``apply_after_step``
 ``mse_loss``           the same expression as a function (what ``bench.py`` and the tests call)
+``LossReprojCfg``      loss_reproj.py:13-18
+``LossReprojCfgWrapper`` loss_reproj.py:21-23
+``LossReproj``         loss_reproj.py:29-101 (+ project_to_cam, misc/cam_utils.py:289-307): the reprojection loss
+``reproj_loss``        the same as a function; also takes ``[b,v,h,w,3]`` and returns one loss per view in one call
 =====================  =========================================================================
 
 The reference evaluates the expression with eager PyTorch (four kernels forward, four backward over the rendered
@@ -17,6 +21,7 @@ No CPU path: tensors must live on a HIP device.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from abc import ABC, abstractmethod
 from dataclasses import dataclass, fields
 from typing import Generic, TypeVar
@@ -171,3 +176,153 @@ class LossMse(Loss[LossMseCfg, LossMseCfgWrapper]):
         if global_step < self.cfg.apply_after_step:           # not applied yet (loss_mse.py:44-46)
             return torch.tensor(0, dtype=torch.float32, device=image.device)
         return mse_loss(prediction, image, self.cfg.weight)
+
+
+# ---- reprojection loss -------------------------------------------------------------------------------------------
+# mode string -> kernel term (include/spfsplat_hip.h SPF_REPROJ_*): "tanh" and "dyntanh" differ only in lw; every
+# string the reference does not name takes its `else` branch, the l1 + log term (loss_reproj.py:150-155)
+_REPROJ_MODES = {"tanh": 0, "dyntanh": 0, "l1": 1, "l1+sqrt": 2}
+_REPROJ_LOG = 3
+
+
+def reproj_lw(mode: str, global_step, total_iterations, circle_schedule: bool, soft_clamp: float = 50.0,
+              soft_clamp_min: float = 1.0) -> float:
+    """The tanh scale lw of `mode` (loss_reproj.py:117-133), in float64 on the host as the reference computes it:
+    "tanh": soft_clamp; "dyntanh": (1 - s) soft_clamp + soft_clamp_min with s = global_step / total_iterations, or
+    1 - sqrt(1 - s^2) with the circle schedule (NaN past total_iterations, as np.sqrt gives there).  Other modes: 1."""
+    if mode == "tanh":
+        return float(soft_clamp)
+    if mode != "dyntanh":
+        return 1.0
+    s = global_step / total_iterations
+    if circle_schedule:
+        r = 1 - s ** 2
+        s = 1 - math.sqrt(r) if r >= 0 else math.nan
+    return (1 - s) * soft_clamp + soft_clamp_min
+
+
+def _reproj_args(p5: Tensor, poses: Tensor, intr: Tensor, code: int, weight: float, lw: float, hard: float,
+                 soft: float):
+    b, v, h, w, _ = p5.shape
+    return _lib.SpfReproj(C.c_void_p(p5.data_ptr()), p5.stride(0), p5.stride(1), C.c_void_p(poses.data_ptr()),
+                          C.c_void_p(intr.data_ptr()), b, v, h, w, code, weight, lw, hard, soft)
+
+
+class _Reproj(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pts3d: Tensor, poses: Tensor, intrinsics: Tensor, code: int, weight: float, lw: float,
+                hard: float, soft: float):
+        batched = pts3d.dim() == 5
+        p5 = pts3d if batched else pts3d.unsqueeze(1)
+        if not p5[0, 0].is_contiguous():        # the kernels stride over [b, v] only; each image is read contiguous
+            p5 = p5.contiguous()
+        b, v, h, w, _ = p5.shape
+        po = poses.reshape(b, v, 4, 4).contiguous()
+        ki = intrinsics.reshape(b, v, 3, 3).contiguous()
+        lib = _lib.load()
+        dev = p5.device
+        args = _reproj_args(p5, po, ki, code, weight, lw, hard, soft)
+        nslots = lib.spf_reproj_partial_blocks(b, v, h, w)
+        partial = torch.empty(2 * nslots, dtype=torch.float32, device=dev)
+        loss = torch.empty((v,) if batched else (), dtype=torch.float32, device=dev)
+        scale = torch.empty(v, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(lib.spf_reproj_forward(C.byref(args), C.c_void_p(partial.data_ptr()), C.c_void_p(loss.data_ptr()),
+                                              C.c_void_p(scale.data_ptr()), stream), "spf_reproj_forward")
+        ctx.save_for_backward(p5, po, ki, scale)
+        ctx.params = (code, weight, lw, hard, soft, nslots)
+        ctx.shapes = (pts3d.shape, poses.shape, intrinsics.shape)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad):
+        p5, po, ki, scale = ctx.saved_tensors
+        code, weight, lw, hard, soft, nslots = ctx.params
+        need_p, need_pose, need_k = ctx.needs_input_grad[:3]
+        b, v = p5.shape[:2]
+        dev = p5.device
+        g = grad.to(torch.float32).reshape(v).contiguous()
+        dp = torch.empty(p5.shape, dtype=torch.float32, device=dev) if need_p else None
+        dpose = torch.empty(b, v, 4, 4, dtype=torch.float32, device=dev) if need_pose else None
+        dk = torch.empty(b, v, 3, 3, dtype=torch.float32, device=dev) if need_k else None
+        gpartial = (torch.empty(24 * nslots, dtype=torch.float32, device=dev) if (need_pose or need_k) else None)
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr() if t is not None else None)
+        lib = _lib.load()
+        args = _reproj_args(p5, po, ki, code, weight, lw, hard, soft)
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(lib.spf_reproj_backward(C.byref(args), ptr(scale), ptr(g), ptr(dp), ptr(gpartial), ptr(dpose),
+                                               ptr(dk), stream), "spf_reproj_backward")
+        sp, spose, sk = ctx.shapes
+        return (dp.view(sp) if dp is not None else None, dpose.view(spose) if dpose is not None else None,
+                dk.view(sk) if dk is not None else None, None, None, None, None, None)
+
+
+def reproj_loss(pts3d: Tensor, im_poses: Tensor, intrinsics: Tensor, *, weight: float, mode: str, global_step,
+                total_iterations, circle_schedule: bool, detach_pts3d: bool = False, hard_clamp: float = 1000.0,
+                soft_clamp: float = 50.0, soft_clamp_min: float = 1.0) -> Tensor:
+    """``LossReproj.forward`` (loss_reproj.py:53-101) on the HIP library: pts3d [b,h,w,3] (world points, one per pixel),
+    im_poses [b,4,4] (camera -> world), intrinsics [b,3,3] (normalised) -> a 0-dim float32 loss.  With pts3d
+    [b,v,h,w,3], im_poses [b,v,4,4] and intrinsics [b,v,3,3] it returns loss[v], view i normalised by its own valid
+    count: what v calls with ``pts3d[:, i]`` return, bitwise, in four launches whatever v is.
+
+    Differences from the reference, all deliberate: when no point is valid the loss is a 0-dim device zero with zero
+    gradients (the reference returns the Python int 0); bf16 / f16 / f64 inputs are computed in float32 (the reference
+    would compute float64 in float64) and their gradients are cast back by autograd; nothing synchronises the host (no
+    pixel grid upload, no torch.inverse singularity check: a singular pose gives non-finite values, not an error)."""
+    if pts3d.dim() not in (4, 5) or pts3d.shape[-1] != 3:
+        raise RuntimeError(f"reproj_loss: pts3d must be [b,h,w,3] or [b,v,h,w,3], got {tuple(pts3d.shape)}")
+    lead = pts3d.shape[:pts3d.dim() - 3]
+    if tuple(im_poses.shape) != (*lead, 4, 4) or tuple(intrinsics.shape) != (*lead, 3, 3):
+        raise RuntimeError(f"reproj_loss: im_poses {tuple(im_poses.shape)} / intrinsics {tuple(intrinsics.shape)} do not "
+                           f"match pts3d {tuple(pts3d.shape)} (want {(*lead, 4, 4)} / {(*lead, 3, 3)})")
+    for name, t in (("pts3d", pts3d), ("im_poses", im_poses), ("intrinsics", intrinsics)):
+        if not t.is_cuda:
+            raise RuntimeError(f"reproj_loss: {name} is on {t.device}; this build only runs on a HIP device (no CPU "
+                               "fallback)")
+        if not t.is_floating_point():
+            raise RuntimeError(f"reproj_loss: {name} must be a floating-point tensor, got {t.dtype}")
+    if pts3d.numel() == 0:
+        raise RuntimeError("reproj_loss: empty input")
+    if detach_pts3d:
+        pts3d = pts3d.detach()
+    code = _REPROJ_MODES.get(mode, _REPROJ_LOG)
+    lw = reproj_lw(mode, global_step, total_iterations, circle_schedule, soft_clamp, soft_clamp_min)
+    pts3d, im_poses, intrinsics = (t if t.dtype == torch.float32 else t.float() for t in (pts3d, im_poses, intrinsics))
+    return _Reproj.apply(pts3d, im_poses, intrinsics, code, float(weight), float(lw), float(hard_clamp),
+                         float(soft_clamp))
+
+
+@dataclass
+class LossReprojCfg:
+    weight: float
+    mode: str
+    circle_schedule: bool
+    total_iterations: int
+
+
+@dataclass
+class LossReprojCfgWrapper:
+    reproj: LossReprojCfg
+
+
+class LossReproj(Loss[LossReprojCfg, LossReprojCfgWrapper]):
+    """The clamps are instance attributes read at every call, as in the reference (loss_reproj.py:48-50)."""
+
+    def __init__(self, cfg: LossReprojCfgWrapper) -> None:
+        super().__init__(cfg)
+        self.repro_loss_hard_clamp = 1000
+        self.soft_clamp = 50
+        self.soft_clamp_min = 1
+
+    def forward(self, pts3d: Tensor, im_poses: Tensor, intrinsics: Tensor, global_step: int,
+                detach_pts3d: bool = False) -> Tensor:
+        """[b,h,w,3] -> 0-dim loss (the reference's call); [b,v,h,w,3] -> loss[v], one per view (see reproj_loss)."""
+        return reproj_loss(pts3d, im_poses, intrinsics, weight=self.cfg.weight, mode=self.cfg.mode,
+                           global_step=global_step, total_iterations=self.cfg.total_iterations,
+                           circle_schedule=self.cfg.circle_schedule, detach_pts3d=detach_pts3d,
+                           hard_clamp=self.repro_loss_hard_clamp, soft_clamp=self.soft_clamp,
+                           soft_clamp_min=self.soft_clamp_min)
