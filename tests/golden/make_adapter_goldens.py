@@ -29,7 +29,7 @@ ga = load("src.model.encoder.common.gaussian_adapter", "model/encoder/common/gau
 
 gen = torch.Generator().manual_seed(8)
 out = {}
-for deg in (0, 2, 4):
+for deg in (0, 2, 4, 1, 3):      # (1 and 3 were appended later, drawn after 0 / 2 / 4 from the same generator: those keep their bits)
     ad = ga.UnifiedGaussianAdapter(ga.GaussianAdapterCfg(gaussian_scale_min=0.5, gaussian_scale_max=15.0, sh_degree=deg))
     raw = (torch.randn(2, 37, ad.d_in, generator=gen) * 3.0).requires_grad_(True)
     raw.data[0, 0, :3] = torch.tensor([25.0, -30.0, 6.0])        # softplus linear branch / tiny / clamp at 0.3

@@ -93,21 +93,47 @@ def test_adapter_fused_into_the_decoder_is_the_two_pass_path(hip_lib, deg, views
     2e-5 of scale here, north_star asks for 1e-4 / 1e-3) and the radii exactly, with the raw rows read in place from a
     strided view of an 83-channel head output (encoder_spfsplatv2.py:261-268); nine views: the gradient of the harmonics
     leaves through the unstaged path."""
-    import spfsplatv2_amd as spf
-    from spfsplatv2_amd import adapter, synthetic as syn
+    from spfsplatv2_amd import synthetic as syn
     K = (deg + 1) ** 2
     b = syn.make_batch("TEST", 2, views, seed=61 + deg, s_mult=8.0, G=900, K=K, image_hw=(64, 48)).to("cuda")
     gen = torch.Generator("cuda").manual_seed(7)
-    cfg = adapter.GaussianAdapterCfg(0.5, 15.0, deg)
-    plain, fused = adapter.UnifiedGaussianAdapter(cfg).cuda(), adapter.UnifiedGaussianAdapter(cfg, fuse_into_decoder=True).cuda()
     C = 7 + 3 * K
     head = torch.randn(2, 900, C + 1, device="cuda", generator=gen)
     head[..., 1:4] = head[..., 1:4] * 3.0 + 6.0                  # scales of a few per cent of the scene (some at the 0.3 clamp)
     head[..., 8:] *= 30.0                                          # (the mask scales the higher bands down by 40 .. 2,560)
+    _fused_against_two_pass(b, head, deg, strided, gen)
+
+
+def test_adapter_fused_into_the_decoder_is_the_two_pass_path_at_the_reference_size(hip_lib):
+    """The same comparison, same gates, on the call the shipped 2-view model really makes (synthetic.CONFIGS["REF2V"]): one
+    scene, 131,072 Gaussians, 25 SH coefficients, two 256 x 256 views, the raw rows read in place from the 83-channel head
+    output.  The raw channels are the ones the adapter maps back onto the synthetic scene (softplus^-1 of its scales, its
+    unit quaternions, harmonics / sh_mask), so the decoder sees REF2V's own workload.  No CPU rasterizer oracle at this
+    size (minutes): tests/test_gpu_adapter_parity.py is what ties the two-pass side to float64."""
+    from oracle import adapter_ref
+    from spfsplatv2_amd import synthetic as syn
+    b = syn.make_batch("REF2V", 1, 2, seed=4243)
+    assert tuple(b.harmonics.shape) == (1, 131072, 3, 25) and tuple(b.image_shape) == (256, 256)
+    y = (b.scales.double() / 0.001).clamp_min(1e-12)
+    raw_scales = torch.where(y > 20.0, y, torch.log(torch.expm1(y.clamp_max(20.0)))).float()
+    head = torch.cat((torch.randn(1, 131072, 1, generator=torch.Generator().manual_seed(5)), raw_scales, b.rotations,
+                      (b.harmonics / adapter_ref.sh_mask(4)).reshape(1, 131072, 75)), dim=-1).cuda()
+    assert tuple(head.shape) == (1, 131072, 83)
+    _fused_against_two_pass(b.to("cuda"), head, 4, True, torch.Generator("cuda").manual_seed(7))
+
+
+def _fused_against_two_pass(b, head, deg, strided, gen):
+    """`b`: the batch on the device; `head` [S, G, 1 + 7 + 3K]: the head output (density first) the raw rows live in."""
+    import spfsplatv2_amd as spf
+    from spfsplatv2_amd import adapter
+    S, views = b.extrinsics.shape[:2]
+    H, W = b.image_shape
+    cfg = adapter.GaussianAdapterCfg(0.5, 15.0, deg)
+    plain, fused = adapter.UnifiedGaussianAdapter(cfg).cuda(), adapter.UnifiedGaussianAdapter(cfg, fuse_into_decoder=True).cuda()
     dec = spf.get_decoder(spf.DecoderSplattingCUDACfg("splatting_cuda", [0.1, 0.2, 0.3], True, True, True)).cuda()
     dec.auto_plan = None
     dec.sh_band4 = deg == 4
-    w = torch.rand(2, views, 3, 64, 48, device="cuda", generator=gen)
+    w = torch.rand(S, views, 3, H, W, device="cuda", generator=gen)
 
     def run(ad, raw_leaf, raw_in):
         leaves = {"means": b.means.clone().requires_grad_(True), "opacities": b.opacities.clone().requires_grad_(True),
@@ -145,10 +171,12 @@ def test_adapter_fused_into_the_decoder_is_the_two_pass_path(hip_lib, deg, views
 
 def test_adapter_fused_into_the_decoder_against_the_oracle(hip_lib):
     """The fused path held against the ORACLE, not against the product's other path: raw rows -> a float64 torch
-    restatement of UnifiedGaussianAdapter.forward (gaussian_adapter.py:122-150: 0.001 softplus clamped at 0.3, q / (|q| +
-    eps), raw x sh_mask) -> oracle/splat_ref.py, its gradients chained back to the raw channels by autograd; the usual
-    gates (RGB 1e-4, gradients 1e-3 of scale and 1e-2 per element, radii exact, knife-edge pixels masked on both sides)."""
+    restatement of UnifiedGaussianAdapter.forward (oracle/adapter_ref.py, gaussian_adapter.py:122-150: 0.001 softplus
+    clamped at 0.3, q / (|q| + eps), raw x sh_mask) -> oracle/splat_ref.py, its gradients chained back to the raw
+    channels by autograd; the usual gates (RGB 1e-4, gradients 1e-3 of scale and 1e-2 per element, radii exact,
+    knife-edge pixels masked on both sides)."""
     import spfsplatv2_amd as spf
+    from oracle import adapter_ref
     from spfsplatv2_amd import adapter, synthetic as syn
     K, S, V, G = 25, 2, 2, 1200
     batch = syn.make_batch("TEST", S, V, seed=77, s_mult=10.0, G=G, K=K, image_hw=(64, 48))
@@ -164,9 +192,7 @@ def test_adapter_fused_into_the_decoder_against_the_oracle(hip_lib):
     mask64, eps = fused.sh_mask.double().cpu(), 1e-8
 
     def adapter64(r):                                          # gaussian_adapter.py:122-150, float64
-        scales = (0.001 * torch.nn.functional.softplus(r[..., :3])).clamp_max(0.3)
-        rot = r[..., 3:7] / (r[..., 3:7].norm(dim=-1, keepdim=True) + eps)
-        return scales, rot, r[..., 7:].reshape(*r.shape[:-1], 3, K) * mask64
+        return adapter_ref.adapter_forward(r, mask64, eps)
 
     with torch.no_grad():
         sc, ro, sh = adapter64(raw.double())
