@@ -27,6 +27,8 @@
  *                           curope/kernels.cu:84-108 (in place, forward and backward).
  *   spf_reproj_*            LossReproj.forward (src/loss/loss_reproj.py:53-101, project_to_cam in
  *                           src/misc/cam_utils.py:289-307) and its autograd backward, for all context views at once.
+ *   spf_ssim_*, spf_psnr_*  ssim / SSIM (src/loss/loss_ssim.py:58-189) with its autograd backward, and compute_ssim /
+ *                           compute_psnr (src/evaluation/metrics.py:11-52), for a whole batch of images on the device.
  *
  * Return value of every int function: 0 = success, otherwise a negative SPF_E_* code;
  * spf_last_error() returns a host string describing the most recent failure on this thread.
@@ -400,6 +402,43 @@ int spf_reproj_forward(const SpfReproj* args, void* partial, float* loss, float*
  * gpartial is needed (and only then) when one of them is given. */
 int spf_reproj_backward(const SpfReproj* args, const float* scale, const float* dL_dloss, float* dL_dpts3d,
                         float* gpartial, float* dL_dposes, float* dL_dintrinsics, void* stream);
+
+/* SSIM (ssim / SSIM, src/loss/loss_ssim.py:58-189, and compute_ssim, src/evaluation/metrics.py:36-52) of X, Y [N,C,H,W]
+ * contiguous float32, every H x W plane on its own.  With the 1-D window win[0 .. ws) (ws odd, 3 .. 33) applied along
+ * both axes over the VALID region, n_valid = (H - ws + 1)(W - ws + 1) positions, and E[.] the filtered moments:
+ *   mu_x = E[x], mu_y = E[y], s_x = cov_norm (E[xx] - mu_x^2), s_y likewise, s_xy = cov_norm (E[xy] - mu_x mu_y)
+ *   S = (2 mu_x mu_y + C1) / (mu_x^2 + mu_y^2 + C1) * (2 s_xy + C2) / (s_x + s_y + C2)
+ *   plane_mean[n,c] = sum S / n_valid
+ *   out: size_average ? mean over all planes (1 float) : mean over the channels (N floats); with `nonnegative` each
+ *   plane's mean goes through relu first.
+ * cov_norm = 1 is the reference's `_ssim`; cov_norm = 121/120 with ws = 11 is scikit-image's Gaussian-weighted
+ * structural_similarity (sample covariance), which compute_ssim calls.  The moment maps and the S map stay in LDS and
+ * registers.  No atomics, no allocation, no synchronisation; results are run-to-run identical and a plane's numbers do
+ * not depend on the other planes of the call.  Planes may start at any 4-byte aligned address. */
+#define SPF_SSIM_MAX_WIN 33
+typedef struct SpfSsim {
+    const float* X;
+    const float* Y;
+    int32_t N, C, H, W;
+    int32_t ws;                   /* window length: odd, 3 .. SPF_SSIM_MAX_WIN, <= H and <= W */
+    float C1, C2, cov_norm;
+    int32_t size_average;         /* 0: out[N]; otherwise out[1] */
+    int32_t nonnegative;          /* relu on every plane's mean */
+    float win[SPF_SSIM_MAX_WIN];  /* the window's weights, by value; entries from ws on are ignored */
+} SpfSsim;
+/* Scratch sizing (host only, no GPU): the number of (tile, plane) slots of the forward = floats of `partial`, or -1 for
+ * sizes that the forward would reject. */
+int64_t spf_ssim_partial_blocks(int32_t N, int32_t C, int32_t H, int32_t W, int32_t ws);
+/* Forward (three launches): plane_mean [N,C] (before the relu; the backward reads it) and out. */
+int spf_ssim_forward(const SpfSsim* args, float* partial, float* plane_mean, float* out, void* stream);
+/* Backward (one launch): dL_dX and / or dL_dY [N,C,H,W] contiguous (NULL: not wanted; at least one is).  dL_dout (1 or N
+ * floats, as `out`) and plane_mean are read on the device.  The moments are recomputed from X and Y: nothing but
+ * plane_mean is kept between the passes. */
+int spf_ssim_backward(const SpfSsim* args, const float* plane_mean, const float* dL_dout, float* dL_dX, float* dL_dY,
+                      void* stream);
+/* PSNR (compute_psnr, src/evaluation/metrics.py:11-19) of N images of n floats each, contiguous:
+ * psnr[i] = -10 log10(mean((clip(gt, 0, 1) - clip(pred, 0, 1))^2)), +inf for identical images.  One launch, fixed order. */
+int spf_psnr_forward(const float* ground_truth, const float* predicted, int32_t N, int64_t n, float* psnr, void* stream);
 
 /* In-place 2-D rotary embedding.  tokens[B,N,H,D] with element strides (stride_b, stride_n, stride_h) and
  * stride(D) == 1; dtype: 0 = float32, 1 = float16, 2 = bfloat16.  positions[B / pos_div, N, 2] int64 contiguous

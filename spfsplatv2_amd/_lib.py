@@ -57,6 +57,15 @@ class SpfReproj(C.Structure):
                 ("soft_clamp", C.c_float)]
 
 
+SSIM_MAX_WIN = 33
+
+
+class SpfSsim(C.Structure):
+    _fields_ = [("X", C.c_void_p), ("Y", C.c_void_p), ("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("ws", C.c_int32), ("C1", C.c_float), ("C2", C.c_float), ("cov_norm", C.c_float),
+                ("size_average", C.c_int32), ("nonnegative", C.c_int32), ("win", C.c_float * SSIM_MAX_WIN)]
+
+
 # Every symbol include/spfsplat_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "spf_abi_version": (C.c_int, []),
@@ -93,6 +102,10 @@ SYMBOLS = {
     "spf_reproj_forward": (C.c_int, [C.POINTER(SpfReproj), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_reproj_backward": (C.c_int, [C.POINTER(SpfReproj), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    "spf_ssim_partial_blocks": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "spf_ssim_forward": (C.c_int, [C.POINTER(SpfSsim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_ssim_backward": (C.c_int, [C.POINTER(SpfSsim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_psnr_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
     "spf_adapter_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_adapter_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_void_p,

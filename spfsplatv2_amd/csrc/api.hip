@@ -31,6 +31,10 @@ hipError_t launch_mse_bwd(const float*, const float*, int64_t, float, const floa
 int64_t reproj_slots(int, int, int, int, int*);
 hipError_t launch_reproj_fwd(const SpfReproj&, void*, float*, float*, hipStream_t);
 hipError_t launch_reproj_bwd(const SpfReproj&, const float*, const float*, float*, float*, float*, float*, hipStream_t);
+int64_t ssim_slots(int, int, int, int, int);
+hipError_t launch_ssim_fwd(const SpfSsim&, float*, float*, float*, hipStream_t);
+hipError_t launch_ssim_bwd(const SpfSsim&, const float*, const float*, float*, float*, hipStream_t);
+hipError_t launch_psnr(const float*, const float*, int, int64_t, float*, hipStream_t);
 hipError_t launch_camera_fwd(const SpfCamera&, hipStream_t);
 hipError_t launch_camera_bwd(const SpfCamera&, const float*, float*, hipStream_t);
 hipError_t launch_camera_fwd_zero(const SpfCamera&, void*, uint64_t, hipStream_t);
@@ -713,6 +717,58 @@ int spf_reproj_backward(const SpfReproj* args, const float* scale, const float* 
         return fail(SPF_E_INVALID, "reproj: dL_dpts3d must be 4-byte aligned");
     SPF_HIP(spf::launch_reproj_bwd(*args, scale, dL_dloss, dL_dpts3d, gpartial, dL_dposes, dL_dintrinsics,
                                    static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+// sizes of an SSIM call: 0, or the message of the first one that is wrong
+static const char* ssim_size_error(int N, int C, int H, int W, int ws) {
+    if (N < 1 || C < 1 || H < 1 || W < 1) return "ssim: N, C, H, W must be positive";
+    if (ws < 3 || ws > SPF_SSIM_MAX_WIN) return "ssim: window size outside 3..33";
+    if (!(ws & 1)) return "ssim: window size must be odd";
+    if (H < ws || W < ws) return "ssim: image side shorter than the window";
+    if ((int64_t)H * W >= ((int64_t)1 << 31)) return "ssim: H x W is too large";
+    if ((int64_t)N * C >= ((int64_t)1 << 31)) return "ssim: N x C is too large";
+    return nullptr;
+}
+
+int64_t spf_ssim_partial_blocks(int32_t N, int32_t C, int32_t H, int32_t W, int32_t ws) {
+    if (ssim_size_error(N, C, H, W, ws)) return -1;
+    return spf::ssim_slots(N, C, H, W, ws);
+}
+
+static int check_ssim(const SpfSsim* a) {
+    if (!a) return fail(SPF_E_INVALID, "ssim: args is null");
+    if (const char* e = ssim_size_error(a->N, a->C, a->H, a->W, a->ws))
+        return fail(SPF_E_INVALID, "%s (got N %d C %d H %d W %d ws %d)", e, a->N, a->C, a->H, a->W, a->ws);
+    if (!a->X || !a->Y) return fail(SPF_E_INVALID, "ssim: null pointer");
+    if ((reinterpret_cast<uintptr_t>(a->X) | reinterpret_cast<uintptr_t>(a->Y)) & 3)
+        return fail(SPF_E_INVALID, "ssim: tensors must be 4-byte aligned");
+    return SPF_OK;
+}
+
+int spf_ssim_forward(const SpfSsim* args, float* partial, float* plane_mean, float* out, void* stream_) {
+    if (int rc = check_ssim(args)) return rc;
+    if (!partial || !plane_mean || !out) return fail(SPF_E_INVALID, "ssim: null pointer");
+    SPF_HIP(spf::launch_ssim_fwd(*args, partial, plane_mean, out, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_ssim_backward(const SpfSsim* args, const float* plane_mean, const float* dL_dout, float* dL_dX, float* dL_dY,
+                      void* stream_) {
+    if (int rc = check_ssim(args)) return rc;
+    if (!plane_mean || !dL_dout) return fail(SPF_E_INVALID, "ssim: null pointer");
+    if (!dL_dX && !dL_dY) return fail(SPF_E_INVALID, "ssim: no gradient requested");
+    if ((reinterpret_cast<uintptr_t>(dL_dX) | reinterpret_cast<uintptr_t>(dL_dY)) & 3)
+        return fail(SPF_E_INVALID, "ssim: tensors must be 4-byte aligned");
+    SPF_HIP(spf::launch_ssim_bwd(*args, plane_mean, dL_dout, dL_dX, dL_dY, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_psnr_forward(const float* ground_truth, const float* predicted, int32_t N, int64_t n, float* psnr,
+                     void* stream_) {
+    if (!ground_truth || !predicted || !psnr) return fail(SPF_E_INVALID, "psnr: null pointer");
+    if (N < 1 || n < 1) return fail(SPF_E_INVALID, "psnr: N and n must be positive (got %d, %lld)", N, (long long)n);
+    SPF_HIP(spf::launch_psnr(ground_truth, predicted, N, n, psnr, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
 
