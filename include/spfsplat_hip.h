@@ -29,6 +29,8 @@
  *                           src/misc/cam_utils.py:289-307) and its autograd backward, for all context views at once.
  *   spf_ssim_*, spf_psnr_*  ssim / SSIM (src/loss/loss_ssim.py:58-189) with its autograd backward, and compute_ssim /
  *                           compute_psnr (src/evaluation/metrics.py:11-52), for a whole batch of images on the device.
+ *   spf_lpips_*             LPIPS(net="vgg") as LossLpips (src/loss/loss_lpips.py:57-85) and compute_lpips
+ *                           (src/evaluation/metrics.py:22-33) call it, with its backward; weights come from the caller.
  *
  * Return value of every int function: 0 = success, otherwise a negative SPF_E_* code;
  * spf_last_error() returns a host string describing the most recent failure on this thread.
@@ -439,6 +441,69 @@ int spf_ssim_backward(const SpfSsim* args, const float* plane_mean, const float*
 /* PSNR (compute_psnr, src/evaluation/metrics.py:11-19) of N images of n floats each, contiguous:
  * psnr[i] = -10 log10(mean((clip(gt, 0, 1) - clip(pred, 0, 1))^2)), +inf for identical images.  One launch, fixed order. */
 int spf_psnr_forward(const float* ground_truth, const float* predicted, int32_t N, int64_t n, float* psnr, void* stream);
+
+/* LPIPS (lpips 0.1, net="vgg", lpips=True, spatial=False, evaluation mode; LossLpips, src/loss/loss_lpips.py:57-85, and
+ * compute_lpips, src/evaluation/metrics.py:22-33) of N image pairs in0[n], in1[n], each [3,H,W] float32 with contiguous
+ * planes, H, W >= 16:
+ *   x <- 2x - 1 (normalize), x <- (x - shift_c) / scale_c; VGG16 features (zero padding 1 applied AFTER that step, bias,
+ *   ReLU, 2x2 max pool in front of blocks 2..5); taps relu1_2, relu2_2, relu3_3, relu4_3, relu5_3;
+ *   per tap and pixel u = a / (||a|| + 1e-10), v likewise, d = sum_c lin[c] (u_c - v_c)^2; out[n] = sum over the taps
+ *   of the mean of d over the tap's pixels.
+ * Weights, packed once by the caller (all float32, 16-byte aligned):
+ *   wfwd   per layer l = 0..12 in order [tap = 3 dy + dx][C_in][C_out] = W_l[c_out][c_in][dy][dx]
+ *   wbwd   per layer [tap][C_out][C_in] = W_l[c_out][c_in][2 - dy][2 - dx] (the backward-data convolution)
+ *   bias   the 13 bias vectors in order; lin: the five 1x1 vectors (64, 128, 256, 512, 512) in order
+ *   shift_scale  shift[3] then scale[3]
+ * The convolutions run on the float32 matrix instructions (every output the sum of nine k-ordered fmaf chains, one per
+ * tap); activations are
+ * channels-last inside the workspace.  No atomics, no allocation, no synchronisation: results are run-to-run identical
+ * and a pair's numbers do not depend on the other pairs of the call.  Where a feature vector is all zero the 1 / ||a||
+ * term of the gradient is taken as 0. */
+typedef struct SpfLpips {
+    const float* in0;
+    const float* in1;
+    int64_t stride0, stride1;     /* floats from one image to the next (>= 3 H W) */
+    int32_t N, H, W;
+    int32_t normalize;            /* 1: inputs are in [0, 1] */
+    float weight;                 /* of the mean (spf_lpips_forward's `mean`, and the backward from it) */
+    int32_t reserved;
+    const float* wfwd;
+    const float* wbwd;
+    const float* bias;
+    const float* lin;
+    const float* shift_scale;
+} SpfLpips;
+/* Bytes of the caller-allocated workspace for n_total = 2 N images of which n_with_grad (0, N or 2 N) will go through
+ * the backward trunk; negative for unsupported sizes.  Host only. */
+int64_t spf_lpips_workspace_bytes(int32_t n_with_grad, int32_t n_total, int32_t h, int32_t w);
+/* Forward (the whole launch chain): out[N], and when `mean` is given mean[0] = weight * mean_n out[n].  The workspace
+ * keeps every activation for the backward. */
+int spf_lpips_forward(const SpfLpips* args, void* workspace, float* out, float* mean, void* stream);
+/* Backward after spf_lpips_forward on the same workspace: d_in0 and / or d_in1 [N,3,H,W] contiguous (NULL: not wanted; at
+ * least one is; only the wanted images run the backward trunk).  dL_dout: N floats, or with upstream_is_mean one float,
+ * the gradient of `mean`; read on the device. */
+int spf_lpips_backward(const SpfLpips* args, void* workspace, const float* dL_dout, int32_t upstream_is_mean,
+                       float* d_in0, float* d_in1, void* stream);
+/* The kernels of the chain one at a time, on channels-last [n,h,w,c] float32 tensors (the tests drive these).
+ * conv3x3: out[n,h,w,cout] = (relu)(conv(in where mask > 0, wpack) + bias); wpack [9][cin][cout] (a layer's slice of wfwd,
+ * or of wbwd with cin and cout swapped); mask (same shape as in) and bias may be NULL; cin % 16 == 0, cout % 64 == 0. */
+int spf_lpips_conv3x3(const float* in, const float* mask, const float* wpack, const float* bias, float* out, int32_t n,
+                      int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t relu, void* stream);
+/* First layer on args->in0 (N images, [3,H,W] planes) -> out [N,H,W,64]; and its backward-data: g, act [N,H,W,64] ->
+ * d_in0 [N,3,H,W], g counted where act > 0. */
+int spf_lpips_conv1_forward(const SpfLpips* args, float* out, void* stream);
+int spf_lpips_conv1_backward(const SpfLpips* args, const float* g, const float* act, float* d_in0, void* stream);
+/* 2x2 max pool (floor mode) [n,h,w,c] -> [n,h/2,w/2,c], c % 4 == 0; backward: inout [n,h,w,c] += gp routed to the first
+ * maximum (row-major) of each window of act. */
+int spf_lpips_pool_forward(const float* in, float* out, int32_t n, int32_t h, int32_t w, int32_t c, void* stream);
+int spf_lpips_pool_backward(const float* gp, const float* act, float* inout, int32_t n, int32_t h, int32_t w, int32_t c,
+                            void* stream);
+/* One tap of the head on fa, fb [n,hw,c] (c = 64, 128, 256 or 512): out[n] = mean over the pixels of d; partial:
+ * n * ceil(hw / 64) floats of scratch.  Backward: d_a and / or d_b [n,hw,c] from the upstream gradient up[n]. */
+int spf_lpips_head_forward(const float* fa, const float* fb, const float* lin, int32_t n, int32_t hw, int32_t c,
+                           float* partial, float* out, void* stream);
+int spf_lpips_head_backward(const float* fa, const float* fb, const float* lin, int32_t n, int32_t hw, int32_t c,
+                            const float* up, float* d_a, float* d_b, void* stream);
 
 /* In-place 2-D rotary embedding.  tokens[B,N,H,D] with element strides (stride_b, stride_n, stride_h) and
  * stride(D) == 1; dtype: 0 = float32, 1 = float16, 2 = bfloat16.  positions[B / pos_div, N, 2] int64 contiguous

@@ -66,6 +66,13 @@ class SpfSsim(C.Structure):
                 ("size_average", C.c_int32), ("nonnegative", C.c_int32), ("win", C.c_float * SSIM_MAX_WIN)]
 
 
+class SpfLpips(C.Structure):
+    _fields_ = [("in0", C.c_void_p), ("in1", C.c_void_p), ("stride0", C.c_int64), ("stride1", C.c_int64),
+                ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("normalize", C.c_int32), ("weight", C.c_float),
+                ("reserved", C.c_int32), ("wfwd", C.c_void_p), ("wbwd", C.c_void_p), ("bias", C.c_void_p),
+                ("lin", C.c_void_p), ("shift_scale", C.c_void_p)]
+
+
 # Every symbol include/spfsplat_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "spf_abi_version": (C.c_int, []),
@@ -106,6 +113,22 @@ SYMBOLS = {
     "spf_ssim_forward": (C.c_int, [C.POINTER(SpfSsim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_ssim_backward": (C.c_int, [C.POINTER(SpfSsim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_psnr_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    "spf_lpips_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "spf_lpips_forward": (C.c_int, [C.POINTER(SpfLpips), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_lpips_backward": (C.c_int, [C.POINTER(SpfLpips), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "spf_lpips_conv3x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "spf_lpips_conv1_forward": (C.c_int, [C.POINTER(SpfLpips), C.c_void_p, C.c_void_p]),
+    "spf_lpips_conv1_backward": (C.c_int, [C.POINTER(SpfLpips), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_lpips_pool_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_void_p]),
+    "spf_lpips_pool_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_void_p]),
+    "spf_lpips_head_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_lpips_head_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_adapter_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_adapter_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_void_p,

@@ -35,6 +35,19 @@ int64_t ssim_slots(int, int, int, int, int);
 hipError_t launch_ssim_fwd(const SpfSsim&, float*, float*, float*, hipStream_t);
 hipError_t launch_ssim_bwd(const SpfSsim&, const float*, const float*, float*, float*, hipStream_t);
 hipError_t launch_psnr(const float*, const float*, int, int64_t, float*, hipStream_t);
+int64_t lpips_workspace_bytes(int, int, int, int);
+size_t lpips_pack_offset(int);
+hipError_t launch_lpips_fwd(const SpfLpips&, float*, float*, float*, hipStream_t);
+hipError_t launch_lpips_bwd(const SpfLpips&, float*, const float*, int, float*, float*, hipStream_t);
+hipError_t launch_lpips_conv(const float*, const float*, const float*, const float*, float*, int, int, int, int, int, int,
+                             hipStream_t);
+hipError_t launch_lpips_conv1(const SpfLpips&, int, float*, hipStream_t);
+hipError_t launch_lpips_conv1_bwd(const SpfLpips&, const float*, const float*, int, float*, int, float*, hipStream_t);
+hipError_t launch_lpips_pool(const float*, float*, int, int, int, int, hipStream_t);
+hipError_t launch_lpips_pool_bwd(const float*, const float*, float*, int, int, int, int, hipStream_t);
+hipError_t launch_lpips_head_single(const float*, const float*, const float*, int, int, int, float*, float*, hipStream_t);
+hipError_t launch_lpips_head_bwd(const float*, const float*, const float*, int, int, int, const float*, int, float, float*,
+                                 float*, hipStream_t);
 hipError_t launch_camera_fwd(const SpfCamera&, hipStream_t);
 hipError_t launch_camera_bwd(const SpfCamera&, const float*, float*, hipStream_t);
 hipError_t launch_camera_fwd_zero(const SpfCamera&, void*, uint64_t, hipStream_t);
@@ -802,6 +815,134 @@ int spf_rope2d_pair(void* tokens, void* tokens2, const int64_t* positions, int32
     if (!tokens2) return fail(SPF_E_INVALID, "tokens2 is null");
     return rope2d_impl(tokens, tokens2, positions, B, N, H, D, stride_b, stride_n, stride_h, pos_div, dtype, base, fwd,
                        stream_);
+}
+
+// sizes of an LPIPS call: 0, or the message of the first one that is wrong
+static const char* lpips_size_error(int N, int H, int W) {
+    if (N < 1 || N > 65535) return "lpips: N must be 1 .. 65535";
+    if (H < 16 || W < 16) return "lpips: image side shorter than 16 (the fifth tap would be empty)";
+    if ((int64_t)2 * N * H * W * 64 >= ((int64_t)1 << 40)) return "lpips: N x H x W is too large";
+    if ((int64_t)2 * N * H * W >= ((int64_t)1 << 31) - 256) return "lpips: N x H x W is too large";
+    return nullptr;
+}
+
+int64_t spf_lpips_workspace_bytes(int32_t n_with_grad, int32_t n_total, int32_t h, int32_t w) {
+    if (n_total < 2 || (n_total & 1) || lpips_size_error(n_total / 2, h, w)) return -1;
+    if (n_with_grad != 0 && n_with_grad != n_total / 2 && n_with_grad != n_total) return -1;
+    return spf::lpips_workspace_bytes(n_with_grad, n_total, h, w);
+}
+
+static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+static int check_lpips(const SpfLpips* a, bool first_only) {
+    if (!a) return fail(SPF_E_INVALID, "lpips: args is null");
+    if (const char* e = lpips_size_error(a->N, a->H, a->W))
+        return fail(SPF_E_INVALID, "%s (got N %d H %d W %d)", e, a->N, a->H, a->W);
+    if (!a->in0 || (!first_only && !a->in1)) return fail(SPF_E_INVALID, "lpips: null image pointer");
+    const int64_t img = (int64_t)3 * a->H * a->W;
+    if (a->stride0 < img || (!first_only && a->stride1 < img))
+        return fail(SPF_E_INVALID, "lpips: image stride shorter than 3 H W");
+    if ((reinterpret_cast<uintptr_t>(a->in0) | reinterpret_cast<uintptr_t>(a->in1)) & 3)
+        return fail(SPF_E_INVALID, "lpips: images must be 4-byte aligned");
+    if (!a->wfwd || !a->wbwd || !a->bias || !a->shift_scale || (!first_only && !a->lin))
+        return fail(SPF_E_INVALID, "lpips: null weight pointer");
+    if (misaligned16(a->wfwd) || misaligned16(a->wbwd)) return fail(SPF_E_INVALID, "lpips: weight packs must be 16-byte aligned");
+    return SPF_OK;
+}
+
+int spf_lpips_forward(const SpfLpips* args, void* workspace, float* out, float* mean, void* stream_) {
+    if (int rc = check_lpips(args, false)) return rc;
+    if (!workspace || !out) return fail(SPF_E_INVALID, "lpips: null pointer");
+    if (misaligned16(workspace)) return fail(SPF_E_INVALID, "lpips: workspace must be 16-byte aligned");
+    SPF_HIP(spf::launch_lpips_fwd(*args, static_cast<float*>(workspace), out, mean, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_lpips_backward(const SpfLpips* args, void* workspace, const float* dL_dout, int32_t upstream_is_mean,
+                       float* d_in0, float* d_in1, void* stream_) {
+    if (int rc = check_lpips(args, false)) return rc;
+    if (!workspace || !dL_dout) return fail(SPF_E_INVALID, "lpips: null pointer");
+    if (misaligned16(workspace)) return fail(SPF_E_INVALID, "lpips: workspace must be 16-byte aligned");
+    if (!d_in0 && !d_in1) return fail(SPF_E_INVALID, "lpips: no gradient requested");
+    SPF_HIP(spf::launch_lpips_bwd(*args, static_cast<float*>(workspace), dL_dout, upstream_is_mean ? 1 : 0, d_in0, d_in1,
+                                  static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+static int check_lpips_map(const char* what, int32_t n, int32_t h, int32_t w, int32_t c, int32_t cmul) {
+    if (n < 1 || h < 1 || w < 1 || c < 1) return fail(SPF_E_INVALID, "%s: n, h, w, c must be positive", what);
+    if (c % cmul) return fail(SPF_E_INVALID, "%s: channel count %d is not a multiple of %d", what, c, cmul);
+    if ((int64_t)n * h * w >= ((int64_t)1 << 31) - 256) return fail(SPF_E_INVALID, "%s: n x h x w is too large", what);
+    return SPF_OK;
+}
+
+int spf_lpips_conv3x3(const float* in, const float* mask, const float* wpack, const float* bias, float* out, int32_t n,
+                      int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t relu, void* stream_) {
+    if (int rc = check_lpips_map("lpips conv3x3", n, h, w, cin, 16)) return rc;
+    if (cout < 64 || cout % 64) return fail(SPF_E_INVALID, "lpips conv3x3: cout %d is not a multiple of 64", cout);
+    if (!in || !wpack || !out) return fail(SPF_E_INVALID, "lpips conv3x3: null pointer");
+    if (misaligned16(in) || misaligned16(mask) || misaligned16(wpack) || misaligned16(out))
+        return fail(SPF_E_INVALID, "lpips conv3x3: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_lpips_conv(in, mask, wpack, bias, out, n, h, w, cin, cout, relu ? 1 : 0,
+                                   static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_lpips_conv1_forward(const SpfLpips* args, float* out, void* stream_) {
+    if (int rc = check_lpips(args, true)) return rc;
+    if (!out || misaligned16(out)) return fail(SPF_E_INVALID, "lpips conv1: out is null or not 16-byte aligned");
+    SPF_HIP(spf::launch_lpips_conv1(*args, args->N, out, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_lpips_conv1_backward(const SpfLpips* args, const float* g, const float* act, float* d_in0, void* stream_) {
+    if (int rc = check_lpips(args, true)) return rc;
+    if (!g || !act || !d_in0) return fail(SPF_E_INVALID, "lpips conv1 backward: null pointer");
+    if (misaligned16(g) || misaligned16(act)) return fail(SPF_E_INVALID, "lpips conv1 backward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_lpips_conv1_bwd(*args, g, act, args->N, d_in0, args->N, nullptr, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_lpips_pool_forward(const float* in, float* out, int32_t n, int32_t h, int32_t w, int32_t c, void* stream_) {
+    if (int rc = check_lpips_map("lpips pool", n, h, w, c, 4)) return rc;
+    if (!in || !out || misaligned16(in) || misaligned16(out))
+        return fail(SPF_E_INVALID, "lpips pool: null or not 16-byte aligned pointer");
+    SPF_HIP(spf::launch_lpips_pool(in, out, n, h, w, c, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_lpips_pool_backward(const float* gp, const float* act, float* inout, int32_t n, int32_t h, int32_t w, int32_t c,
+                            void* stream_) {
+    if (int rc = check_lpips_map("lpips pool backward", n, h, w, c, 4)) return rc;
+    if (!gp || !act || !inout || misaligned16(gp) || misaligned16(act) || misaligned16(inout))
+        return fail(SPF_E_INVALID, "lpips pool backward: null or not 16-byte aligned pointer");
+    SPF_HIP(spf::launch_lpips_pool_bwd(gp, act, inout, n, h, w, c, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+static int check_lpips_head(int32_t n, int32_t hw, int32_t c) {
+    if (n < 1 || hw < 1) return fail(SPF_E_INVALID, "lpips head: n and hw must be positive");
+    if (c != 64 && c != 128 && c != 256 && c != 512) return fail(SPF_E_INVALID, "lpips head: c must be 64, 128, 256 or 512 (got %d)", c);
+    if ((int64_t)n * hw >= ((int64_t)1 << 31) - 256) return fail(SPF_E_INVALID, "lpips head: n x hw is too large");
+    if (n > 65535) return fail(SPF_E_INVALID, "lpips head: more than 65535 pairs");
+    return SPF_OK;
+}
+
+int spf_lpips_head_forward(const float* fa, const float* fb, const float* lin, int32_t n, int32_t hw, int32_t c,
+                           float* partial, float* out, void* stream_) {
+    if (int rc = check_lpips_head(n, hw, c)) return rc;
+    if (!fa || !fb || !lin || !partial || !out) return fail(SPF_E_INVALID, "lpips head: null pointer");
+    SPF_HIP(spf::launch_lpips_head_single(fa, fb, lin, n, hw, c, partial, out, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_lpips_head_backward(const float* fa, const float* fb, const float* lin, int32_t n, int32_t hw, int32_t c,
+                            const float* up, float* d_a, float* d_b, void* stream_) {
+    if (int rc = check_lpips_head(n, hw, c)) return rc;
+    if (!fa || !fb || !lin || !up) return fail(SPF_E_INVALID, "lpips head: null pointer");
+    if (!d_a && !d_b) return fail(SPF_E_INVALID, "lpips head: no gradient requested");
+    SPF_HIP(spf::launch_lpips_head_bwd(fa, fb, lin, n, hw, c, up, 0, 0.f, d_a, d_b, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
 }
 
 int spf_stage_timing_enable(int32_t mask) {

@@ -12,6 +12,10 @@ here                   reference (/root/reference/src/loss/)
 ``LossReprojCfgWrapper`` loss_reproj.py:21-23
 ``LossReproj``         loss_reproj.py:29-101 (+ project_to_cam, misc/cam_utils.py:289-307): the reprojection loss
 ``reproj_loss``        the same as a function; also takes ``[b,v,h,w,3]`` and returns one loss per view in one call
+``LossLpipsCfg``       loss_lpips.py:16-19
+``LossLpipsCfgWrapper`` loss_lpips.py:22-24
+``LossLpips``          loss_lpips.py:57-85: ``weight * LPIPS(net="vgg")(prediction, image, normalize=True).mean()`` over
+                       the ``b v`` images, 0 before ``apply_after_step``; the network is spfsplatv2_amd/lpips.py
 =====================  =========================================================================
 
 The reference evaluates the expression with eager PyTorch (four kernels forward, four backward over the rendered
@@ -326,3 +330,39 @@ class LossReproj(Loss[LossReprojCfg, LossReprojCfgWrapper]):
                            circle_schedule=self.cfg.circle_schedule, detach_pts3d=detach_pts3d,
                            hard_clamp=self.repro_loss_hard_clamp, soft_clamp=self.soft_clamp,
                            soft_clamp_min=self.soft_clamp_min)
+
+
+# ---- LPIPS loss --------------------------------------------------------------------------------------------------
+@dataclass
+class LossLpipsCfg:
+    weight: float
+    apply_after_step: int
+
+
+@dataclass
+class LossLpipsCfgWrapper:
+    lpips: LossLpipsCfg
+
+
+class LossLpips(Loss[LossLpipsCfg, LossLpipsCfgWrapper]):
+    """The reference builds ``LPIPS(net="vgg")`` (which may download weights) in its constructor; here the weights come
+    from `weights` or ``$SPF_LPIPS_WEIGHTS`` (spfsplatv2_amd.lpips.resolve_weights) and resolve on the first step that
+    applies the loss, so constructing it needs no file.  The mean over the images and its backward are taken inside the
+    library."""
+
+    def __init__(self, cfg: LossLpipsCfgWrapper, weights=None) -> None:
+        super().__init__(cfg)
+        self.weights = weights
+
+    def forward(self, prediction: Tensor, image: Tensor, gaussians, global_step: int) -> Tensor:
+        if global_step < self.cfg.apply_after_step:           # not applied yet (loss_lpips.py:74-76)
+            return torch.tensor(0, dtype=torch.float32, device=image.device)
+        from .lpips import LpipsWeights, _check_pair, lpips_mean, resolve_weights
+        if prediction.dim() != 5 or image.dim() != 5:
+            raise ValueError(f"LossLpips: prediction and image must be [b,v,3,h,w], got {tuple(prediction.shape)} and "
+                             f"{tuple(image.shape)}")
+        pred, img = prediction.flatten(0, 1), image.flatten(0, 1)
+        _check_pair("LossLpips", pred, img)
+        if not isinstance(self.weights, LpipsWeights):
+            self.weights = resolve_weights(self.weights)
+        return lpips_mean(pred, img, self.weights, normalize=True, weight=self.cfg.weight)

@@ -1,4 +1,5 @@
-"""Evaluation metrics on the HIP library: host mirror of the reference's ``compute_ssim`` and ``compute_psnr``.
+"""Evaluation metrics on the HIP library: host mirror of the reference's ``compute_psnr``, ``compute_ssim`` and
+``compute_lpips``.
 
 ================  ========================================================================================
 here              reference (/root/reference/src/evaluation/metrics.py)
@@ -6,13 +7,16 @@ here              reference (/root/reference/src/evaluation/metrics.py)
 ``compute_psnr``  metrics.py:11-19: ``-10 log10(mean((clip(gt) - clip(pred))^2))`` per image
 ``compute_ssim``  metrics.py:36-52: scikit-image's ``structural_similarity(win_size=11, gaussian_weights=True,
                   channel_axis=0, data_range=1.0)`` per image, mean over the channels
+``compute_lpips`` metrics.py:22-33: ``LPIPS(net="vgg").forward(ground_truth, predicted, normalize=True)[:, 0, 0, 0]``
 ================  ========================================================================================
 
 The reference copies every image to the host and filters it with scikit-image on one CPU core.  Here both metrics stay on
 the device: no host copy, no synchronisation, results in ``predicted.dtype`` on ``predicted.device``.  skimage's
 Gaussian-weighted SSIM crops 5 pixels from every border after a reflect-padded filter of radius 5, so what it averages
 is the valid convolution of the SSIM kernels (spfsplatv2_amd/csrc/ssim.hip) with a window of 11, sigma 1.5, and its
-sample covariance is the factor cov_norm = 121/120.  ``compute_lpips`` needs VGG weights and is not provided.
+sample covariance is the factor cov_norm = 121/120.  ``compute_lpips`` runs spfsplatv2_amd/lpips.py (pinned to a
+restatement of the published method, tests/lpips_oracle.py, not to the ``lpips`` package itself); its VGG weights come from
+the caller: ``weights=`` or ``$SPF_LPIPS_WEIGHTS`` (lpips.py says how to make the file).  Nothing is ever downloaded.
 """
 from __future__ import annotations
 
@@ -65,3 +69,13 @@ def compute_psnr(ground_truth: Tensor, predicted: Tensor) -> Tensor:
         _lib.check(lib.spf_psnr_forward(C.c_void_p(gt.data_ptr()), C.c_void_p(pred.data_ptr()), pred.shape[0],
                                         pred[0].numel(), C.c_void_p(out.data_ptr()), stream), "spf_psnr_forward")
     return out.to(predicted.dtype)
+
+
+@torch.no_grad()
+def compute_lpips(ground_truth: Tensor, predicted: Tensor, weights=None) -> Tensor:
+    """[batch, 3, height, width] x 2 in [0, 1] -> [batch]: LPIPS(net="vgg") of every pair, ground truth first."""
+    from .lpips import _check_pair as check_lpips_pair, lpips
+    _check_pair("compute_lpips", ground_truth, predicted)
+    check_lpips_pair("compute_lpips", ground_truth, predicted)
+    value = lpips(ground_truth.detach(), predicted.detach(), weights, normalize=True)
+    return value[:, 0, 0, 0].to(predicted.dtype)
