@@ -116,12 +116,15 @@ def orthographic_callsite_args(extrinsics, width, height, near, far, image_shape
 
 def decoder_forward(means, harmonics, opacities, rotations, scales, extrinsics, intrinsics, near, far, image_shape,
                     background_color, make_scale_invariant=True, dtype=torch.float32, want_fragile=False,
-                    band4=False, want_radii_fragile=False):
+                    band4=False, want_radii_fragile=False, decisions=None, force_keep=None):
     """DecoderSplattingCUDA.forward (decoder_splatting_cuda.py:41-78) on the CPU oracle.
 
     [b,g,...] Gaussians, [b,v,...] cameras -> color [b,v,3,h,w], depth [b,v,h,w] (already x near),
     alpha [b,v,1,h,w], radii [b,v,g] (+ fragile [b,v,h,w]) (+ radii_fragile [b,v,g]).  Differentiable w.r.t. its
     float inputs.  `band4`: evaluate SH band 4 when d_sh = 25 (see splat_ref.SH_C4).
+    `decisions`: a list that receives one dict per (scene, view), scene-major (splat_ref.composite: what was decided
+    next to a threshold; needs `want_fragile`).  `force_keep`: a list of b*v entries, each None or
+    {(tx, ty): bool [256, L]}, the keep masks that render is evaluated with.
     """
     b, v = extrinsics.shape[:2]
     rep = lambda t: t[:, None].expand(b, v, *t.shape[1:]).reshape(b * v, *t.shape[1:])   # the `repeat`s
@@ -130,13 +133,18 @@ def decoder_forward(means, harmonics, opacities, rotations, scales, extrinsics, 
                          far.reshape(-1), image_shape, bg[None].expand(b * v, 3), rep(means), rep(harmonics),
                          rep(opacities), rep(rotations), rep(scales), scale_invariant=make_scale_invariant)
     cols, deps, alps, rads, frs, rfr = [], [], [], [], [], []
-    for a in args:
+    for i, a in enumerate(args):
+        dec = None
+        if decisions is not None:
+            dec = {}
+            decisions.append(dec)
         c = lambda t: None if t is None else t.to(dtype)
         out = splat_ref.rasterize(c(a["means3D"]), c(a["scales"]), c(a["rotations"]), c(a["opacities"]),
                                   c(a["shs"]), c(a["colors_precomp"]), c(a["viewmatrix"]), c(a["projmatrix"]),
                                   c(a["bg"]), a["tanfovx"], a["tanfovy"], a["image_height"], a["image_width"],
                                   a["sh_degree"], a["scale_modifier"], want_fragile=want_fragile, band4=band4,
-                                  want_radii_fragile=want_radii_fragile)
+                                  want_radii_fragile=want_radii_fragile, decisions=dec,
+                                  force_keep=None if force_keep is None else force_keep[i])
         cols.append(out[0]); deps.append(out[1]); alps.append(out[2]); rads.append(out[3])
         if want_fragile:
             frs.append(out[4])

@@ -280,11 +280,24 @@ def tile_lists(pr: Projected, H: int, W: int):
 
 
 def composite(pr: Projected, bg: Tensor, H: int, W: int, want_fragile: bool = False,
-              frozen: dict | None = None, capture: dict | None = None):
+              frozen: dict | None = None, capture: dict | None = None,
+              decisions: dict | None = None, force_keep: dict | None = None):
     """Tile-wise front-to-back alpha compositing (stage R6).
 
     Returns image[3,H,W], depth[1,H,W], alpha[1,H,W] (+ fragile[H,W] bool if asked).
     `frozen` / `capture`: see `project` (here: the offset that turns o*exp(power) into min(0.99, .), per tile).
+    `decisions` / `force_keep` (tests/branch_explain.py; independent of `frozen` / `capture`, the gradient conventions
+    stay as they are): which of a pixel's list entries are composited is a set of DISCRETE decisions (power <= 0,
+    alpha >= 1/255, the 1e-4 stop), collected in `keep`.
+    * `decisions={}` (needs `want_fragile`) is filled with what was decided next to a threshold:
+      decisions["tiles"][(tx, ty)] for every tile with a pixel inside one of the three windows -- `rows` (the tile-local
+      indices of those pixels) and, for these rows only (a [256, L] float64 record of every tile of a full-size case
+      would be gigabytes), the detached `alpha`, `pow_ok` (power <= 0), `valid`, `near_alpha`, `near_pow`, `near_T`;
+      the whole tile's `keep` [256, L]; the contributors' `ids`, `rgb` [L, 3] and `depth` [L];
+      decisions["other_tiles"][(tx, ty)]: [256] bool, pixels flagged for a reason that is no keep decision (the smooth
+      exponent-rounding limit, a depth-order tie).
+    * `force_keep={(tx, ty): bool [256, L]}` replaces `keep` of those tiles: the image and, through autograd, the
+      gradients are those of the float64 (or float32) function with exactly these entries composited.
     """
     dt = pr.xy.dtype
     rows_c = [[None] * ((W + TILE - 1) // TILE) for _ in range((H + TILE - 1) // TILE)]
@@ -328,6 +341,10 @@ def composite(pr: Projected, bg: Tensor, H: int, W: int, want_fragile: bool = Fa
                 # cumprod is monotone, so once an entry is refused all later ones are too
                 stopped = torch.cumsum((valid & ~keep).to(torch.int32), dim=1) > 0
                 keep = keep & ~stopped
+                if force_keep is not None and (tx, ty) in force_keep:
+                    forced = force_keep[(tx, ty)]
+                    assert forced.dtype == torch.bool and forced.shape == keep.shape, (tx, ty, forced.shape, keep.shape)
+                    keep = forced
             a_k = torch.where(keep, alpha, torch.zeros_like(alpha))
             incl_k = torch.cumprod(1.0 - a_k, dim=1)
             T_excl = torch.cat([torch.ones_like(incl_k[:, :1]), incl_k[:, :-1]], dim=1)
@@ -364,10 +381,12 @@ def composite(pr: Projected, bg: Tensor, H: int, W: int, want_fragile: bool = Fa
                     # alpha * 4e-7 * mag; where that adds up to a visible amount no float32 evaluation of the classic
                     # formula reaches 1e-4 (the oracle's own float32 evaluation is off by 6e-5..9e-5 on the pixels
                     # this flags) -- only under splats centred hundreds of pixels away
-                    frag = frag | ((w.detach() * mag).sum(dim=1) * 4e-7 > 3e-5)
+                    smooth = (w.detach() * mag).sum(dim=1) * 4e-7 > 3e-5
+                    frag = frag | smooth
                     # the ORDER of two entries is decided by float32 depth bits (B#10): where two of a pixel's
                     # contributors are closer in depth than float32 resolves, either may come first -- flagged where
                     # swapping them would move a colour channel by more than 2e-5 (T a_i a_j |c_i - c_j|)
+                    order_tie = torch.zeros_like(frag)
                     if pr.depth_tol is not None and ids.numel() > 1:
                         zs, zt = pr.depth[ids].detach(), pr.depth_tol[ids]
                         cand = keep | first_refused
@@ -384,15 +403,30 @@ def composite(pr: Projected, bg: Tensor, H: int, W: int, want_fragile: bool = Fa
                             #  is composited at all)
                             at_stop = first_refused[:, k:] | first_refused[:, :-k]
                             swap = torch.where(at_stop, T_excl[:, :-k] * torch.maximum(a_c[:, :-k], a_c[:, k:]), swap)
-                            frag = frag | ((swap > 2e-5) & tie[None, :]).any(dim=1)
+                            hit = ((swap > 2e-5) & tie[None, :]).any(dim=1)
+                            frag = frag | hit
+                            order_tie = order_tie | hit
                     if capture is not None and "fragile_stats" in capture:      # (diagnostics: which window flags how many pixels)
                         fs = capture["fragile_stats"]
                         base = (near_alpha | near_pow | near_T).any(dim=1)
                         for name, m in (("near_alpha", near_alpha.any(dim=1)), ("near_pow", near_pow.any(dim=1)),
                                         ("near_T", near_T.any(dim=1)),
-                                        ("smooth_mag", (w.detach() * mag).sum(dim=1) * 4e-7 > 3e-5),
+                                        ("smooth_mag", smooth),
                                         ("order_or_smooth_only", frag & ~base), ("any", frag)):
                             fs[name] = fs.get(name, 0) + int(m.sum())
+                    if decisions is not None and bool(frag.any()):
+                        near = near_alpha | near_pow | near_T
+                        rows = torch.nonzero(near.any(dim=1)).flatten()
+                        # "other": flagged by the smooth term or an order tie above, whether a window flags it too or not
+                        other = smooth | order_tie
+                        if bool(other.any()):
+                            decisions.setdefault("other_tiles", {})[(tx, ty)] = other
+                        if rows.numel():
+                            decisions.setdefault("tiles", {})[(tx, ty)] = dict(
+                                rows=rows, ids=ids, alpha=alpha.detach()[rows], pow_ok=(power <= 0)[rows],
+                                valid=valid[rows], near_alpha=near_alpha[rows], near_pow=near_pow[rows],
+                                near_T=near_T[rows], keep=keep.clone(), rgb=pr.rgb[ids].detach(),
+                                depth=pr.depth[ids].detach())
             else:
                 frag = torch.zeros(n_pix, dtype=torch.bool)
         rows_c[ty][tx] = C.reshape(TILE, TILE, 3)
@@ -414,22 +448,26 @@ def rasterize(means3D: Tensor, scales: Tensor, rotations: Tensor, opacities: Ten
               viewmatrix: Tensor, projmatrix: Tensor, bg: Tensor,
               tanfovx: float, tanfovy: float, H: int, W: int,
               sh_degree: int, scale_modifier: float = 1.0, want_fragile: bool = False, band4: bool = False,
-              frozen: dict | None = None, capture: dict | None = None, want_radii_fragile: bool = False):
+              frozen: dict | None = None, capture: dict | None = None, want_radii_fragile: bool = False,
+              decisions: dict | None = None, force_keep: dict | None = None):
     """One (scene, view) render: the semantics of one ``GaussianRasterizer(settings)(...)`` call
     (/root/reference/src/model/decoder/cuda_splatting.py:124-138).
 
     Returns (image[3,H,W], depth[1,H,W], alpha[1,H,W], radii[G] int32[, fragile[H,W]]).
+    `decisions` / `force_keep`: see `composite`; here decisions["other"] [H,W] is added -- every pixel flagged for a
+    reason that is no keep decision (composite's, a tile membership, the SH clamp).
     """
     pr = project(means3D, scales, rotations, opacities, shs, colors_precomp, viewmatrix,
                  projmatrix, tanfovx, tanfovy, H, W, sh_degree, scale_modifier, band4=band4,
                  frozen=frozen, capture=capture)
-    out = composite(pr, bg, H, W, want_fragile=want_fragile, frozen=frozen, capture=capture)
+    out = composite(pr, bg, H, W, want_fragile=want_fragile, frozen=frozen, capture=capture,
+                    decisions=decisions, force_keep=force_keep)
     if want_fragile:
         # Tile membership decided by a rounding knife-edge (footprint radius within 1e-4 of an integer, or a rect
         # bound within ~1e-4 px of a tile border): only the tiles whose membership would actually change are
         # tainted, i.e. the difference between the largest and the smallest plausible rect.
         with torch.no_grad():
-            fr = out[3].clone()
+            fr = torch.zeros_like(out[3])           # what THIS stage flags (joined with composite's flags below)
             gx, gy = (W + TILE - 1) // TILE, (H + TILE - 1) // TILE
             px, py = pr.xy[:, 0].double(), pr.xy[:, 1].double()
             raw = pr.radius_raw.double()
@@ -479,6 +517,14 @@ def rasterize(means3D: Tensor, scales: Tensor, rotations: Tensor, opacities: Ten
                 al_g = torch.clamp(pr.opacity[g].detach().double() * torch.exp(pw_g.clamp(max=0.0)), max=ALPHA_MAX)
                 hit = (pw_g <= 1e-9) & (al_g >= ALPHA_MIN * (1.0 - 1e-3))
                 fr[yy[hit], xx[hit]] = True
+            if decisions is not None:
+                other = fr.clone()
+                for (tx, ty), m in decisions.get("other_tiles", {}).items():
+                    y0, x0 = ty * TILE, tx * TILE
+                    blk = m.reshape(TILE, TILE)[:max(0, min(TILE, H - y0)), :max(0, min(TILE, W - x0))]
+                    other[y0:y0 + blk.shape[0], x0:x0 + blk.shape[1]] |= blk
+                decisions["other"] = other
+            fr = fr | out[3]
         res = (out[0], out[1], out[2], pr.radii, fr)
     else:
         res = (out[0], out[1], out[2], pr.radii)

@@ -44,14 +44,20 @@ def test_parity_vs_oracle_at_full_size(hip_lib, K, s_mult):
     1/255, ...), where float32 and float64 may take different branches: a contribution of up to 1/255 appears or
     not, and so does its gradient.  Those pixels (flagged by the float64 oracle, < 2 %) are excluded from the RGB
     gate as everywhere else AND switched off in the loss of both sides, so that the gradient gate (1e-3 of the
-    tensor's scale, over every Gaussian) compares like with like."""
+    tensor's scale, over every Gaussian) compares like with like.
+    SECOND comparison, forced (util.BranchForcing): the flagged pixels are not masked but held against the float64
+    oracle on the branch the kernel took there, image and gradients, same gates.  The report line also carries the
+    float32 oracle's own unmasked `gall_*` (`oracle_f32_gall_*`) next to the product's: reported, not gated."""
     batch = syn.make_batch(config="C2", n_scenes=1, n_views=1, seed=8, K=K, s_mult=s_mult)
-    ref = util.run_oracle(batch, torch.float64, mask_fragile=True, unmasked_too=True)
-    prod = util.run_product(batch, pixel_mask=ref["pixel_mask"], unmasked_too=True)
+    ref = util.run_oracle(batch, torch.float64, mask_fragile=True, unmasked_too=True, decisions=True)
+    forcing = util.BranchForcing(batch, ref)
+    prod = util.run_product(batch, pixel_mask=ref["pixel_mask"], unmasked_too=True, after_forward=forcing.mask_for)
     rep = util.compare(prod, ref, max_fragile_frac=FRAGILE_CAP_C2)
     rep["num_pairs"] = prod["stats"].get("num_pairs")
-    _report(f"c2_full_size_K{K}", rep)
+    forced = forcing.compare(prod)
+    _report(f"c2_full_size_K{K}", {**rep, **forcing.report_entry(forced), **util.float32_gall(batch, ref)})
     assert not rep["fails"], rep
+    assert not forced["fails"], forced
     assert prod["stats"]["num_pairs"] > 60000
 
 
@@ -68,12 +74,17 @@ def test_parity_vs_oracle(hip_lib, name):
     batch = syn.make_batch(**kw)
     # knife-edge pixels (flagged by the float64 oracle) are excluded from the RGB gate and switched off in the loss of
     # both sides, so that the gradient gate compares like with like (see test_parity_vs_oracle_at_full_size)
-    ref = util.run_oracle(batch, torch.float64, background=bg, scale_invariant=si, mask_fragile=True, unmasked_too=True)
-    prod = util.run_product(batch, background=bg, scale_invariant=si, pixel_mask=ref["pixel_mask"], unmasked_too=True)
+    ref = util.run_oracle(batch, torch.float64, background=bg, scale_invariant=si, mask_fragile=True, unmasked_too=True,
+                          decisions=True)
+    forcing = util.BranchForcing(batch, ref, background=bg, scale_invariant=si)
+    prod = util.run_product(batch, background=bg, scale_invariant=si, pixel_mask=ref["pixel_mask"], unmasked_too=True,
+                            after_forward=forcing.mask_for)
     rep = util.compare(prod, ref)
     rep["num_pairs"] = prod["stats"].get("num_pairs")
-    _report(name, rep)
+    forced = forcing.compare(prod)        # the flagged pixels on the branch the kernel took (util.BranchForcing)
+    _report(name, {**rep, **forcing.report_entry(forced)})
     assert not rep["fails"], rep
+    assert not forced["fails"], forced
     # (util.compare also gates: radii bit-exact off the Gaussian's own rounding knife-edges, and the number of pixels
     # of the UNMASKED image that are off by > 1e-4 is bounded by the number of flagged pixels)
     assert rep["radii_mismatch"] == 0 and rep["bad_frac_all"] <= rep["fragile_frac"]

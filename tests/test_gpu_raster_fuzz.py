@@ -8,22 +8,7 @@ from tests import util
 pytestmark = pytest.mark.gpu
 
 
-def _random_case(seed: int):
-    g = torch.Generator().manual_seed(seed)
-    ri = lambda lo, hi: int(torch.randint(lo, hi + 1, (1,), generator=g))
-    S, V = ri(1, 3), ri(1, 3)
-    K = [1, 4, 9, 16, 25][ri(0, 4)]
-    G = ri(1, 2500)
-    hw = (ri(5, 90), ri(5, 120))
-    s_mult = [1.0, 4.0, 15.0, 60.0, 250.0][ri(0, 4)]
-    bg = tuple(float(x) for x in torch.rand(3, generator=g))
-    si = bool(ri(0, 1))
-    batch = syn.make_batch("TEST", S, V, seed=seed, s_mult=s_mult, G=G, K=K, image_hw=hw)
-    # move some cameras so that part of the scene is behind / very close to the camera, vary near per view
-    batch.extrinsics[..., 2, 3] += (torch.rand(S, V, generator=g) - 0.3) * 3.0
-    batch.near = batch.near * (0.5 + torch.rand(S, V, generator=g) * 2.0)
-    batch.opacities = (batch.opacities * (0.2 + 1.0 * torch.rand(1, generator=g))).clamp(max=0.999)
-    return batch, bg, si, dict(S=S, V=V, K=K, G=G, hw=hw, s_mult=s_mult, si=si)
+_random_case = util.random_fuzz_case
 
 
 # Knife-edge budget per seed: TWICE the fraction of pixels the float64 oracle flags on that seed (measured on the CPU,
@@ -39,13 +24,33 @@ def fragile_cap(key) -> float:
     return max(2.0 * FRAGILE_MEASURED.get(key, 0.0), 0.002)
 
 
+# The forced comparison's residual cap (util.BranchForcing: at most half of the flagged pixels and 0.1 % of the image still
+# masked) holds per seed, with two remarks, both measured on the CPU with the float32 oracle standing in for the product:
+# * the four seeds with footprints x 250 (106, 112, 115, 248) meet it only with `keep_light` (41 / 67 / 56 / 31 pixels are
+#   undecidable under dozens of overlapping splats; all but 1 / 0 / 1 / 0 of them differ only in entries of weight
+#   alpha * T < 1e-4 and are then compared on the oracle's own branch) -- so every seed runs with it;
+# * seed 275 is in the list BECAUSE of its SH clamp edge: 96 of its 100 flagged pixels (1.2 % of the image) are the reach
+#   of one Gaussian whose colour is within 1e-6 of the clamp at 0, which is no keep decision and stays masked whatever the
+#   image says.  It cannot meet the cap on any implementation; its forced gates and `unexplained == 0` are asserted, the
+#   cap is not.
+RESIDUAL_CAP_NOT_MEASURABLE = {275}
+
+
 @pytest.mark.parametrize("seed", list(range(100, 116)) + [204, 248, 275])   # + an empty render, huge splats, an SH clamp edge
 def test_random_configurations(hip_lib, seed):
     batch, bg, si, desc = _random_case(seed)
-    ref = util.run_oracle(batch, torch.float64, background=bg, scale_invariant=si, mask_fragile=True)
-    prod = util.run_product(batch, background=bg, scale_invariant=si, pixel_mask=ref["pixel_mask"])
+    ref = util.run_oracle(batch, torch.float64, background=bg, scale_invariant=si, mask_fragile=True, decisions=True)
+    # (a seed with fewer than 4 flagged pixels is exempt from the "at most half stay masked" clause)
+    forcing = util.BranchForcing(batch, ref, min_flagged_for_half=4, keep_light=True, background=bg, scale_invariant=si)
+    prod = util.run_product(batch, background=bg, scale_invariant=si, pixel_mask=ref["pixel_mask"],
+                            after_forward=forcing.mask_for)
     rep = util.compare(prod, ref, max_fragile_frac=fragile_cap(seed))
+    forced = forcing.compare(prod)        # the flagged pixels on the branch the kernel took (util.BranchForcing)
+    from tests.test_gpu_raster import _report
+    _report(f"fuzz_seed_{seed}", {**rep, **forcing.report_entry(forced)})
     assert not rep["fails"], (desc, rep)
+    allowed = {"residual_cap"} if seed in RESIDUAL_CAP_NOT_MEASURABLE else set()
+    assert set(forced["fails"]) <= allowed, (desc, forced)
 
 
 def _wide_case(seed):
