@@ -255,6 +255,28 @@ int spf_raster_max_lds_tiles(void);
  * the stage timing below counts one launch per chunk.  Measured slower than the single chain on MI355X (see api.hip),
  * hence off by default. */
 int spf_raster_chunks(int32_t S, int32_t V, int32_t H, int32_t W, int32_t backward);
+/* Which tile sort kernels a call launches, in launch order, for a longest-list hint (0 = unknown), `tiles_call` tiles in
+ * the whole call and the environment as it is now (SPF_SORT_BLOCKS / _SEPARATE / _BIG_MIXED / _LDS_2K / _SINGLE): launch
+ * i runs kernel[i] (SPF_SORT_*), which sorts the lists with lo[i] < entries <= hi[i] and returns at once on every other
+ * tile, so the intervals must tile (1, hint] without gap or overlap; order[i] is 1 on the launch that also writes the
+ * composite kernels' launch order (with_order != 0: the first launch, which is SPF_SORT_ORDER_ONLY when there is
+ * nothing to sort).  Arrays of SPF_SORT_MAX_LAUNCHES entries.  The plan the library itself launches from; host-side
+ * arithmetic only.  Returns the number of launches, -1 for tiles_call < 1 or a null array. */
+#define SPF_SORT_ORDER_ONLY 0   /* spf_tile_order_kernel */
+#define SPF_SORT_MIXED 1        /* spf_sort_tiles_mixed_kernel<false>: (1, 2048] */
+#define SPF_SORT_MIXED_BIG 2    /* spf_sort_tiles_mixed_kernel<true>: (1, 4096] */
+#define SPF_SORT_PAIR 3         /* spf_sort_tiles_pair_kernel: (1, 1024] */
+#define SPF_SORT_WAVE8 4        /* spf_sort_tiles_wave_kernel<8, true>: (1, 512] */
+#define SPF_SORT_WAVE16 5       /* spf_sort_tiles_wave_kernel<16, true>: (1, 1024] */
+#define SPF_SORT_WAVE32 6       /* spf_sort_tiles_wave_kernel<32, false>: (1024, 2048] */
+#define SPF_SORT_BLOCK4 7       /* spf_sort_tiles_block_kernel<4>: (512, 1024] */
+#define SPF_SORT_BLOCK8 8       /* spf_sort_tiles_block_kernel<8>: (1024, 2048] */
+#define SPF_SORT_BLOCK16 9      /* spf_sort_tiles_block_kernel<16>: (2048, 4096] */
+#define SPF_SORT_LDS 10         /* spf_sort_tiles_lds_kernel<1024>: (4096, 8192], (2048, 8192] or (8192, 16384] */
+#define SPF_SORT_BIG 11         /* spf_sort_tiles_big_kernel: (16384, 0xffffffff] */
+#define SPF_SORT_MAX_LAUNCHES 8
+int spf_raster_sort_plan(uint32_t max_tile_hint, int32_t tiles_call, int32_t with_order, int32_t* kernel, uint32_t* lo,
+                         uint32_t* hi, int32_t* order);
 
 /* Camera tensors from poses / intrinsics, and the gradient of the poses from dL/dviewmatrix
  * (dL_dviewmatrix [R,4,4] in, dL_dextrinsics [R,4,4] out; cam->viewmatrix must hold the forward result). */

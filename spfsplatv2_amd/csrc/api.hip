@@ -14,6 +14,8 @@ hipError_t launch_project_bwd(const SpfDims&, const SpfInputs&, const SpfState&,
 hipError_t launch_tile_scan(const SpfState&, int, int, int, uint32_t, bool, hipStream_t);
 uint32_t dense_threshold();
 hipError_t launch_bin_pairs(const SpfDims&, const SpfState&, uint64_t, int, int, uint32_t, hipStream_t);
+SortSwitches read_sort_switches();
+int plan_tile_sort(uint32_t, int, bool, const SortSwitches&, SortLaunch*);
 hipError_t launch_tile_sort(const SpfState&, const TileLists&, int, int, uint64_t, uint32_t, const uint2*, int,
                             hipStream_t);
 hipError_t launch_render_fwd(const SpfDims&, const SpfInputs&, const SpfState&, const SpfOutputs&, uint64_t, int, int,
@@ -314,6 +316,14 @@ int spf_raster_chunks(int32_t S, int32_t V, int32_t H, int32_t W, int32_t backwa
     bool by_scene = false;
     const int C = plan_chunks(S, V, spf_raster_num_tiles(H, W), bounds, &by_scene);
     return (backward && !by_scene) ? 1 : C;
+}
+int spf_raster_sort_plan(uint32_t max_tile_hint, int32_t tiles_call, int32_t with_order, int32_t* kernel, uint32_t* lo,
+                         uint32_t* hi, int32_t* order) {
+    if (tiles_call < 1 || !kernel || !lo || !hi || !order) return -1;
+    spf::SortLaunch plan[SPF_SORT_MAX_LAUNCHES];
+    const int n = spf::plan_tile_sort(max_tile_hint, tiles_call, with_order != 0, spf::read_sort_switches(), plan);
+    for (int i = 0; i < n; ++i) kernel[i] = plan[i].kernel, lo[i] = plan[i].lo, hi[i] = plan[i].hi, order[i] = plan[i].order;
+    return n;
 }
 
 static int check_camera(const SpfCamera* c, bool fwd) {

@@ -930,85 +930,135 @@ hipError_t launch_bin_pairs(const SpfDims& d, const SpfState& st, uint64_t capac
     return hipGetLastError();
 }
 
-// Size classes: (1, 512]: one wave per tile, list in registers; (512, 1024], (1024, 2048], (2048, 4096]: one 256-thread block
-// per tile, list in registers, three LDS exchanges; (4096, 8192], (8192, 16384]: one 1024-thread
-// block per tile in LDS; > 16384: chunked LDS sort with a few global merge passes.  `max_tile_hint` (0 = unknown) lets the host skip empty classes.
-// `RT`: tiles of this launch; `RT_call`: tiles of the whole call it is a chunk of (picks the kernel family).
-// `tl`: where the lists are (packed, or direct bins)
-// `order` (direct bins, or null): eight more blocks in front of the first kernel write the composite lists kernels' launch
-// order there (tile_order_block).
-hipError_t launch_tile_sort(const SpfState& st, const TileLists& tl, int RT, int RT_call, uint64_t capacity,
-                            uint32_t max_tile_hint, const uint2* order_c, int T,
-                            hipStream_t stream) {   // T: tiles per render (0: contiguous tile ranges per XCD, see xcd_map)
-    uint2* order = const_cast<uint2*>(order_c);
-    const int ob = order ? 8 * order_windows(RT) : 0;
+// The tile sort.  Every kernel sorts the lists of ITS size class, lo < entries <= hi, and returns at once on the other tiles:
+// a call is sorted exactly when the classes of its launches tile (1, longest list] without gap or overlap.  plan_tile_sort
+// builds that, walking upward from 1 until the hint is covered (tests/test_abi.py holds every hint, family and switch to it
+// through spf_raster_sort_plan).  The classes: (1, 512], (1, 1024], (1024, 2048]: one wave per tile, 8 / 16 / 32 keys per
+// lane; (1, 1024]: a pair of waves per tile; (512, 1024], (1024, 2048], (2048, 4096]: one 256-thread block per tile, 4 / 8 / 16
+// keys per thread in registers, three LDS exchanges; (1, 2048], (1, 4096]: those of a call of few tiles as sections of ONE
+// launch; (4096, 8192], (8192, 16384]: one 1024-thread block per tile in LDS; above: chunked LDS sort with global merge passes.
+SortSwitches read_sort_switches() {
+    const char* const b = getenv("SPF_SORT_BLOCKS");       // (tests: "0" / "1" pin one of the two families)
+    const char* const bm = getenv("SPF_SORT_BIG_MIXED");   // ("0": the 2,049 .. 4,096 class as a launch of its own, as before)
+    return {b ? b[0] == '1' : -1, getenv("SPF_SORT_SEPARATE") != nullptr, getenv("SPF_SORT_SINGLE") != nullptr,
+            getenv("SPF_SORT_LDS_2K") != nullptr, !(bm && bm[0] == '0')};
+}
+
+// `max_tile_hint` (0 = unknown) lets the host stop at the class of the longest list; out[SPF_SORT_MAX_LAUNCHES] (seven at
+// the most: SPF_SORT_SEPARATE, hint unknown).  Returns the number of launches.  Reads no environment and no device.
+int plan_tile_sort(uint32_t max_tile_hint, int tiles_call, bool with_order, const SortSwitches& sw, SortLaunch* out) {
     const uint32_t mx = max_tile_hint ? max_tile_hint : 0xffffffffu;
-    const uint32_t thr = dense_threshold(), thr_f = dense_threshold_fwd();
-    const int wgrid = (RT + kBlock / kWave - 1) / (kBlock / kWave);
     // Lists of 513 .. 2048 entries: one wave per tile (16 / 32 keys per lane) when there are enough tiles to fill the
     // chip with single waves, one 256-thread block per tile when there are not (measured: 2,048 tiles of ~1,000 entries
     // 68 -> 60 us, 4,096 tiles of ~540 entries 69 -> 52 us with blocks; 8,192 tiles of ~540 entries 55 us with waves,
     // 65 us with blocks)
-    const char* force = getenv("SPF_SORT_BLOCKS");       // (tests: "0" / "1" pin one of the two families)
-    const bool blocks = force ? force[0] == '1' : RT_call < 6144;
-    const bool mixed = blocks && mx > 512 && !getenv("SPF_SORT_SEPARATE");    // 2 .. 2048 in one launch (see the kernel)
-    if (order && !(mx > 1))      // nothing to sort: the order on its own
-        spf_tile_order_kernel<<<ob, kBlock, 0, stream>>>(tl.count, st.tile_flags, order, RT, T, tl.cap, thr, thr_f);
-    // (SPF_SORT_BIG_MIXED=0: the 2,049 .. 4,096 class as a launch of its own, as before)
-    const char* const bm = getenv("SPF_SORT_BIG_MIXED");
-    const bool big_mixed = mixed && mx > 2048 && !getenv("SPF_SORT_LDS_2K") && !(bm && bm[0] == '0');
-    if (big_mixed)
-        spf_sort_tiles_mixed_kernel<true><<<ob + 2 * RT + wgrid, kBlock, 0, stream>>>(tl, st.tile_flags, st.counters, st.pairs,
-                                                                                      capacity, RT, thr, order, T, thr_f);
-    else if (mixed)
-        spf_sort_tiles_mixed_kernel<false><<<ob + RT + wgrid, kBlock, 0, stream>>>(tl, st.tile_flags, st.counters, st.pairs,
-                                                                                   capacity, RT, thr, order, T, thr_f);
-    // many tiles, lists of 2 .. 1024: a pair of waves per tile (C2 29.3 -> 27.7 us, C5 57.3 -> 50.1; SPF_SORT_SINGLE=1: one wave)
-    // (8 px grid: lists are a quarter as long -- up to 512 entries one wave per tile, four tiles per block, is the better fit)
-    const bool pairsk = !blocks && mx > 1 && mx <= 1024 && !getenv("SPF_SORT_SINGLE");
-    if (pairsk)
-        spf_sort_tiles_pair_kernel<<<ob + RT, 2 * kWave, 0, stream>>>(tl, st.tile_flags, st.counters, st.pairs, capacity, RT,
-                                                                      thr, order, T, thr_f);
-    if (mx > 1 && (mx <= 512 || blocks) && !mixed && !pairsk)  // lists of 2 .. 512: four tiles per block, one wave each, 2 / 4 / 8 keys per lane
-        spf_sort_tiles_wave_kernel<8, true><<<ob + wgrid, kBlock, 0, stream>>>(tl, st.tile_flags, st.counters, st.pairs,
-                                                                               capacity, 1, RT, thr, order, T, thr_f);
-    if (mx > 512 && !blocks && !pairsk)     // 2 .. 1024 with one wave per tile (up to 16 keys per lane)
-        spf_sort_tiles_wave_kernel<16, true><<<ob + wgrid, kBlock, 0, stream>>>(tl, st.tile_flags, st.counters, st.pairs,
-                                                                                capacity, 1, RT, thr, order, T, thr_f);
-    if (mx > 1024 && !blocks)    // 1025 .. 2048 with one wave per tile (32 keys per lane)
-        spf_sort_tiles_wave_kernel<32, false><<<wgrid, kBlock, 0, stream>>>(tl, st.tile_flags, st.counters, st.pairs,
-                                                                            capacity, 1024, RT, thr, nullptr, 0, thr_f);
-    if (mx > 512 && blocks && !mixed)      // 513 .. 1024: one block per tile, 4 keys per thread
-        spf_sort_tiles_block_kernel<4><<<RT, kBlock, 0, stream>>>(tl, st.counters, st.pairs, capacity, 512);
-    if (mx > 1024 && blocks && !mixed)     // 1025 .. 2048: 8 keys per thread
-        spf_sort_tiles_block_kernel<8><<<RT, kBlock, 0, stream>>>(tl, st.counters, st.pairs, capacity, 1024);
-    // 2049 .. 4096: one 256-thread block per tile, SIXTEEN keys per thread in registers (each wave sorts its 1,024 keys
-    // with lane exchanges, the last two merges start with three exchanges through LDS) -- round 5: the reference's
-    // 10-view shape is 768 tiles of ~2,800 entries, ALL in this class, and the all-LDS network below took 74 us for them
-    // (78 barrier-separated passes of 1,024 threads); 4097 .. 8192 stay with it
-    if (mx > 2048 && !getenv("SPF_SORT_LDS_2K") && !big_mixed)
-        spf_sort_tiles_block_kernel<16><<<RT, kBlock, 0, stream>>>(tl, st.counters, st.pairs, capacity, 2048);
-    if (mx > 2048 && getenv("SPF_SORT_LDS_2K"))
-        spf_sort_tiles_lds_kernel<1024><<<RT, 1024, 8192 * 8, stream>>>(tl, st.counters, st.pairs, capacity, 2048, 8192);
-    else if (mx > 4096)
-        spf_sort_tiles_lds_kernel<1024><<<RT, 1024, 8192 * 8, stream>>>(tl, st.counters, st.pairs, capacity, 4096, 8192);
-    if (mx > 8192) {
-        // the opt-in to 128 KB of dynamic LDS is a per-DEVICE function attribute: remember it per device
-        static std::atomic<bool> attr_set[64];          // (zero-initialised; the attribute is idempotent, so two host
-        int dev = 0;                                      //  threads racing here at worst both set it)
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spf_sort_tiles_lds_kernel<1024>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8);
-            if (e != hipSuccess) return e;
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spf_sort_tiles_big_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8);
-            if (e != hipSuccess) return e;
-            if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
-        }
-        spf_sort_tiles_lds_kernel<1024><<<RT, 1024, 16384 * 8, stream>>>(tl, st.counters, st.pairs, capacity, 8192, 16384);
+    const bool blocks = sw.blocks < 0 ? tiles_call < 6144 : sw.blocks == 1;
+    int n = 0;
+    uint32_t done = 1;                      // the launches so far cover the lists of up to `done` entries
+    const auto add = [&](int kernel, uint32_t hi) {
+        out[n] = {kernel, done, hi, with_order && n == 0};
+        ++n, done = hi;
+    };
+    if (with_order && mx <= 1) add(SPF_SORT_ORDER_ONLY, 1);        // nothing to sort: the order on its own
+    while (done < mx) {
+        if (done == 1 && blocks) {
+            // few tiles: the classes up to 2,048 entries as ONE launch, up to 4,096 when the call has such lists (the
+            // reference's 10-view shape is 768 tiles of ~2,800 entries); SPF_SORT_SEPARATE: a launch per class.  Up to
+            // 512 entries one wave per tile, four tiles per block, is the better fit
+            if (mx <= 512 || sw.separate) add(SPF_SORT_WAVE8, 512);
+            else if (mx > 2048 && sw.big_mixed && !sw.lds_2k) add(SPF_SORT_MIXED_BIG, 4096);
+            else add(SPF_SORT_MIXED, 2048);
+        } else if (done == 1) {
+            // many tiles, lists of 2 .. 1024: a pair of waves per tile (C2 29.3 -> 27.7 us, C5 57.3 -> 50.1;
+            // SPF_SORT_SINGLE=1, or longer lists in the call: one wave)
+            if (mx <= 1024 && !sw.single) add(SPF_SORT_PAIR, 1024);
+            else if (mx <= 512) add(SPF_SORT_WAVE8, 512);
+            else add(SPF_SORT_WAVE16, 1024);
+        } else if (done == 512) add(SPF_SORT_BLOCK4, 1024);
+        else if (done == 1024) add(blocks ? SPF_SORT_BLOCK8 : SPF_SORT_WAVE32, 2048);
+        // 2049 .. 4096 in registers: the all-LDS network took 74 us for the 10-view shape (78 barrier-separated passes
+        // of 1,024 threads), 97.5 -> 63 us for the stage; SPF_SORT_LDS_2K=1 is that old path
+        else if (done == 2048) sw.lds_2k ? add(SPF_SORT_LDS, 8192) : add(SPF_SORT_BLOCK16, 4096);
+        else if (done <= 8192) add(SPF_SORT_LDS, 2 * done);         // (4096, 8192] and (8192, 16384]
+        else add(SPF_SORT_BIG, 0xffffffffu);
     }
-    if (mx > 16384)
-        spf_sort_tiles_big_kernel<<<RT, 1024, 16384 * 8, stream>>>(tl, st.counters, st.pairs, capacity, 16384);
+    return n;
+}
+
+// `RT`: tiles of this launch (sizes the grids); `RT_call`: tiles of the whole call it is a chunk of (picks the family).
+// `tl`: where the lists are (packed, or direct bins)
+// `order` (direct bins, or null): eight more blocks per window in front of the first kernel write the composite lists
+// kernels' launch order there (tile_order_block).
+hipError_t launch_tile_sort(const SpfState& st, const TileLists& tl, int RT, int RT_call, uint64_t capacity,
+                            uint32_t max_tile_hint, const uint2* order_c, int T,
+                            hipStream_t stream) {   // T: tiles per render (0: contiguous tile ranges per XCD, see xcd_map)
+    uint2* order = const_cast<uint2*>(order_c);
+    const uint32_t thr = dense_threshold(), thr_f = dense_threshold_fwd();
+    const int wgrid = (RT + kBlock / kWave - 1) / (kBlock / kWave);
+    SortLaunch plan[SPF_SORT_MAX_LAUNCHES];
+    const int n = plan_tile_sort(max_tile_hint, RT_call, order != nullptr, read_sort_switches(), plan);
+    for (const SortLaunch* l = plan; l < plan + n; ++l) {
+        const int ob = l->order ? 8 * order_windows(RT) : 0;
+        switch (l->kernel) {
+        case SPF_SORT_ORDER_ONLY:
+            spf_tile_order_kernel<<<ob, kBlock, 0, stream>>>(tl.count, st.tile_flags, order, RT, T, tl.cap, thr, thr_f);
+            break;
+        case SPF_SORT_MIXED_BIG:
+            spf_sort_tiles_mixed_kernel<true><<<ob + 2 * RT + wgrid, kBlock, 0, stream>>>(
+                tl, st.tile_flags, st.counters, st.pairs, capacity, RT, thr, order, T, thr_f);
+            break;
+        case SPF_SORT_MIXED:
+            spf_sort_tiles_mixed_kernel<false><<<ob + RT + wgrid, kBlock, 0, stream>>>(
+                tl, st.tile_flags, st.counters, st.pairs, capacity, RT, thr, order, T, thr_f);
+            break;
+        case SPF_SORT_PAIR:
+            spf_sort_tiles_pair_kernel<<<ob + RT, 2 * kWave, 0, stream>>>(tl, st.tile_flags, st.counters, st.pairs, capacity,
+                                                                          RT, thr, order, T, thr_f);
+            break;
+        case SPF_SORT_WAVE8:
+            spf_sort_tiles_wave_kernel<8, true><<<ob + wgrid, kBlock, 0, stream>>>(
+                tl, st.tile_flags, st.counters, st.pairs, capacity, l->lo, RT, thr, order, T, thr_f);
+            break;
+        case SPF_SORT_WAVE16:
+            spf_sort_tiles_wave_kernel<16, true><<<ob + wgrid, kBlock, 0, stream>>>(
+                tl, st.tile_flags, st.counters, st.pairs, capacity, l->lo, RT, thr, order, T, thr_f);
+            break;
+        case SPF_SORT_WAVE32:
+            spf_sort_tiles_wave_kernel<32, false><<<wgrid, kBlock, 0, stream>>>(
+                tl, st.tile_flags, st.counters, st.pairs, capacity, l->lo, RT, thr, nullptr, 0, thr_f);
+            break;
+        case SPF_SORT_BLOCK4:
+            spf_sort_tiles_block_kernel<4><<<RT, kBlock, 0, stream>>>(tl, st.counters, st.pairs, capacity, l->lo);
+            break;
+        case SPF_SORT_BLOCK8:
+            spf_sort_tiles_block_kernel<8><<<RT, kBlock, 0, stream>>>(tl, st.counters, st.pairs, capacity, l->lo);
+            break;
+        case SPF_SORT_BLOCK16:
+            spf_sort_tiles_block_kernel<16><<<RT, kBlock, 0, stream>>>(tl, st.counters, st.pairs, capacity, l->lo);
+            break;
+        case SPF_SORT_LDS:
+            if (l->hi > 8192) {     // 128 KB of dynamic LDS, here and in the big kernel (whose launch only ever follows this one)
+                // the opt-in is a per-DEVICE function attribute: remember it per device
+                static std::atomic<bool> attr_set[64];          // (zero-initialised; the attribute is idempotent, so two host
+                int dev = 0;                                      //  threads racing here at worst both set it)
+                if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
+                    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spf_sort_tiles_lds_kernel<1024>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8);
+                    if (e != hipSuccess) return e;
+                    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spf_sort_tiles_big_kernel),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8);
+                    if (e != hipSuccess) return e;
+                    if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
+                }
+            }
+            spf_sort_tiles_lds_kernel<1024><<<RT, 1024, (size_t)l->hi * 8, stream>>>(tl, st.counters, st.pairs, capacity,
+                                                                                     l->lo, l->hi);
+            break;
+        case SPF_SORT_BIG:
+            spf_sort_tiles_big_kernel<<<RT, 1024, 16384 * 8, stream>>>(tl, st.counters, st.pairs, capacity, l->lo);
+            break;
+        }
+    }
     return hipGetLastError();
 }
 

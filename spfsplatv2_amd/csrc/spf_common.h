@@ -22,6 +22,18 @@ inline int max_lds_tiles() {
     return v < kMaxLdsTiles ? v : kMaxLdsTiles;
 }
 
+// The tile sort's launch plan (binning.hip::plan_tile_sort; spf_raster_sort_plan returns it to the host)
+struct SortSwitches {       // the SPF_SORT_* environment, read once per launch (read_sort_switches)
+    int blocks;             // SPF_SORT_BLOCKS: -1 unset (the tile count picks the family), 0 waves, 1 blocks
+    bool separate, single, lds_2k;
+    bool big_mixed;         // false only under SPF_SORT_BIG_MIXED=0
+};
+struct SortLaunch {
+    int kernel;             // SPF_SORT_*
+    uint32_t lo, hi;        // sorts the lists with lo < entries <= hi
+    bool order;             // this launch carries the blocks that write the composite kernels' launch order
+};
+
 // Record layout (floats): 0 x, 1 y, 2 conic A, 3 conic B | 4 conic C, 5 opacity, 6 depth,
 // 7 cull radius^2 | 8 r, 9 g, 10 b, 11 flags (int bits: colour-channel clamp mask).
 // Gradient record (one per (Gaussian, tile) pair): 0 dx, 1 dy (pixel space), 2 da, 3 db, 4 dc, 5 dopacity,

@@ -60,6 +60,115 @@ def test_launch_slots_cover_every_tile_once(hip_lib):
     assert hip_lib.spf_raster_launch_slot_tile(8, 256, 8, 0) == -1 and hip_lib.spf_raster_launch_slot_tile(8, 256, 0, 256) == -1
 
 
+_SORT_ENV = ("SPF_SORT_BLOCKS", "SPF_SORT_BIG_MIXED", "SPF_SORT_SEPARATE", "SPF_SORT_LDS_2K", "SPF_SORT_SINGLE")
+_SORT_INF = 0xffffffff
+
+
+def _sort_ids():
+    """The SPF_SORT_* kernel ids of the header, by name without the prefix."""
+    text = (ROOT / "include" / "spfsplat_hip.h").read_text()
+    return {name: int(val) for name, val in re.findall(r"#define SPF_SORT_([A-Z0-9_]+) (\d+)\b", text)}
+
+
+def _sort_plan_arrays():
+    n_max = _sort_ids()["MAX_LAUNCHES"]
+    return (C.c_int32 * n_max)(), (C.c_uint32 * n_max)(), (C.c_uint32 * n_max)(), (C.c_int32 * n_max)()
+
+
+def _sort_plan(hip_lib, hint, tiles, with_order):
+    kernel, lo, hi, order = _sort_plan_arrays()
+    n = hip_lib.spf_raster_sort_plan(hint, tiles, int(with_order), kernel, lo, hi, order)
+    assert 0 <= n <= len(kernel), (hint, tiles, with_order, n)
+    return [(kernel[i], lo[i], hi[i], order[i]) for i in range(n)]
+
+
+def _set_sort_env(monkeypatch, **values):
+    for name in _SORT_ENV:
+        v = values.get(name[len("SPF_SORT_"):].lower())
+        if v is None:
+            monkeypatch.delenv(name, raising=False)
+        else:
+            monkeypatch.setenv(name, v)
+
+
+def test_sort_plan_covers_every_list_length_once(hip_lib, monkeypatch):
+    """Every tile sort kernel sorts the lists of its own size class (lo, hi] and skips the rest, so a call is sorted iff
+    the classes of its launches (binning.hip::plan_tile_sort, through spf_raster_sort_plan) tile (1, hint] without gap or
+    overlap -- for every hint around the class borders, both families by tile count, and every setting of the five
+    switches.  The launch order blocks ride on the first launch, and only there."""
+    import itertools
+    ids = _sort_ids()
+    hints = (0, 1, 2, 64, 512, 513, 1024, 1025, 2048, 2049, 4096, 4097, 8192, 8193, 16384, 16385, 131072)
+    combos = 0
+    for blocks, big_mixed, separate, lds_2k, single in itertools.product(
+            (None, "0", "1"), (None, "0", "1"), (None, "1"), (None, "1"), (None, "1")):
+        _set_sort_env(monkeypatch, blocks=blocks, big_mixed=big_mixed, separate=separate, lds_2k=lds_2k, single=single)
+        combos += 1
+        for hint, tiles, with_order in itertools.product(hints, (256, 6143, 6144, 8192), (False, True)):
+            plan = _sort_plan(hip_lib, hint, tiles, with_order)
+            where = (blocks, big_mixed, separate, lds_2k, single, hint, tiles, with_order, plan)
+            assert [o for _, _, _, o in plan] == ([1] + [0] * (len(plan) - 1) if with_order else [0] * len(plan)), where
+            sorts = sorted((lo, hi) for k, lo, hi, _ in plan if k != ids["ORDER_ONLY"])
+            if hint == 1:
+                assert [k for k, _, _, _ in plan] == ([ids["ORDER_ONLY"]] if with_order else []), where
+                continue
+            assert len(sorts) == len(plan), where
+            reach = 1
+            for lo, hi in sorts:
+                assert lo == reach and hi > lo, where
+                reach = hi
+            assert reach >= (hint if hint else _SORT_INF), where
+    assert combos == 72
+    assert hip_lib.spf_raster_sort_plan(64, 0, 0, *_sort_plan_arrays()) == -1                       # nonsense arguments
+    assert hip_lib.spf_raster_sort_plan(64, 256, 0, None, None, None, None) == -1
+
+
+def test_sort_plan_defaults_and_switches_are_pinned(hip_lib, monkeypatch):
+    """What a call launches by default, per hint and family, and what each switch changes (the launches of the chain of
+    conditions this table replaced, derived from its code)."""
+    ids = _sort_ids()
+    names = {v: k for k, v in ids.items() if k != "MAX_LAUNCHES"}
+
+    def plan(hint, tiles, with_order=False):
+        return [(names[k], lo, hi) for k, lo, hi, _ in _sort_plan(hip_lib, hint, tiles, with_order)]
+
+    _set_sort_env(monkeypatch)
+    lds_4k, lds_8k, big = ("LDS", 4096, 8192), ("LDS", 8192, 16384), ("BIG", 16384, _SORT_INF)
+    tails = ((4097, 8192, [lds_4k]), (8193, 16384, [lds_4k, lds_8k]), (16385, 131072, [lds_4k, lds_8k, big]),
+             (0, 0, [lds_4k, lds_8k, big]))
+    few = [(2, 512, [("WAVE8", 1, 512)]), (513, 2048, [("MIXED", 1, 2048)]), (2049, 4096, [("MIXED_BIG", 1, 4096)])]
+    few += [(a, b, few[-1][2] + tail) for a, b, tail in tails]
+    waves = [("WAVE16", 1, 1024), ("WAVE32", 1024, 2048)]
+    many = [(2, 1024, [("PAIR", 1, 1024)]), (1025, 2048, waves), (2049, 4096, waves + [("BLOCK16", 2048, 4096)])]
+    many += [(a, b, many[-1][2] + tail) for a, b, tail in tails]
+    for tiles_of, table in (((1, 256, 6143), few), ((6144, 8192, 1 << 20), many)):
+        for tiles in tiles_of:
+            for a, b, want in table:
+                for hint in {a, (a + b) // 2, b}:
+                    assert plan(hint, tiles) == want, (hint, tiles)
+                    assert plan(hint, tiles, True) == want, (hint, tiles)
+            assert plan(1, tiles) == [] and plan(1, tiles, True) == [("ORDER_ONLY", 1, 1)]
+    # one line per switch
+    _set_sort_env(monkeypatch, separate="1")
+    assert plan(2048, 256) == [("WAVE8", 1, 512), ("BLOCK4", 512, 1024), ("BLOCK8", 1024, 2048)]
+    _set_sort_env(monkeypatch, big_mixed="0")
+    assert plan(4096, 256) == [("MIXED", 1, 2048), ("BLOCK16", 2048, 4096)]
+    _set_sort_env(monkeypatch, big_mixed="1")
+    assert plan(4096, 256) == [("MIXED_BIG", 1, 4096)]
+    _set_sort_env(monkeypatch, lds_2k="1")
+    assert plan(4096, 256) == [("MIXED", 1, 2048), ("LDS", 2048, 8192)]
+    assert plan(8192, 256) == [("MIXED", 1, 2048), ("LDS", 2048, 8192)]
+    assert plan(8193, 8192) == waves + [("LDS", 2048, 8192), lds_8k]
+    _set_sort_env(monkeypatch, single="1")
+    assert plan(1024, 8192) == [("WAVE16", 1, 1024)] and plan(512, 8192) == [("WAVE8", 1, 512)]
+    assert plan(1024, 256) == [("MIXED", 1, 2048)]                             # (the switch is the wave family's)
+    for tiles in (256, 8192):
+        _set_sort_env(monkeypatch, blocks="0")
+        assert plan(2048, tiles) == waves and plan(1024, tiles) == [("PAIR", 1, 1024)]
+        _set_sort_env(monkeypatch, blocks="1")
+        assert plan(2048, tiles) == [("MIXED", 1, 2048)] and plan(512, tiles) == [("WAVE8", 1, 512)]
+
+
 def test_argument_validation_without_compute(hip_lib):
     """Bad arguments are rejected before anything touches a device."""
     from spfsplatv2_amd import _lib

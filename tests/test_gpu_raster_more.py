@@ -1,5 +1,7 @@
 """More GPU parity: long tile lists (every sort size class), colours-precomputed and orthographic entry points,
 gradient switches, degenerate inputs, and size-independent properties at BASELINE's full C2 size."""
+import functools
+
 import pytest
 import torch
 
@@ -386,21 +388,27 @@ def test_both_sort_families_give_the_same_lists(hip_lib, monkeypatch):
             assert torch.equal(a["grads"][n], b["grads"][n]), n
 
 
+@functools.lru_cache(maxsize=None)
+def _testbig_with_longest_list(seed, G, lo, hi, aim):
+    """One scene, one view of the TESTBIG shape with opacities x 0.03 whose longest tile list has lo < n <= hi entries,
+    and that length.  The longest list grows ~linearly with G: start at `G`, step towards `aim`.  (Shared between tests:
+    nobody changes the batch.)"""
+    for _ in range(8):
+        batch = syn.make_batch("TESTBIG", 1, 1, seed=seed, s_mult=1.0, G=G)
+        batch.opacities = batch.opacities * 0.03
+        longest = util.run_product(batch, with_grads=False)["stats"]["max_tile_list"]
+        if lo < longest <= hi:
+            return batch, longest
+        G = max(int(G * aim / max(longest, 1)), 64)
+    raise AssertionError(("no batch with a longest list in the range", lo, hi, G, longest))
+
+
 def test_long_list_class_inside_the_mixed_sort_launch_gives_the_same_lists(hip_lib, monkeypatch):
     """Calls of few tiles sort lists of 2,049..4,096 entries (sixteen keys per thread) in the same launch as the shorter
     classes (`spf_sort_tiles_mixed_kernel<true>`); `SPF_SORT_BIG_MIXED=0` gives that class a launch of its own, as before.
     Same networks on the same lists: bit-equal images and gradients, exact and planned."""
     import spfsplatv2_amd as spf
-    batch, G = None, 9000
-    for _ in range(8):                                   # (the longest list grows ~linearly with G: aim at 2,600)
-        cand = syn.make_batch("TESTBIG", 1, 1, seed=23, s_mult=1.0, G=G)
-        cand.opacities = cand.opacities * 0.03
-        longest = util.run_product(cand, with_grads=False)["stats"]["max_tile_list"]
-        if 2048 < longest <= 3400:
-            batch = cand
-            break
-        G = max(int(G * 2600 / max(longest, 1)), 64)
-    assert batch is not None, ("no batch with a longest list of 2,049..3,400 entries", G, longest)
+    batch, _ = _testbig_with_longest_list(23, 9000, 2048, 3400, 2600)
     outs = []
     for big in ("0", "1"):
         monkeypatch.setenv("SPF_SORT_BIG_MIXED", big)
@@ -409,6 +417,52 @@ def test_long_list_class_inside_the_mixed_sort_launch_gives_the_same_lists(hip_l
         assert spf.plan_flags(planned["decoder"].last_call) == 0
         outs.append((exact, planned))
     monkeypatch.delenv("SPF_SORT_BIG_MIXED")
+    for a, b in zip(*outs):
+        assert torch.equal(a["color"], b["color"]) and torch.equal(a["depth"], b["depth"])
+        for n in util.GRAD_NAMES:
+            assert torch.equal(a["grads"][n], b["grads"][n]), n
+
+
+def test_separate_block_classes_give_the_same_lists_as_the_mixed_launch(hip_lib, monkeypatch):
+    """Few-tiles family: `SPF_SORT_SEPARATE=1` sorts the classes up to 512, 1,024 and 2,048 entries as a launch each
+    (`spf_sort_tiles_wave_kernel<8>`, `spf_sort_tiles_block_kernel<4>`, `<8>`), the default as sections of one
+    (`spf_sort_tiles_mixed_kernel<false>`): same networks on the same lists, so bit-equal images and gradients -- with the
+    longest list in the 4-keys class and in the 8-keys class."""
+    monkeypatch.setenv("SPF_SORT_BLOCKS", "1")
+    cases = [_testbig_with_longest_list(21, 2200, 512, 1024, 800), _testbig_with_longest_list(21, 3300, 1024, 2048, 1500)]
+    seen = {"4" if 512 < m <= 1024 else ("8" if 1024 < m <= 2048 else "-") for _, m in cases}
+    assert seen == {"4", "8"}, [m for _, m in cases]
+    outs = []
+    for separate in ("1", ""):
+        if separate:
+            monkeypatch.setenv("SPF_SORT_SEPARATE", separate)
+        else:
+            monkeypatch.delenv("SPF_SORT_SEPARATE")
+        outs.append([util.run_product(batch) for batch, _ in cases])
+    for (_, m), a, b in zip(cases, *outs):
+        assert a["stats"]["max_tile_list"] == m == b["stats"]["max_tile_list"]
+        assert torch.equal(a["color"], b["color"]) and torch.equal(a["depth"], b["depth"])
+        for n in util.GRAD_NAMES:
+            assert torch.equal(a["grads"][n], b["grads"][n]), n
+
+
+def test_lds_sort_from_2049_entries_gives_the_same_lists(hip_lib, monkeypatch):
+    """`SPF_SORT_LDS_2K=1` sorts lists of 2,049 .. 8,192 entries with the all-LDS network (`spf_sort_tiles_lds_kernel`
+    from 2,048 on, the shorter classes in `spf_sort_tiles_mixed_kernel<false>`), the default keeps 2,049 .. 4,096 in
+    registers: same unique order, so bit-equal images and gradients, exact and planned."""
+    import spfsplatv2_amd as spf
+    batch, longest = _testbig_with_longest_list(23, 9000, 2048, 3400, 2600)
+    outs = []
+    for lds_2k in ("1", ""):
+        if lds_2k:
+            monkeypatch.setenv("SPF_SORT_LDS_2K", lds_2k)
+        else:
+            monkeypatch.delenv("SPF_SORT_LDS_2K")
+        exact = util.run_product(batch)
+        assert exact["stats"]["max_tile_list"] == longest
+        planned = util.run_product(batch, max_pairs=spf.plan_pair_budget(exact["stats"], check="deferred"))
+        assert spf.plan_flags(planned["decoder"].last_call) == 0
+        outs.append((exact, planned))
     for a, b in zip(*outs):
         assert torch.equal(a["color"], b["color"]) and torch.equal(a["depth"], b["depth"])
         for n in util.GRAD_NAMES:
