@@ -31,6 +31,10 @@
  *                           compute_psnr (src/evaluation/metrics.py:11-52), for a whole batch of images on the device.
  *   spf_lpips_*             LPIPS(net="vgg") as LossLpips (src/loss/loss_lpips.py:57-85) and compute_lpips
  *                           (src/evaluation/metrics.py:22-33) call it, with its backward; weights come from the caller.
+ *   spf_regr3d_*            Regr3D.forward, the distillation point loss (src/loss/loss_point.py:188-254, with
+ *                           normalize_pointcloud 'avg_dis', src/geometry/ptc_geometry.py:270-328, and invalid_to_zeros,
+ *                           src/model/encoder/backbone/croco/misc.py:129-138) as src/model/model_wrapper.py:171,323-331
+ *                           builds and calls it, with its autograd backward to the two predicted point maps.
  *
  * Return value of every int function: 0 = success, otherwise a negative SPF_E_* code;
  * spf_last_error() returns a host string describing the most recent failure on this thread.
@@ -45,7 +49,8 @@
 extern "C" {
 #endif
 
-#define SPF_ABI_VERSION 7
+#define SPF_ABI_VERSION 7   /* unchanged by the spf_regr3d_* family: it only ADDS a struct and three entry points; no
+                              existing struct, signature or meaning moved, so a caller built against 7 still fits */
 
 #define SPF_OK 0
 #define SPF_E_INVALID (-1)   /* bad argument (null pointer, size, unsupported degree ...) */
@@ -426,6 +431,51 @@ int spf_reproj_forward(const SpfReproj* args, void* partial, float* loss, float*
  * gpartial is needed (and only then) when one of them is given. */
 int spf_reproj_backward(const SpfReproj* args, const float* scale, const float* dL_dloss, float* dL_dpts3d,
                         float* gpartial, float* dL_dposes, float* dL_dintrinsics, void* stream);
+
+/* Distillation point loss (Regr3D.forward, src/loss/loss_point.py:188-254, norm_mode 'avg_dis' or none) of two views of
+ * B point maps of n = H W points.  With dis = |gt| in float32, per view v and batch item b:
+ *   quantile mode (has_dist_clip = 0): q_lo, q_hi = torch.quantile(dis[b], [0.002, 0.998]) by torch's definition -- rank
+ *     r = float32(q) * (n - 1) in float32, lerp(sorted[floor r], sorted[ceil r], r - floor r) -- the four order statistics
+ *     found EXACTLY by a radix select over the bit patterns (histogram passes, no sort);
+ *     valid = q_lo <= dis <= q_hi and conf >= 3;
+ *   clip mode (has_dist_clip = 1): valid = dis <= dist_clip; conf1 / conf2 are not read (may be NULL);
+ *   nf_pr[b] = max((sum_valid1 |pr1| + sum_valid2 |pr2|) / (n1[b] + n2[b] + 1e-8), 1e-8), nf_gt[b] likewise from gt
+ *     (normalize = 0: both are 1; gt_scale = 1: nf_gt is 1);
+ *   loss_v = mean over ALL valid points of view v of |pr / nf_pr[b] - gt / nf_gt[b]| (NaN for a view without one: the mean
+ *     of nothing); loss = loss_1 + loss_2, or loss_2 with disable_view1.
+ * A NaN norm compares false, so such a point is invalid; it orders above +inf in the select (torch.quantile would
+ * return NaN for that row).
+ * gt_pts*, pr_pts* are read in place: batch item b of a tensor starts b * stride floats from its pointer (stride >= 0),
+ * its H*W*3 floats are contiguous, and a 16-byte aligned row is read with 16-byte loads.  conf1, conf2 [B,H,W] are
+ * contiguous.  No float atomics, no allocation, no synchronisation: every float sum is formed from per-slot partials in a
+ * fixed order, so results are run-to-run identical and do not depend on the strides. */
+typedef struct SpfRegr3d {
+    const float* gt_pts1;
+    const float* gt_pts2;
+    const float* pr_pts1;
+    const float* pr_pts2;
+    const float* conf1;
+    const float* conf2;
+    int64_t stride_gt1, stride_gt2, stride_pr1, stride_pr2;
+    int32_t B, H, W;
+    int32_t has_dist_clip;        /* 0: quantile mask (dist_clip is None in the reference); 1: dis <= dist_clip */
+    float dist_clip;
+    int32_t disable_view1;
+    int32_t normalize;            /* norm_mode 'avg_dis' (1) or falsy (0) */
+    int32_t gt_scale;             /* 1: the ground truth is not normalised */
+} SpfRegr3d;
+/* Bytes of the caller's scratch (16-byte aligned; it carries the per-slot partials and the per-row scalars from the forward
+ * to the backward -- nothing per point), or -1 for sizes the forward would reject.  Host only. */
+int64_t spf_regr3d_scratch_bytes(int32_t B, int32_t H, int32_t W);
+/* Forward: loss[1], and the stats block of 8 B 32-bit words that the backward reads and a caller may log:
+ *   n_valid[2][B] (int32) | q[2][B][2] (q_lo, q_hi; clip mode: 0, dist_clip) | nf_pr[B] | nf_gt[B]. */
+int spf_regr3d_forward(const SpfRegr3d* args, void* scratch, float* stats, float* loss, void* stream);
+/* Backward (one launch) after the forward on the same args, scratch and stats: d_pr1, d_pr2 [B,H,W,3] contiguous, either may
+ * be NULL (not wanted; at least one is).  dL_dloss[1] is read on the device.  Both the direct term and the path through
+ * nf_pr count (with disable_view1, pr_pts1 still receives the latter); |x| has gradient 0 at 0; invalid points get
+ * exactly 0. */
+int spf_regr3d_backward(const SpfRegr3d* args, const void* scratch, const float* stats, const float* dL_dloss,
+                        float* d_pr1, float* d_pr2, void* stream);
 
 /* SSIM (ssim / SSIM, src/loss/loss_ssim.py:58-189, and compute_ssim, src/evaluation/metrics.py:36-52) of X, Y [N,C,H,W]
  * contiguous float32, every H x W plane on its own.  With the 1-D window win[0 .. ws) (ws odd, 3 .. 33) applied along

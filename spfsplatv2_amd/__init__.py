@@ -9,7 +9,7 @@ from .rasterizer import (CallRecord, GaussianRasterizationSettings, GaussianRast
                          last_forward_stats, last_plan_flags, plan_flags, plan_pair_budget, rasterize_batch,
                          render_batch, sh_band4_default)
 from .loss import (Loss, LossLpips, LossLpipsCfg, LossLpipsCfgWrapper, LossMse, LossMseCfg, LossMseCfgWrapper, LossReproj,
-                   LossReprojCfg, LossReprojCfgWrapper, mse_loss, reproj_loss, unit_grad)
+                   LossReprojCfg, LossReprojCfgWrapper, Regr3D, mse_loss, regr3d_loss, reproj_loss, unit_grad)
 from .lpips import LPIPS, LpipsWeights, lpips
 from .metrics import compute_lpips, compute_psnr, compute_ssim
 from .ssim import SSIM, ssim
@@ -20,5 +20,5 @@ __all__ = [
     "DECODERS", "Decoder", "DecoderOutput", "DecoderSplattingCUDA", "DecoderSplattingCUDACfg",
     "DecoderSplattingHIP", "Gaussians", "get_decoder", "get_fov", "get_projection_matrix", "render_cuda",
     "render_cuda_orthographic", "render_views", "GaussianRasterizationSettings", "GaussianRasterizer",
-    "last_forward_stats", "PairBudget", "plan_pair_budget", "last_plan_flags", "plan_flags", "CallRecord", "sh_band4_default", "orthographic_camera", "rasterize_batch", "render_batch", "camera_forward", "camera_tensors", "Loss", "LossMse", "LossMseCfg", "LossMseCfgWrapper", "mse_loss", "unit_grad", "LossReproj", "LossReprojCfg", "LossReprojCfgWrapper", "reproj_loss", "ssim", "SSIM", "compute_ssim", "compute_psnr", "LossLpips", "LossLpipsCfg", "LossLpipsCfgWrapper", "lpips", "LPIPS", "LpipsWeights", "compute_lpips", "PositionGetter", "append_token_position", "RoPE2D", "RotaryPositionEmbedding2D", "cuRoPE2D", "cuRoPE2D_func", "rope_2d", "rope_2d_head_major", "rope_2d_pair", "hostbind",
+    "last_forward_stats", "PairBudget", "plan_pair_budget", "last_plan_flags", "plan_flags", "CallRecord", "sh_band4_default", "orthographic_camera", "rasterize_batch", "render_batch", "camera_forward", "camera_tensors", "Loss", "LossMse", "LossMseCfg", "LossMseCfgWrapper", "mse_loss", "unit_grad", "LossReproj", "LossReprojCfg", "LossReprojCfgWrapper", "reproj_loss", "Regr3D", "regr3d_loss", "ssim", "SSIM", "compute_ssim", "compute_psnr", "LossLpips", "LossLpipsCfg", "LossLpipsCfgWrapper", "lpips", "LPIPS", "LpipsWeights", "compute_lpips", "PositionGetter", "append_token_position", "RoPE2D", "RotaryPositionEmbedding2D", "cuRoPE2D", "cuRoPE2D_func", "rope_2d", "rope_2d_head_major", "rope_2d_pair", "hostbind",
 ]

@@ -57,6 +57,14 @@ class SpfReproj(C.Structure):
                 ("soft_clamp", C.c_float)]
 
 
+class SpfRegr3d(C.Structure):
+    _fields_ = [("gt_pts1", C.c_void_p), ("gt_pts2", C.c_void_p), ("pr_pts1", C.c_void_p), ("pr_pts2", C.c_void_p),
+                ("conf1", C.c_void_p), ("conf2", C.c_void_p), ("stride_gt1", C.c_int64), ("stride_gt2", C.c_int64),
+                ("stride_pr1", C.c_int64), ("stride_pr2", C.c_int64), ("B", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("has_dist_clip", C.c_int32), ("dist_clip", C.c_float), ("disable_view1", C.c_int32),
+                ("normalize", C.c_int32), ("gt_scale", C.c_int32)]
+
+
 SSIM_MAX_WIN = 33
 
 
@@ -111,6 +119,10 @@ SYMBOLS = {
     "spf_reproj_forward": (C.c_int, [C.POINTER(SpfReproj), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_reproj_backward": (C.c_int, [C.POINTER(SpfReproj), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    "spf_regr3d_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "spf_regr3d_forward": (C.c_int, [C.POINTER(SpfRegr3d), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_regr3d_backward": (C.c_int, [C.POINTER(SpfRegr3d), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
     "spf_ssim_partial_blocks": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "spf_ssim_forward": (C.c_int, [C.POINTER(SpfSsim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_ssim_backward": (C.c_int, [C.POINTER(SpfSsim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -33,6 +33,9 @@ hipError_t launch_mse_bwd(const float*, const float*, int64_t, float, const floa
 int64_t reproj_slots(int, int, int, int, int*);
 hipError_t launch_reproj_fwd(const SpfReproj&, void*, float*, float*, hipStream_t);
 hipError_t launch_reproj_bwd(const SpfReproj&, const float*, const float*, float*, float*, float*, float*, hipStream_t);
+int64_t regr3d_scratch_words(int, int, int);
+hipError_t launch_regr3d_fwd(const SpfRegr3d&, void*, float*, float*, hipStream_t);
+hipError_t launch_regr3d_bwd(const SpfRegr3d&, const void*, const float*, const float*, float*, float*, hipStream_t);
 int64_t ssim_slots(int, int, int, int, int);
 hipError_t launch_ssim_fwd(const SpfSsim&, float*, float*, float*, hipStream_t);
 hipError_t launch_ssim_bwd(const SpfSsim&, const float*, const float*, float*, float*, hipStream_t);
@@ -690,6 +693,60 @@ int spf_mse_backward(const float* prediction, const float* image, int64_t n, flo
         return fail(SPF_E_INVALID, "mse: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_mse_bwd(prediction, image, n, 2.0f * weight / (float)n, dL_dloss, dL_dprediction,
                                 static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+static bool regr3d_sizes_ok(int32_t B, int32_t H, int32_t W) {
+    if (B < 1 || H < 1 || W < 1) return false;
+    // (a row's 3 H W floats are indexed with 32-bit point numbers; per-view counts and slot numbers are 32-bit)
+    if ((int64_t)H * W * 3 >= ((int64_t)1 << 31) || (int64_t)B * H * W >= ((int64_t)1 << 30)) return false;
+    return B < (1 << 18);
+}
+
+int64_t spf_regr3d_scratch_bytes(int32_t B, int32_t H, int32_t W) {
+    if (!regr3d_sizes_ok(B, H, W)) return -1;
+    return 4 * spf::regr3d_scratch_words(B, H, W);
+}
+
+static int check_regr3d(const SpfRegr3d* a) {
+    if (!a) return fail(SPF_E_INVALID, "regr3d: args is null");
+    if (!a->gt_pts1 || !a->gt_pts2 || !a->pr_pts1 || !a->pr_pts2) return fail(SPF_E_INVALID, "regr3d: null pointer");
+    if (!a->has_dist_clip && (!a->conf1 || !a->conf2))
+        return fail(SPF_E_INVALID, "regr3d: null confidences (they are needed unless dist_clip is given)");
+    if (a->B < 1 || a->H < 1 || a->W < 1)
+        return fail(SPF_E_INVALID, "regr3d: B, H, W must be positive (got %d %d %d)", a->B, a->H, a->W);
+    if (!regr3d_sizes_ok(a->B, a->H, a->W))
+        return fail(SPF_E_INVALID, "regr3d: %d x %d x %d points is too large", a->B, a->H, a->W);
+    if (a->stride_gt1 < 0 || a->stride_gt2 < 0 || a->stride_pr1 < 0 || a->stride_pr2 < 0)
+        return fail(SPF_E_INVALID, "regr3d: negative batch strides are not supported");
+    if (a->has_dist_clip && a->dist_clip != a->dist_clip) return fail(SPF_E_INVALID, "regr3d: dist_clip is NaN");
+    if ((reinterpret_cast<uintptr_t>(a->gt_pts1) | reinterpret_cast<uintptr_t>(a->gt_pts2) |
+         reinterpret_cast<uintptr_t>(a->pr_pts1) | reinterpret_cast<uintptr_t>(a->pr_pts2) |
+         reinterpret_cast<uintptr_t>(a->conf1) | reinterpret_cast<uintptr_t>(a->conf2)) & 3)
+        return fail(SPF_E_INVALID, "regr3d: tensors must be 4-byte aligned");
+    return SPF_OK;
+}
+
+int spf_regr3d_forward(const SpfRegr3d* args, void* scratch, float* stats, float* loss, void* stream_) {
+    if (int rc = check_regr3d(args)) return rc;
+    if (!scratch || !stats || !loss) return fail(SPF_E_INVALID, "regr3d: null pointer");
+    if (reinterpret_cast<uintptr_t>(scratch) & 15) return fail(SPF_E_INVALID, "regr3d: scratch must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(stats) | reinterpret_cast<uintptr_t>(loss)) & 3)
+        return fail(SPF_E_INVALID, "regr3d: stats and loss must be 4-byte aligned");
+    SPF_HIP(spf::launch_regr3d_fwd(*args, scratch, stats, loss, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_regr3d_backward(const SpfRegr3d* args, const void* scratch, const float* stats, const float* dL_dloss,
+                        float* d_pr1, float* d_pr2, void* stream_) {
+    if (int rc = check_regr3d(args)) return rc;
+    if (!scratch || !stats || !dL_dloss) return fail(SPF_E_INVALID, "regr3d: null pointer");
+    if (!d_pr1 && !d_pr2) return fail(SPF_E_INVALID, "regr3d: no gradient requested");
+    if (reinterpret_cast<uintptr_t>(scratch) & 15) return fail(SPF_E_INVALID, "regr3d: scratch must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_pr1) | reinterpret_cast<uintptr_t>(d_pr2) | reinterpret_cast<uintptr_t>(stats) |
+         reinterpret_cast<uintptr_t>(dL_dloss)) & 3)
+        return fail(SPF_E_INVALID, "regr3d: gradients, stats and dL_dloss must be 4-byte aligned");
+    SPF_HIP(spf::launch_regr3d_bwd(*args, scratch, stats, dL_dloss, d_pr1, d_pr2, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
 

@@ -16,6 +16,9 @@ here                   reference (/root/reference/src/loss/)
 ``LossLpipsCfgWrapper`` loss_lpips.py:22-24
 ``LossLpips``          loss_lpips.py:57-85: ``weight * LPIPS(net="vgg")(prediction, image, normalize=True).mean()`` over
                        the ``b v`` images, 0 before ``apply_after_step``; the network is spfsplatv2_amd/lpips.py
+``Regr3D``             loss_point.py:188-254 (+ normalize_pointcloud, geometry/ptc_geometry.py:270-328): the distillation
+                       point loss, as model_wrapper.py:171 builds it and :323-331 calls it
+``regr3d_loss``        the same as a function; ``return_stats=True`` also returns the counts, thresholds and norms
 =====================  =========================================================================
 
 The reference evaluates the expression with eager PyTorch (four kernels forward, four backward over the rendered
@@ -366,3 +369,152 @@ class LossLpips(Loss[LossLpipsCfg, LossLpipsCfgWrapper]):
         if not isinstance(self.weights, LpipsWeights):
             self.weights = resolve_weights(self.weights)
         return lpips_mean(pred, img, self.weights, normalize=True, weight=self.cfg.weight)
+
+
+# ---- distillation point loss ---------------------------------------------------------------------------------------
+def _regr3d_rows(t: Tensor) -> Tensor:
+    """A [B,H,W,3] operand the kernels can read in place: float32, every batch item's H*W*3 floats contiguous, a
+    non-negative batch stride, 4-byte aligned.  The caller's ``means[:, i].squeeze(-2)`` views pass as they are."""
+    if t.dtype != torch.float32:
+        t = t.float()
+    b, h, w, _ = t.shape
+    ok = t.stride(3) == 1 and (w == 1 or t.stride(2) == 3) and (h == 1 or t.stride(1) == 3 * w) and \
+        (b == 1 or t.stride(0) >= 0)
+    return t if ok else t.contiguous()
+
+
+def _regr3d_args(gt1, gt2, pr1, pr2, c1, c2, dist_clip, disable_view1, normalize, gt_scale):
+    b, h, w, _ = gt1.shape
+
+    def ptr(t):
+        return C.c_void_p(t.data_ptr() if t is not None else None)
+    return _lib.SpfRegr3d(ptr(gt1), ptr(gt2), ptr(pr1), ptr(pr2), ptr(c1), ptr(c2), gt1.stride(0), gt2.stride(0),
+                          pr1.stride(0), pr2.stride(0), b, h, w, int(dist_clip is not None),
+                          float(dist_clip) if dist_clip is not None else 0.0, int(bool(disable_view1)),
+                          int(bool(normalize)), int(bool(gt_scale)))
+
+
+class _Regr3D(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gt1: Tensor, gt2: Tensor, pr1: Tensor, pr2: Tensor, conf1, conf2, dist_clip, disable_view1: bool,
+                normalize: bool, gt_scale: bool):
+        gt1, gt2, pr1, pr2 = (_regr3d_rows(t) for t in (gt1, gt2, pr1, pr2))
+        c1, c2 = ((None, None) if dist_clip is not None else
+                  tuple(c.to(torch.float32).contiguous() for c in (conf1, conf2)))
+        b, h, w, _ = gt1.shape
+        lib = _lib.load()
+        dev = gt1.device
+        args = _regr3d_args(gt1, gt2, pr1, pr2, c1, c2, dist_clip, disable_view1, normalize, gt_scale)
+        nbytes = lib.spf_regr3d_scratch_bytes(b, h, w)
+        if nbytes < 0:
+            raise RuntimeError(f"regr3d_loss: {b} x {h} x {w} points is not a supported size")
+        scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+        stats = torch.empty(8 * b, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(lib.spf_regr3d_forward(C.byref(args), C.c_void_p(scratch.data_ptr()),
+                                              C.c_void_p(stats.data_ptr()), C.c_void_p(loss.data_ptr()), stream),
+                       "spf_regr3d_forward")
+        ctx.save_for_backward(gt1, gt2, pr1, pr2, c1, c2, scratch, stats)
+        ctx.params = (dist_clip, disable_view1, normalize, gt_scale)
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, grad, _grad_stats):
+        gt1, gt2, pr1, pr2, c1, c2, scratch, stats = ctx.saved_tensors
+        need1, need2 = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        dev = gt1.device
+        g = grad.to(torch.float32).reshape(1).contiguous()
+        d1 = torch.empty(pr1.shape, dtype=torch.float32, device=dev) if need1 else None
+        d2 = torch.empty(pr2.shape, dtype=torch.float32, device=dev) if need2 else None
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr() if t is not None else None)
+        lib = _lib.load()
+        args = _regr3d_args(gt1, gt2, pr1, pr2, c1, c2, *ctx.params)
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(lib.spf_regr3d_backward(C.byref(args), ptr(scratch), ptr(stats), ptr(g), ptr(d1), ptr(d2),
+                                               stream), "spf_regr3d_backward")
+        return None, None, d1, d2, None, None, None, None, None, None
+
+
+def regr3d_loss(gt_pts1: Tensor, gt_pts2: Tensor, pr_pts1: Tensor, pr_pts2: Tensor, conf1: Tensor | None = None,
+                conf2: Tensor | None = None, *, dist_clip: float | None = None, disable_view1: bool = False,
+                norm_mode="avg_dis", gt_scale: bool = False, return_stats: bool = False):
+    """``Regr3D(norm_mode, gt_scale=gt_scale)(gt_pts1, gt_pts2, pr_pts1, pr_pts2, conf1, conf2, dist_clip,
+    disable_view1)`` (loss_point.py:208-254) on the HIP library: point maps [B,H,W,3], confidences [B,H,W] -> a 0-dim
+    float32 loss.  ``dist_clip is None``: a point is valid when its ground-truth norm lies within the row's 0.2 % and
+    99.8 % quantiles (torch.quantile's definition, found by an exact radix select) and its confidence is >= 3;
+    otherwise when the norm is <= dist_clip (the confidences are not read).  Predictions and ground truth are divided by
+    their mean valid norm, jointly over the two views and per batch item (``norm_mode='avg_dis'``; falsy: not at all;
+    ``gt_scale``: predictions only); the loss is the mean distance over all valid points of view 1 plus that of view 2
+    (view 2 alone with ``disable_view1``).  A view without a valid point gives NaN, as the mean of nothing does in the
+    reference, with finite gradients.
+
+    Gradients flow to pr_pts1 and pr_pts2 only -- directly and through their normalisation factor -- and invalid points
+    get exactly 0.  bf16 / f16 / f64 inputs are computed in float32 and their gradients cast back by autograd.  The
+    predictions may be strided views of ``[b,v,h,w,1,3]`` (``means[:, i].squeeze(-2)``): they are read in place.
+    Nothing synchronises the host.
+
+    ``return_stats=True``: also a dict of device tensors -- ``n_valid`` [2,B] int32, ``q`` [2,B,2] (q_lo, q_hi; with
+    dist_clip: 0, dist_clip), ``nf_pr`` [B], ``nf_gt`` [B]."""
+    if norm_mode and norm_mode != "avg_dis":
+        raise NotImplementedError(f"regr3d_loss: norm_mode {norm_mode!r} is not implemented (only 'avg_dis' or none)")
+    pts = (("gt_pts1", gt_pts1), ("gt_pts2", gt_pts2), ("pr_pts1", pr_pts1), ("pr_pts2", pr_pts2))
+    confs = (("conf1", conf1), ("conf2", conf2))
+    if dist_clip is None and (conf1 is None or conf2 is None):
+        raise ValueError("regr3d_loss: conf1 and conf2 are needed unless dist_clip is given")
+    given = pts + tuple((n, c) for n, c in confs if c is not None)
+    for name, t in given:
+        if not isinstance(t, Tensor):
+            raise TypeError(f"regr3d_loss: {name} must be a tensor")
+    for name, t in given:
+        if t.requires_grad and not name.startswith("pr_"):
+            raise ValueError(f"regr3d_loss: {name} requires grad, but gradients flow to pr_pts1 and pr_pts2 only; "
+                             "detach it")
+    for name, t in given:
+        if not t.is_cuda:
+            raise RuntimeError(f"regr3d_loss: {name} is on {t.device}; this build only runs on a HIP device (no CPU "
+                               "fallback)")
+        if not t.is_floating_point():
+            raise RuntimeError(f"regr3d_loss: {name} must be a floating-point tensor, got {t.dtype}")
+    shape = tuple(gt_pts1.shape)
+    if len(shape) != 4 or shape[-1] != 3 or gt_pts1.numel() == 0:
+        raise RuntimeError(f"regr3d_loss: gt_pts1 must be a non-empty [B,H,W,3], got {shape}")
+    for name, t in pts[1:]:
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"regr3d_loss: {name} {tuple(t.shape)} does not match gt_pts1 {shape}")
+    for name, c in confs:
+        if c is not None and dist_clip is None and tuple(c.shape) != shape[:3]:
+            raise RuntimeError(f"regr3d_loss: {name} {tuple(c.shape)} does not match the point maps {shape[:3]}")
+    if dist_clip is not None:
+        dist_clip = float(dist_clip)
+    # (cast here, not inside the function: autograd then casts the gradients back to the inputs' type)
+    pr_pts1, pr_pts2 = (t if t.dtype == torch.float32 else t.float() for t in (pr_pts1, pr_pts2))
+    loss, stats = _Regr3D.apply(gt_pts1, gt_pts2, pr_pts1, pr_pts2, conf1, conf2, dist_clip, bool(disable_view1),
+                                bool(norm_mode), bool(gt_scale))
+    if not return_stats:
+        return loss
+    b = shape[0]
+    return loss, {"n_valid": stats[:2 * b].view(torch.int32).view(2, b), "q": stats[2 * b:6 * b].view(2, b, 2),
+                  "nf_pr": stats[6 * b:7 * b], "nf_gt": stats[7 * b:8 * b]}
+
+
+class Regr3D(nn.Module):
+    """The reference's ``Regr3D`` (loss_point.py:188-254), constructor and call signature: drops into
+    model_wrapper.py:171 and :326.  ``alpha`` is kept as an attribute, as there; nothing reads it."""
+
+    def __init__(self, norm_mode="avg_dis", alpha=0.2, gt_scale=False):
+        super().__init__()
+        if norm_mode and norm_mode != "avg_dis":
+            raise NotImplementedError(f"Regr3D: norm_mode {norm_mode!r} is not implemented (only 'avg_dis' or none)")
+        self.norm_mode = norm_mode
+        self.alpha = alpha
+        self.gt_scale = gt_scale
+
+    def forward(self, gt_pts1, gt_pts2, pr_pts1, pr_pts2, conf1=None, conf2=None, dist_clip=None, disable_view1=False):
+        return regr3d_loss(gt_pts1, gt_pts2, pr_pts1, pr_pts2, conf1, conf2, dist_clip=dist_clip,
+                           disable_view1=disable_view1, norm_mode=self.norm_mode, gt_scale=self.gt_scale)
