@@ -35,6 +35,12 @@
  *                           normalize_pointcloud 'avg_dis', src/geometry/ptc_geometry.py:270-328, and invalid_to_zeros,
  *                           src/model/encoder/backbone/croco/misc.py:129-138) as src/model/model_wrapper.py:171,323-331
  *                           builds and calls it, with its autograd backward to the two predicted point maps.
+ *   spf_pose_compose_*      process_pose (src/model/encoder/encoder_spfsplatv2.py:340-359 with convert_pose_to_4x4,
+ *                           src/misc/cam_utils.py:275-286; the VGGT variant encoder_spfsplatv2l.py:248-269) and its backward.
+ *   spf_depth_project_*     depth_projector / process_depth (src/misc/cam_utils.py:310-318) and its backward.
+ *   spf_pose_error          compute_pose_error (src/evaluation/metrics.py:70-99) for N pairs, with the three means.
+ *   spf_focal_*             estimate_focal_knowing_depth 'weiszfeld' and estimate_intrinsics
+ *                           (src/misc/intrinsics_utils.py:33-108,162-174), one focal per scene.
  *
  * Return value of every int function: 0 = success, otherwise a negative SPF_E_* code;
  * spf_last_error() returns a host string describing the most recent failure on this thread.
@@ -50,7 +56,9 @@ extern "C" {
 #endif
 
 #define SPF_ABI_VERSION 7   /* unchanged by the spf_regr3d_* family: it only ADDS a struct and three entry points; no
-                              existing struct, signature or meaning moved, so a caller built against 7 still fits */
+                              existing struct, signature or meaning moved, so a caller built against 7 still fits.
+                              The same holds for the pose path (spf_pose_compose_*, spf_depth_project_*, spf_pose_error,
+                              spf_focal_*): eight entry points added, nothing moved */
 
 #define SPF_OK 0
 #define SPF_E_INVALID (-1)   /* bad argument (null pointer, size, unsupported degree ...) */
@@ -476,6 +484,60 @@ int spf_regr3d_forward(const SpfRegr3d* args, void* scratch, float* stats, float
  * exactly 0. */
 int spf_regr3d_backward(const SpfRegr3d* args, const void* scratch, const float* stats, const float* dL_dloss,
                         float* d_pr1, float* d_pr2, void* stream);
+
+/* The pose path.  Every function: float32 in and out, no allocation, no synchronisation, no atomics; every float sum has
+ * one order, so a run repeats bitwise and a strided view gives the bits of its contiguous copy.
+ *
+ * Pose composition (process_pose).  enc[b, v, 9]: view (s, i) starts at enc + s * stride_b + i * stride_v floats, its nine
+ * floats are contiguous.  Encodings:
+ *   SPF_POSE_ROT6D  columns 0:3 = a1, 3:6 = a2: b1 = a1 / max(|a1|, 1e-12), b2 = normalise(a2 - (b1 . a2) b1) likewise,
+ *                   b3 = b1 x b2 are the ROWS of R; columns 6:9 = t; (R, t) is camera -> world.
+ *   SPF_POSE_QUAT   ("absT_quaR_FoV") columns 0:3 = T, 3:7 = a scalar-LAST quaternion that is NOT normalised
+ *                   (two_s = 2 / sum q^2), 7:9 ignored (zero gradient); (R, T) is world -> camera and the pose is its
+ *                   closed-form inverse [R^T | -R^T T].
+ * make_baseline_1: all translations of a scene are divided by |t_0 - t_{context_views - 1}|.  make_relative: every view is
+ * left-multiplied by the GENERAL inverse (float64) of view 0.  poses[b, v, 4, 4] contiguous, bottom rows exactly 0 0 0 1.
+ * The backward recomputes everything from enc: dL_dposes[b, v, 4, 4] -> dL_denc[b, v, 9], both contiguous. */
+#define SPF_POSE_ROT6D 0
+#define SPF_POSE_QUAT 1
+int spf_pose_compose_forward(const float* enc, int64_t stride_b, int64_t stride_v, int32_t b, int32_t v,
+                             int32_t context_views, int32_t encoding, int32_t make_baseline_1, int32_t make_relative,
+                             float* poses, void* stream);
+int spf_pose_compose_backward(const float* enc, int64_t stride_b, int64_t stride_v, int32_t b, int32_t v,
+                              int32_t context_views, int32_t encoding, int32_t make_baseline_1, int32_t make_relative,
+                              const float* dL_dposes, float* dL_denc, void* stream);
+
+/* Depth projection (depth_projector): depth[i, p] = (inverse(poses[i]) [pts[i, p], 1])_z for pts[N, n, 3] (image i starts
+ * i * stride_img floats from pts, its 3 n floats are contiguous; a 16-byte aligned image is read with 16-byte loads) and
+ * poses[N, 4, 4] contiguous; the inverse is a general float64 inverse, once per image.  depth[N, n] contiguous.
+ * Backward: dL_dpts[N, n, 3] contiguous (may be NULL) = g W[2, :3]; dL_dposes[N, 4, 4] (may be NULL, then gpartial too) =
+ * -W^T dW W^T with dW[2, :] = sum_p g [p, 1], summed over gpartial: 4 floats per slot, 16-byte aligned,
+ * spf_depth_project_partial_blocks(N, n) slots (-1 for sizes the calls would reject). */
+int64_t spf_depth_project_partial_blocks(int32_t N, int32_t n);
+int spf_depth_project_forward(const float* pts, int64_t stride_img, const float* poses, int32_t N, int32_t n, float* depth,
+                              void* stream);
+int spf_depth_project_backward(const float* pts, int64_t stride_img, const float* poses, int32_t N, int32_t n,
+                               const float* dL_ddepth, float* dL_dpts, float* gpartial, float* dL_dposes, void* stream);
+
+/* Pose errors of N pairs of 4x4 poses (contiguous), one launch: errors[N, 3] = (error_t, error_t_scale, error_R) per pair
+ * and means[3].  error_R = deg |acos(clamp((tr(R_pred^T R_gt) - 1) / 2, -1, 1))|; error_t = deg acos(clamp(t . t_gt /
+ * (|t| |t_gt| + 1e-9), -1, 1)), then min(e, 180 - e); error_t_scale = |t - t_gt|.  Evaluated in float64 and rounded at the
+ * store (the reference's float32 acos loses up to 0.03 degrees near 0 and 180). */
+int spf_pose_error(const float* pred, const float* gt, int32_t N, float* errors, float* means, void* stream);
+
+/* Focal estimate (estimate_focal_knowing_depth, 'weiszfeld'), one focal per scene over the H W points of ONE image: scene s
+ * starts s * stride_scene floats from pts, its row i another i * stride_row, a row's 3 W floats are contiguous.  Valid:
+ * z > 0 (NaN is not).  a = (x / z, y / z) with +-inf and NaN replaced by 0; pixel (j - pp_x, i - pp_y), pp a device pointer
+ * to one pair (pp_stride 0) or one per scene (pp_stride 2), NULL: (W / 2, H / 2).  f0 = sum a . px / sum a . a, focal_base =
+ * max(H, W) / (2 tan 30 deg) if f0 <= 0; ten rounds f = sum w (a . px) / sum w (a . a), w = 1 / max(|px - f a|, 1e-8); clip to
+ * [min_focal, max_focal] focal_base; focal_base if the result is <= 0.  No valid point gives NaN (NaN takes no <= 0
+ * branch).  Per-point float32, the running sums float64.  focal[B]; intrinsics[B, 3, 3] (may be NULL) = rows (f, 0, cx) /
+ * div0, (0, f, cy) / div1, (0, 0, 1) in float32.  spf_focal_scratch_bytes: bytes of scratch the call needs (16-byte
+ * aligned; 0 today -- a scene is one block's work -- and then scratch may be NULL), -1 for sizes it would reject. */
+int64_t spf_focal_scratch_bytes(int32_t B, int32_t H, int32_t W);
+int spf_focal_estimate(const float* pts, int64_t stride_scene, int64_t stride_row, int32_t B, int32_t H, int32_t W,
+                       const float* pp, int64_t pp_stride, float min_focal, float max_focal, float cx, float cy, float div0,
+                       float div1, void* scratch, float* focal, float* intrinsics, void* stream);
 
 /* SSIM (ssim / SSIM, src/loss/loss_ssim.py:58-189, and compute_ssim, src/evaluation/metrics.py:36-52) of X, Y [N,C,H,W]
  * contiguous float32, every H x W plane on its own.  With the 1-D window win[0 .. ws) (ws odd, 3 .. 33) applied along

@@ -123,6 +123,20 @@ SYMBOLS = {
     "spf_regr3d_forward": (C.c_int, [C.POINTER(SpfRegr3d), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_regr3d_backward": (C.c_int, [C.POINTER(SpfRegr3d), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
+    "spf_pose_compose_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "spf_pose_compose_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_depth_project_partial_blocks": (C.c_int64, [C.c_int32, C.c_int32]),
+    "spf_depth_project_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                            C.c_void_p]),
+    "spf_depth_project_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_pose_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_focal_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "spf_focal_estimate": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_ssim_partial_blocks": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "spf_ssim_forward": (C.c_int, [C.POINTER(SpfSsim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_ssim_backward": (C.c_int, [C.POINTER(SpfSsim), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1,8 +1,11 @@
 // extern "C" entry points of libspfsplat_hip.so (see include/spfsplat_hip.h).
 // Validation + launch sequencing only; no device allocation, no device synchronisation.
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
+
+#include <initializer_list>
 
 #include "spf_common.h"
 
@@ -36,6 +39,16 @@ hipError_t launch_reproj_bwd(const SpfReproj&, const float*, const float*, float
 int64_t regr3d_scratch_words(int, int, int);
 hipError_t launch_regr3d_fwd(const SpfRegr3d&, void*, float*, float*, hipStream_t);
 hipError_t launch_regr3d_bwd(const SpfRegr3d&, const void*, const float*, const float*, float*, float*, hipStream_t);
+hipError_t launch_pose_compose_fwd(const float*, int64_t, int64_t, int, int, int, int, int, int, float*, hipStream_t);
+hipError_t launch_pose_compose_bwd(const float*, int64_t, int64_t, int, int, int, int, int, int, const float*, float*,
+                                   hipStream_t);
+int64_t depth_slots(int, int, int*);
+hipError_t launch_depth_fwd(const float*, int64_t, const float*, int, int, float*, hipStream_t);
+hipError_t launch_depth_bwd(const float*, int64_t, const float*, int, int, const float*, float*, float*, float*,
+                            hipStream_t);
+hipError_t launch_pose_error(const float*, const float*, int, float*, float*, hipStream_t);
+hipError_t launch_focal(const float*, int64_t, int64_t, int, int, int, const float*, int64_t, float, float, float, float,
+                        float, float, float, float*, float*, hipStream_t);
 int64_t ssim_slots(int, int, int, int, int);
 hipError_t launch_ssim_fwd(const SpfSsim&, float*, float*, float*, hipStream_t);
 hipError_t launch_ssim_bwd(const SpfSsim&, const float*, const float*, float*, float*, hipStream_t);
@@ -747,6 +760,123 @@ int spf_regr3d_backward(const SpfRegr3d* args, const void* scratch, const float*
          reinterpret_cast<uintptr_t>(dL_dloss)) & 3)
         return fail(SPF_E_INVALID, "regr3d: gradients, stats and dL_dloss must be 4-byte aligned");
     SPF_HIP(spf::launch_regr3d_bwd(*args, scratch, stats, dL_dloss, d_pr1, d_pr2, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+static bool aligned4(std::initializer_list<const void*> ps) {
+    uintptr_t x = 0;
+    for (const void* p : ps) x |= reinterpret_cast<uintptr_t>(p);
+    return (x & 3) == 0;
+}
+
+static int check_pose_compose(const float* enc, int64_t stride_b, int64_t stride_v, int32_t b, int32_t v, int32_t cv,
+                              int32_t encoding) {
+    if (!enc) return fail(SPF_E_INVALID, "pose_compose: enc is null");
+    if (b < 1 || v < 1) return fail(SPF_E_INVALID, "pose_compose: b and v must be positive (got %d %d)", b, v);
+    if ((int64_t)b * v >= ((int64_t)1 << 26)) return fail(SPF_E_INVALID, "pose_compose: %d x %d poses is too large", b, v);
+    if (cv < 1 || cv > v) return fail(SPF_E_INVALID, "pose_compose: context_views %d is outside 1..%d", cv, v);
+    if (encoding != SPF_POSE_ROT6D && encoding != SPF_POSE_QUAT)
+        return fail(SPF_E_INVALID, "pose_compose: unknown encoding %d", encoding);
+    if (stride_b < 0 || stride_v < 0) return fail(SPF_E_INVALID, "pose_compose: negative strides are not supported");
+    return SPF_OK;
+}
+
+int spf_pose_compose_forward(const float* enc, int64_t stride_b, int64_t stride_v, int32_t b, int32_t v, int32_t cv,
+                             int32_t encoding, int32_t make_baseline_1, int32_t make_relative, float* poses,
+                             void* stream_) {
+    if (int rc = check_pose_compose(enc, stride_b, stride_v, b, v, cv, encoding)) return rc;
+    if (!poses) return fail(SPF_E_INVALID, "pose_compose: poses is null");
+    if (!aligned4({enc, poses})) return fail(SPF_E_INVALID, "pose_compose: tensors must be 4-byte aligned");
+    SPF_HIP(spf::launch_pose_compose_fwd(enc, stride_b, stride_v, b, v, cv, encoding, make_baseline_1 != 0,
+                                         make_relative != 0, poses, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_pose_compose_backward(const float* enc, int64_t stride_b, int64_t stride_v, int32_t b, int32_t v, int32_t cv,
+                              int32_t encoding, int32_t make_baseline_1, int32_t make_relative, const float* dL_dposes,
+                              float* dL_denc, void* stream_) {
+    if (int rc = check_pose_compose(enc, stride_b, stride_v, b, v, cv, encoding)) return rc;
+    if (!dL_dposes || !dL_denc) return fail(SPF_E_INVALID, "pose_compose: null gradient pointer");
+    if (!aligned4({enc, dL_dposes, dL_denc})) return fail(SPF_E_INVALID, "pose_compose: tensors must be 4-byte aligned");
+    SPF_HIP(spf::launch_pose_compose_bwd(enc, stride_b, stride_v, b, v, cv, encoding, make_baseline_1 != 0,
+                                         make_relative != 0, dL_dposes, dL_denc, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+static bool depth_sizes_ok(int32_t N, int32_t n) {
+    // (a point number times 3 is a 32-bit index inside an image; slots are 64-bit)
+    return N >= 1 && n >= 1 && (int64_t)n * 3 < ((int64_t)1 << 31) && N < (1 << 24);
+}
+
+int64_t spf_depth_project_partial_blocks(int32_t N, int32_t n) {
+    if (!depth_sizes_ok(N, n)) return -1;
+    return spf::depth_slots(N, n, nullptr);
+}
+
+static int check_depth(const float* pts, int64_t stride_img, const float* poses, int32_t N, int32_t n) {
+    if (!pts || !poses) return fail(SPF_E_INVALID, "depth_project: null pointer");
+    if (N < 1 || n < 1) return fail(SPF_E_INVALID, "depth_project: N and n must be positive (got %d %d)", N, n);
+    if (!depth_sizes_ok(N, n)) return fail(SPF_E_INVALID, "depth_project: %d x %d points is too large", N, n);
+    if (stride_img < 0) return fail(SPF_E_INVALID, "depth_project: a negative image stride is not supported");
+    return SPF_OK;
+}
+
+int spf_depth_project_forward(const float* pts, int64_t stride_img, const float* poses, int32_t N, int32_t n,
+                              float* depth, void* stream_) {
+    if (int rc = check_depth(pts, stride_img, poses, N, n)) return rc;
+    if (!depth) return fail(SPF_E_INVALID, "depth_project: depth is null");
+    if (!aligned4({pts, poses, depth})) return fail(SPF_E_INVALID, "depth_project: tensors must be 4-byte aligned");
+    SPF_HIP(spf::launch_depth_fwd(pts, stride_img, poses, N, n, depth, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_depth_project_backward(const float* pts, int64_t stride_img, const float* poses, int32_t N, int32_t n,
+                               const float* dL_ddepth, float* dL_dpts, float* gpartial, float* dL_dposes,
+                               void* stream_) {
+    if (int rc = check_depth(pts, stride_img, poses, N, n)) return rc;
+    if (!dL_ddepth) return fail(SPF_E_INVALID, "depth_project: dL_ddepth is null");
+    if (!dL_dpts && !dL_dposes) return fail(SPF_E_INVALID, "depth_project: no gradient requested");
+    if ((dL_dposes != nullptr) != (gpartial != nullptr))
+        return fail(SPF_E_INVALID, "depth_project: dL_dposes and gpartial go together");
+    if (!aligned4({pts, poses, dL_ddepth, dL_dpts, dL_dposes}))
+        return fail(SPF_E_INVALID, "depth_project: tensors must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(gpartial) & 15)
+        return fail(SPF_E_INVALID, "depth_project: gpartial must be 16-byte aligned");
+    SPF_HIP(spf::launch_depth_bwd(pts, stride_img, poses, N, n, dL_ddepth, dL_dpts, gpartial, dL_dposes,
+                                  static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_pose_error(const float* pred, const float* gt, int32_t N, float* errors, float* means, void* stream_) {
+    if (!pred || !gt || !errors || !means) return fail(SPF_E_INVALID, "pose_error: null pointer");
+    if (N < 1) return fail(SPF_E_INVALID, "pose_error: N must be positive (got %d)", N);
+    if (!aligned4({pred, gt, errors, means})) return fail(SPF_E_INVALID, "pose_error: tensors must be 4-byte aligned");
+    SPF_HIP(spf::launch_pose_error(pred, gt, N, errors, means, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+static bool focal_sizes_ok(int32_t B, int32_t H, int32_t W) {
+    return B >= 1 && H >= 1 && W >= 1 && (int64_t)H * W * 3 < ((int64_t)1 << 31) && B < (1 << 24);
+}
+
+int64_t spf_focal_scratch_bytes(int32_t B, int32_t H, int32_t W) { return focal_sizes_ok(B, H, W) ? 0 : -1; }
+
+int spf_focal_estimate(const float* pts, int64_t stride_scene, int64_t stride_row, int32_t B, int32_t H, int32_t W,
+                       const float* pp, int64_t pp_stride, float min_focal, float max_focal, float cx, float cy,
+                       float div0, float div1, void* scratch, float* focal, float* intrinsics, void* stream_) {
+    (void)scratch;
+    if (!pts || !focal) return fail(SPF_E_INVALID, "focal_estimate: null pointer");
+    if (B < 1 || H < 1 || W < 1)
+        return fail(SPF_E_INVALID, "focal_estimate: B, H, W must be positive (got %d %d %d)", B, H, W);
+    if (!focal_sizes_ok(B, H, W)) return fail(SPF_E_INVALID, "focal_estimate: %d x %d x %d points is too large", B, H, W);
+    if (stride_scene < 0 || stride_row < 0) return fail(SPF_E_INVALID, "focal_estimate: negative strides are not supported");
+    if (pp_stride != 0 && pp_stride != 2) return fail(SPF_E_INVALID, "focal_estimate: pp_stride must be 0 or 2");
+    if (!aligned4({pts, pp, focal, intrinsics})) return fail(SPF_E_INVALID, "focal_estimate: tensors must be 4-byte aligned");
+    // focal_base as the reference forms it (a Python float), the clip bounds as torch.clip receives them
+    const double base = (double)(H > W ? H : W) / (2.0 * tan(30.0 * 3.14159265358979323846 / 180.0));
+    SPF_HIP(spf::launch_focal(pts, stride_scene, stride_row, B, H, W, pp, pp_stride, (float)base,
+                              (float)((double)min_focal * base), (float)((double)max_focal * base), cx, cy, div0, div1,
+                              focal, intrinsics, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
 
