@@ -474,15 +474,41 @@ class _spf_errors:
         return False
 
 
+class StateViews(NamedTuple):
+    """The fields of SpfState that share a buffer, as named views of the three tensors a forward call returns them in
+    (`rect`, `tiles`, `pair_idx`): the ONE place that knows where each field starts."""
+    rect: Tensor                    # [RG]      packed tile rect
+    zkey: Tensor                    # [RG...]   depth key (float bits), then the SH clamp bytes
+    sh_clamp: Optional[Tensor]      # [..]      SH clamp masks (None: the buffer holds none)
+    tile_count: Tensor              # [RT]
+    tile_flags: Tensor              # [RT]
+    tile_start: Tensor              # [RT + 1]  (direct bins, >= 2,048 tiles: the launch order [RT][2] starts here)
+    tile_fill: Tensor               # [RT]
+    counters: Tensor                # [4]
+    pair_cursor: Optional[Tensor]   # [8]       (None: the compiled binding's buffer has none)
+    pair_off: Tensor                # [2 RG]    (rect, first pair) per (render, Gaussian)
+    blk_total: Tensor               # [RB]
+    blk_base: Tensor                # [RB...]
+
+
+def _state_views(rect, tiles, pair_idx, RT: int, RG: int, RB: int) -> StateViews:
+    """Slice `rect` (packed rect | depth key | SH clamp bytes), `tiles` (tile_count | tile_flags | tile_start (+1) |
+    tile_fill | counters (4) [| pair cursors (8) | padding]) and `pair_idx` (pair_off | blk_total | blk_base) into their
+    fields.  Pure indexing: works on device tensors and on host copies alike (the tests audit host copies with it)."""
+    return StateViews(
+        rect=rect[:RG], zkey=rect[RG:], sh_clamp=rect[2 * RG:] if rect.numel() > 2 * RG else None,
+        tile_count=tiles[:RT], tile_flags=tiles[RT:2 * RT], tile_start=tiles[2 * RT:3 * RT + 1],
+        tile_fill=tiles[3 * RT + 1:4 * RT + 1], counters=tiles[4 * RT + 1:4 * RT + 5],
+        pair_cursor=tiles[4 * RT + 5:4 * RT + 13] if tiles.numel() >= 4 * RT + 13 else None,
+        pair_off=pair_idx[:2 * RG], blk_total=pair_idx[2 * RG:2 * RG + RB], blk_base=pair_idx[2 * RG + RB:])
+
+
 def _state_struct(rec, radii, rect, tiles, pairs, pair_idx, final_T, n_contrib, RT, RG, RB, verdict_host=None):
-    cursor = tiles[4 * RT + 5:4 * RT + 13] if tiles.numel() >= 4 * RT + 13 else None   # (the compiled binding's buffer has none)
-    return _lib.SpfState(_ptr(rec), _ptr(radii), _ptr(rect[:RG]), _ptr(rect[RG:]), _ptr(tiles[:RT]),
-                         _ptr(tiles[2 * RT:3 * RT + 1]),
-                         _ptr(tiles[3 * RT + 1:4 * RT + 1]), _ptr(tiles[RT:2 * RT]),
-                         _ptr(tiles[4 * RT + 1:4 * RT + 5]), _ptr(pairs),
-                         _ptr(pair_idx[:2 * RG]), _ptr(pair_idx[2 * RG:2 * RG + RB]), _ptr(pair_idx[2 * RG + RB:]),
-                         _ptr(final_T), _ptr(n_contrib), _ptr(cursor),
-                         _ptr(rect[2 * RG:]) if rect.numel() > 2 * RG else None, _ptr(verdict_host))
+    v = _state_views(rect, tiles, pair_idx, RT, RG, RB)
+    return _lib.SpfState(_ptr(rec), _ptr(radii), _ptr(v.rect), _ptr(v.zkey), _ptr(v.tile_count), _ptr(v.tile_start),
+                         _ptr(v.tile_fill), _ptr(v.tile_flags), _ptr(v.counters), _ptr(pairs),
+                         _ptr(v.pair_off), _ptr(v.blk_total), _ptr(v.blk_base),
+                         _ptr(final_T), _ptr(n_contrib), _ptr(v.pair_cursor), _ptr(v.sh_clamp), _ptr(verdict_host))
 
 
 def _raise_if_plan_failed(counters: Tensor, capacity: int, plan=None) -> None:

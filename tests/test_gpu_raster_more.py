@@ -1,5 +1,8 @@
 """More GPU parity: long tile lists (every sort size class), colours-precomputed and orthographic entry points,
-gradient switches, degenerate inputs, and size-independent properties at BASELINE's full C2 size."""
+gradient switches, degenerate inputs, and size-independent properties at BASELINE's full C2 size.
+
+The tests here judge binning and the tile sort through images and gradients; the tile lists themselves -- counts, keys,
+order, scan, pair numbering, every sort kernel at its class borders -- are audited as integers in test_gpu_tile_state.py."""
 import functools
 
 import pytest
