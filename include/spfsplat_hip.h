@@ -58,7 +58,7 @@ extern "C" {
 #define SPF_ABI_VERSION 7   /* unchanged by the spf_regr3d_* family: it only ADDS a struct and three entry points; no
                               existing struct, signature or meaning moved, so a caller built against 7 still fits.
                               The same holds for the pose path (spf_pose_compose_*, spf_depth_project_*, spf_pose_error,
-                              spf_focal_*): eight entry points added, nothing moved */
+                              spf_focal_*): eight entry points added, nothing moved; spf_raster_state_layout likewise */
 
 #define SPF_OK 0
 #define SPF_E_INVALID (-1)   /* bad argument (null pointer, size, unsupported degree ...) */
@@ -245,6 +245,21 @@ const char* spf_last_error(void);
 /* Number of tiles per render and size of the vpartial scratch. */
 int spf_raster_num_tiles(int32_t H, int32_t W);
 int spf_raster_view_partial_blocks(int32_t G);
+/* Where the 13 fields of SpfState that the host bindings keep in THREE buffers start, in 4-byte words:
+ *   rect      rect (RG) | zkey (RG) | sh_clamp (RG bytes, rounded up to whole words)
+ *   tiles     tile_count (RT) | tile_flags (RT) | tile_start (RT + 1) | tile_fill (RT) | counters (4) | pair_cursor (8) |
+ *             padding to a multiple of 16 bytes
+ *   pair_idx  pair_off (2 RG) | blk_total (RB) | blk_base (RB)
+ * for RT = R*T tiles, RG = R*G (render, Gaussian) pairs and RB = R * spf_raster_view_partial_blocks(G) blocks; rect,
+ * tile_count and pair_off sit at offset 0.  The one definition: every binding allocates and slices by it.  Host
+ * arithmetic only (no launch, no device, no environment); SPF_E_INVALID unless RT, RG and RB are positive. */
+typedef struct SpfStateLayout {
+    int64_t rect_words, tiles_words, pair_idx_words;                     /* what to allocate */
+    int64_t zkey, sh_clamp;                                              /* offsets into the rect buffer */
+    int64_t tile_flags, tile_start, tile_fill, counters, pair_cursor;    /* offsets into the tiles buffer */
+    int64_t blk_total, blk_base;                                         /* offsets into the pair_idx buffer */
+} SpfStateLayout;
+int spf_raster_state_layout(int64_t RT, int64_t RG, int64_t RB, SpfStateLayout* out);
 /* Which tile (render * T + tile) block slot `slot` (< R*T / 8) of XCD `xcd` (0..7) of a composite lists launch stands for
  * before the end of every XCD's range is sorted longest list first (planned calls on direct bins of >= 2,048 tiles, R*T
  * a multiple of 8): a contiguous range of renders per XCD -- or, for calls of exactly eight renders, strips of 64 tiles
@@ -303,9 +318,8 @@ int spf_raster_forward_project(const SpfDims* d, const SpfInputs* in, SpfState* 
 /* Decoder fast path (the batched DecoderSplattingCUDA.forward, decoder_splatting_cuda.py:41-78): two launches fewer
  * per step than the calls above.
  *   spf_decoder_prepare           = spf_camera_forward AND the clearing of `zero_bytes` bytes at `zero` in ONE kernel.
- *                                   Pass ONE buffer laid out tile_count | tile_flags | tile_start (R*T+1) | tile_fill |
- *                                   counters (4) [| pair_cursor (8) | padding] and clear all of it (16*R*T + 20 bytes,
- *                                   + 32 with the cursors, rounded up to 16; 16-byte aligned);
+ *                                   Pass the tiles buffer of SpfStateLayout and clear all of it (4 * tiles_words bytes;
+ *                                   16-byte aligned; without the cursors and the padding: 16*R*T + 20 bytes, rounded up);
  *   spf_raster_forward_project_prepared = spf_raster_forward_project without its own clearing.  `cleared_bytes` says how
  *                                   much of that buffer (from tile_count on) the caller cleared: all of it -> the tile scan
  *                                   runs with one block per render instead of a single block; only the first 8*R*T bytes

@@ -26,8 +26,8 @@ class SpfDims(C.Structure):
                 ("bin_cap", C.c_int32), ("pair_capacity", C.c_int64), ("raw_stride", C.c_int64), ("adapter_eps", C.c_float)]
 
 
-def _ptr_struct(name, fields):
-    return type(name, (C.Structure,), {"_fields_": [(f, C.c_void_p) for f in fields]})
+def _ptr_struct(name, fields, ctype=C.c_void_p):
+    return type(name, (C.Structure,), {"_fields_": [(f, ctype) for f in fields]})
 
 
 SpfInputs = _ptr_struct("SpfInputs", ["means3D", "scales", "rotations", "opacities", "shs", "colors",
@@ -41,7 +41,8 @@ SpfGrads = _ptr_struct("SpfGrads", ["dL_dimage", "dL_ddepth", "dL_dalpha", "gpai
                                     "dL_dmeans3D", "dL_dscales", "dL_drotations", "dL_dopacities",
                                     "dL_dshs", "dL_dcolors", "dL_dviewmatrix", "dL_dmeans2D", "dL_dshs_high",
                                     "dL_draw"])
-
+SpfStateLayout = _ptr_struct("SpfStateLayout", ["rect_words", "tiles_words", "pair_idx_words", "zkey", "sh_clamp", "tile_flags",
+                                             "tile_start", "tile_fill", "counters", "pair_cursor", "blk_total", "blk_base"], C.c_int64)
 
 
 class SpfCamera(C.Structure):
@@ -87,6 +88,7 @@ SYMBOLS = {
     "spf_last_error": (C.c_char_p, []),
     "spf_raster_num_tiles": (C.c_int, [C.c_int32, C.c_int32]),
     "spf_raster_view_partial_blocks": (C.c_int, [C.c_int32]),
+    "spf_raster_state_layout": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(SpfStateLayout)]),
     "spf_raster_launch_slot_tile": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "spf_raster_chunks": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "spf_raster_sort_plan": (C.c_int, [C.c_uint32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint32),

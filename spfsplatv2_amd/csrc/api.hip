@@ -314,6 +314,19 @@ int spf_raster_num_tiles(int32_t H, int32_t W) {
     return ((W + SPF_TILE - 1) / SPF_TILE) * ((H + SPF_TILE - 1) / SPF_TILE);
 }
 int spf_raster_view_partial_blocks(int32_t G) { return (G + spf::kBlock - 1) / spf::kBlock; }
+// the ONE place that knows where the fields of the three shared state buffers start (header: SpfStateLayout)
+static SpfStateLayout state_layout(int64_t RT, int64_t RG, int64_t RB) {
+    SpfStateLayout l;
+    l.rect_words = 2 * RG + (RG + 3) / 4, l.zkey = RG, l.sh_clamp = 2 * RG;
+    l.tiles_words = 4 * RT + 16, l.tile_flags = RT, l.tile_start = 2 * RT, l.tile_fill = 3 * RT + 1, l.counters = 4 * RT + 1, l.pair_cursor = 4 * RT + 5;
+    l.pair_idx_words = 2 * RG + 2 * RB, l.blk_total = 2 * RG, l.blk_base = 2 * RG + RB;
+    return l;
+}
+int spf_raster_state_layout(int64_t RT, int64_t RG, int64_t RB, SpfStateLayout* out) {
+    if (!out || RT <= 0 || RG <= 0 || RB <= 0) return fail(SPF_E_INVALID, "state_layout: out is null, or RT, RG, RB not all positive (got %lld %lld %lld)", (long long)RT, (long long)RG, (long long)RB);
+    *out = state_layout(RT, RG, RB);
+    return SPF_OK;
+}
 int spf_raster_launch_slot_tile(int32_t R, int32_t T, int32_t xcd, int32_t slot) {
     if (R < 1 || T < 1 || (int64_t)R * T > (int64_t)1 << 30 || (((int64_t)R * T) & 7) != 0) return -1;
     const int RT = R * T;
@@ -422,11 +435,11 @@ static int forward_project_cleared(const SpfDims* d, const SpfInputs* in, SpfSta
     // the caller cleared.  All of it: one-block-per-render scan.  Only the two count arrays (the older contract): the
     // self-initialising single-block scan.  Less than that: this call clears the counts itself.
     if (!d || !st) return fail(SPF_E_INVALID, "dims / state is null");
-    const uint64_t RT = (uint64_t)d->S * d->V * spf_raster_num_tiles(d->H, d->W);
-    const bool laid_out = st->tile_count && st->tile_flags == st->tile_count + RT && st->tile_start == st->tile_flags + RT &&
-                          st->tile_fill == st->tile_start + RT + 1 && st->counters == st->tile_fill + RT;
-    if (laid_out && cleared_bytes >= 4 * (4 * RT + 5)) return forward_project(d, in, st, 2, stream_, cleared_bytes / 4, cov3D);
-    if (laid_out && cleared_bytes >= 8 * RT) return forward_project(d, in, st, 1, stream_, cleared_bytes / 4, cov3D);
+    const SpfStateLayout l = state_layout((int64_t)d->S * d->V * spf_raster_num_tiles(d->H, d->W), 1, 1);
+    const bool laid_out = st->tile_count && st->tile_flags == st->tile_count + l.tile_flags && st->tile_start == st->tile_count + l.tile_start &&
+                          st->tile_fill == st->tile_count + l.tile_fill && st->counters == st->tile_count + l.counters;
+    if (laid_out && cleared_bytes >= 4 * (uint64_t)(l.counters + 4)) return forward_project(d, in, st, 2, stream_, cleared_bytes / 4, cov3D);
+    if (laid_out && cleared_bytes >= 4 * (uint64_t)l.tile_start) return forward_project(d, in, st, 1, stream_, cleared_bytes / 4, cov3D);
     return forward_project(d, in, st, 0, stream_, 0, cov3D);
 }
 

@@ -56,22 +56,26 @@ SpfInputs make_inputs(const Tensor& means3D, const Tensor& scales, const Tensor&
     return in;
 }
 
-// layout of the state tensors as rasterizer.py allocates them (see _state_struct there)
+// where the fields that share the rect / tiles / pair_idx buffers start: the library's word (spf_raster_state_layout)
+SpfStateLayout state_layout(int64_t RT, int64_t RG, int64_t RB) {
+    SpfStateLayout l;
+    check(spf_raster_state_layout(RT, RG, RB, &l), "spf_raster_state_layout");
+    return l;
+}
+
 SpfState make_state(const Tensor& rec, const Tensor& radii, const Tensor& rect, const Tensor& tiles, const Tensor& pairs,
-                    const Tensor& pair_idx, const Tensor& final_T, const Tensor& n_contrib, int64_t RT, int64_t RG,
-                    int64_t RB) {
+                    const Tensor& pair_idx, const Tensor& final_T, const Tensor& n_contrib, const SpfStateLayout& l) {
     SpfState st;
-    uint32_t* const t = ptr<uint32_t>(tiles);
-    uint32_t* const pi = ptr<uint32_t>(pair_idx);
+    uint32_t *const r = ptr<uint32_t>(rect), *const t = ptr<uint32_t>(tiles), *const pi = ptr<uint32_t>(pair_idx);
     st.rec = ptr<float>(rec); st.radii = ptr<int32_t>(radii);
-    st.rect = ptr<uint32_t>(rect); st.zkey = reinterpret_cast<float*>(ptr<uint32_t>(rect) + RG);
-    st.tile_count = t; st.tile_flags = t + RT; st.tile_start = t + 2 * RT; st.tile_fill = t + 3 * RT + 1;
-    st.counters = t + 4 * RT + 1;
-    st.pair_cursor = tiles.numel() >= 4 * RT + 13 ? t + 4 * RT + 5 : nullptr;
+    st.rect = r; st.zkey = reinterpret_cast<float*>(r + l.zkey);
+    st.tile_count = t; st.tile_flags = t + l.tile_flags; st.tile_start = t + l.tile_start; st.tile_fill = t + l.tile_fill;
+    st.counters = t + l.counters;
+    st.pair_cursor = tiles.numel() >= l.pair_cursor + 8 ? t + l.pair_cursor : nullptr;
     st.pairs = pairs.defined() ? reinterpret_cast<uint64_t*>(pairs.data_ptr()) : nullptr;
-    st.pair_off = pi; st.blk_total = pi + 2 * RG; st.blk_base = pi + 2 * RG + RB;      // pair_off: (rect, first pair) per (render, Gaussian)
+    st.pair_off = pi; st.blk_total = pi + l.blk_total; st.blk_base = pi + l.blk_base;      // pair_off: (rect, first pair) per (render, Gaussian)
     st.final_T = ptr<float>(final_T); st.n_contrib = ptr<uint32_t>(n_contrib);
-    st.sh_clamp = rect.numel() > 2 * RG ? reinterpret_cast<uint8_t*>(ptr<uint32_t>(rect) + 2 * RG) : nullptr;   // SH clamp masks ride behind rect | zkey
+    st.sh_clamp = rect.numel() > l.sh_clamp ? reinterpret_cast<uint8_t*>(r + l.sh_clamp) : nullptr;   // SH clamp masks ride behind rect | zkey
     st.verdict_host = nullptr;
     return st;
 }
@@ -112,24 +116,24 @@ std::tuple<std::vector<Tensor>, std::vector<int64_t>> raster_forward(
     const int64_t K = have_sh ? shs->size(sh_layout ? 3 : 2) : 0;
     const SpfDims dims = make_dims(S, V, G, K, sh_degree, H, W, scale_modifier, sh_layout, sh_band4);
     const int64_t T = spf_raster_num_tiles((int32_t)H, (int32_t)W), P = H * W, RT = R * T, RG = R * G;
-    const int64_t nblk = spf_raster_view_partial_blocks((int32_t)G), RB = R * nblk;
+    const SpfStateLayout lay = state_layout(RT, RG, R * spf_raster_view_partial_blocks((int32_t)G));
     const auto i32 = means3D.options().dtype(at::kInt), f32 = means3D.options().dtype(at::kFloat);
 
-    Tensor rec = at::empty({RG, 12}, f32), radii = at::empty({RG}, i32), rect = at::empty({2 * RG + (RG + 3) / 4}, i32);
-    Tensor pair_idx = at::empty({2 * RG + 2 * RB}, i32), tiles = at::empty({4 * RT + 16}, i32);
+    Tensor rec = at::empty({RG, 12}, f32), radii = at::empty({RG}, i32), rect = at::empty({lay.rect_words}, i32);
+    Tensor pair_idx = at::empty({lay.pair_idx_words}, i32), tiles = at::empty({lay.tiles_words}, i32);
     Tensor final_T = at::empty({R * P}, f32), n_contrib = at::empty({R * P}, i32);
     Tensor image = at::empty({S, V, 3, H, W}, f32), depth = at::empty({S, V, 1, H, W}, f32),
            alpha = at::empty({S, V, 1, H, W}, f32);
 
     const SpfInputs in = make_inputs(means3D, scales, rotations, opacities, shs, colors, viewmatrix, projmatrix, tanfov,
                                      bg, view_scale, view64);
-    SpfState st = make_state(rec, radii, rect, tiles, Tensor(), pair_idx, final_T, n_contrib, RT, RG, RB);
+    SpfState st = make_state(rec, radii, rect, tiles, Tensor(), pair_idx, final_T, n_contrib, lay);
     void* const stream = c10::hip::getCurrentHIPStream(means3D.device().index()).stream();
     check(spf_raster_forward_project(&dims, &in, &st, stream), "spf_raster_forward_project");
 
     int64_t D = -1;
     if (capacity < 0) {
-        const Tensor host = tiles.narrow(0, 4 * RT + 1, 4).to(at::kCPU);       // D, longest list, verdict, dense tiles
+        const Tensor host = tiles.narrow(0, lay.counters, 4).to(at::kCPU);       // D, longest list, verdict, dense tiles
         const int32_t* h = host.data_ptr<int32_t>();
         D = (int64_t)(uint32_t)h[0]; max_tile = (int64_t)(uint32_t)h[1]; dense = (int64_t)(uint32_t)h[3];
         capacity = D;
@@ -161,7 +165,7 @@ std::vector<Tensor> raster_backward(
     // `capacity`: gradient records (= the forward's pair capacity; with direct bins `pairs` holds the bins instead)
     const SpfDims dims = make_dims(S, V, G, K, sh_degree, H, W, scale_modifier, sh_layout, sh_band4, bin_cap, capacity);
     const int64_t T = spf_raster_num_tiles((int32_t)H, (int32_t)W), RT = R * T, RG = R * G;
-    const int64_t nblk = spf_raster_view_partial_blocks((int32_t)G), RB = R * nblk;
+    const int64_t nblk = spf_raster_view_partial_blocks((int32_t)G);
     const auto f32 = means3D.options().dtype(at::kFloat);
     auto grad_in = [&](const OptTensor& g) -> Tensor {
         if (!g.has_value() || !g->defined()) return Tensor();
@@ -180,7 +184,7 @@ std::vector<Tensor> raster_backward(
 
     const SpfInputs in = make_inputs(means3D, scales, rotations, opacities, shs, colors, viewmatrix, projmatrix, tanfov,
                                      bg, view_scale, view64);
-    const SpfState st = make_state(rec, radii, rect, tiles, pairs, pair_idx, final_T, n_contrib, RT, RG, RB);
+    const SpfState st = make_state(rec, radii, rect, tiles, pairs, pair_idx, final_T, n_contrib, state_layout(RT, RG, R * nblk));
     SpfGrads gr;
     gr.dL_dimage = ptr<const float>(gi); gr.dL_ddepth = ptr<const float>(gd); gr.dL_dalpha = ptr<const float>(ga);
     gr.gpair = ptr<float>(gpair); gr.vpartial = ptr<float>(vpartial);

@@ -553,7 +553,7 @@ class DecoderSplattingCUDA(Decoder[DecoderSplattingCUDACfg]):
 
     def _prepare_step(self, key, gaussians, extrinsics, intrinsics, near, far, image_shape):
         """Prepare the static step; None (and prepare_steps off) when that fails."""
-        from .rasterizer import StaticStep, _direct_bin_cap, _f32c
+        from .rasterizer import StaticStep, _check_camera, _check_gaussians, _check_sh, _direct_bin_cap
         from ._lib import load
         h, w = image_shape
         b, v = extrinsics.shape[:2]
@@ -564,13 +564,10 @@ class DecoderSplattingCUDA(Decoder[DecoderSplattingCUDACfg]):
         if not _direct_bin_cap(self.max_pairs, b * v * T, T):
             return None
         # (shapes as render_batch checks them: a mismatch raises here, once, with the usual message)
-        _f32c(intrinsics, "intrinsics", (b, v, 3, 3)); _f32c(near, "near", (b, v)); _f32c(far, "far", (b, v))
-        _f32c(gaussians.scales, "scales", (b, G, 3)); _f32c(gaussians.rotations, "rotations", (b, G, 4))
-        _f32c(gaussians.opacities, "opacities", (b, G))
-        _f32c(gaussians.harmonics, "shs", (b, G, 3, 16 if high is not None else n))
-        if high is not None:
-            _f32c(high, "shs_high", (b, G, 3, 9))
         band4 = sh_band4_default() if self.sh_band4 is None else bool(self.sh_band4)
+        _check_camera(extrinsics, intrinsics, near, far, b, v)
+        _check_gaussians(gaussians.means, gaussians.scales, gaussians.rotations, gaussians.opacities, None, b, G)
+        _check_sh(b, G, isqrt(n) - 1, band4, gaussians.harmonics, "g3k", high)
         trains = any(key[1])
         want = dict(scales_rot=trains and self.enable_cov_grad and (gaussians.scales.requires_grad or gaussians.rotations.requires_grad),
                     shs=trains and self.enable_sh_grad and gaussians.harmonics.requires_grad, colors=False,

@@ -15,14 +15,15 @@ in the HIP kernels.  There is no CPU path: tensors must live on a HIP device.
 from __future__ import annotations
 
 import ctypes as C
+import inspect
+import os
+from collections import namedtuple
 from typing import NamedTuple, Optional
 
 import torch
 from torch import Tensor
 
 from . import _lib
-
-import os
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_batch", "render_batch", "camera_forward", "StaticStep",
            "last_forward_stats", "PairBudget", "plan_pair_budget", "last_plan_flags", "plan_flags", "CallRecord",
@@ -56,7 +57,7 @@ def _note_band4_not_evaluated(sh_degree: int, sh_band4: bool) -> None:
         warnings.warn("spfsplatv2_amd: sh_degree 4 (25 SH coefficients) is evaluated to degree 3 like the published 3DGS "
                       "kernels; whether the reference's rasterizer fork evaluates band 4 is unknown (oracle/PINNING.md). "
                       "Set SPF_SH_BAND4=1 (or sh_band4=True) to evaluate it, SPF_SH_BAND4=0 to silence this note.",
-                      stacklevel=3)
+                      stacklevel=4)
 
 
 def sh_band4_default() -> bool:
@@ -228,6 +229,58 @@ def _cov6(cov3D: Tensor, S: int, G: int) -> Tensor:
     return _f32c(cov3D, "cov3D", (S, G, 6))
 
 
+def _check_camera(extrinsics, intrinsics, near, far, S: int, V: int):
+    """The camera block of a call, [S,V,4,4] / [S,V,3,3] / [S,V] / [S,V], as dense float32 device tensors."""
+    return (_f32c(extrinsics, "extrinsics", (S, V, 4, 4)), _f32c(intrinsics, "intrinsics", (S, V, 3, 3)),
+            _f32c(near, "near", (S, V)), _f32c(far, "far", (S, V)))
+
+
+def _check_gaussians(means3D, scales, rotations, opacities, cov3D, S: int, G: int, pair: bool = True):
+    """The Gaussian block: means [S,G,3], then the scale/rotation pair or `cov3D` (neither with `pair` False: raw rows
+    carry them), then the opacities as [S,G] -> (means3D, scales, rotations, opacities, cov3D [S,G,6])."""
+    means3D = _f32c(means3D, "means3D", (S, G, 3))
+    if cov3D is not None:
+        cov3D = _cov6(cov3D, S, G)
+    elif pair:
+        scales, rotations = _f32c(scales, "scales", (S, G, 3)), _f32c(rotations, "rotations", (S, G, 4))
+    return means3D, scales, rotations, _f32c(opacities.reshape(S, G), "opacities", (S, G)), cov3D
+
+
+def _check_sh(S, G, sh_degree, sh_band4, shs=None, sh_layout="gk3", shs_high=None, raw=None, sh_mask=None):
+    """The harmonics, however they come -- `shs` [S,G,K,3] ("gk3") or [S,G,3,K] ("g3k"), band-split with `shs_high`
+    [S,G,3,9], raw rows [.., 7+3K] with their `sh_mask` [K], or none (colours) -> (shs, shs_high, sh_mask, K,
+    SpfDims.sh_layout, sh_band4).  `sh_band4` None is resolved FIRST: the count is held against the degree evaluated."""
+    if sh_layout not in ("gk3", "g3k"):
+        raise RuntimeError(f"sh_layout must be 'gk3' or 'g3k', got {sh_layout!r}")
+    layout = 1 if sh_layout == "g3k" else 0
+    if sh_band4 is None:
+        sh_band4 = sh_band4_default()
+        _note_band4_not_evaluated(sh_degree, sh_band4)
+    fewest = (min(sh_degree, 4 if sh_band4 else 3) + 1) ** 2
+    if raw is not None and (not isinstance(raw, Tensor) or not raw.is_cuda or raw.dtype != torch.float32):
+        raise RuntimeError("raw must be a float32 tensor on a HIP device (there is no CPU fallback)")
+    K = _sh_coefficients(shs, 2 if shs_high is not None else layout, raw)
+    if raw is not None:
+        if raw.shape[-1] != 7 + 3 * K or K < 1 or raw.numel() != S * G * raw.shape[-1]:
+            raise RuntimeError(f"raw must hold S*G = {S * G} rows of 7 + 3*d_sh channels, got {tuple(raw.shape)}")
+        if not (0 <= sh_degree <= 4) or K < fewest:
+            raise RuntimeError(f"raw holds {K} coefficients per channel, too few for sh_degree {sh_degree}")
+        if sh_mask is None:
+            raise RuntimeError("raw rows need the adapter's sh_mask")
+        sh_mask, layout = _f32c(sh_mask, "sh_mask", (K,)), 3
+    elif shs_high is not None:
+        if shs is None or not layout:
+            raise RuntimeError("shs_high (band 4 of the band-split layout) goes with shs [S,G,3,16] and sh_layout='g3k'")
+        shs, shs_high, layout = _f32c(shs, "shs", (S, G, 3, 16)), _f32c(shs_high, "shs_high", (S, G, 3, 9)), 2
+    elif shs is not None:
+        if K < fewest:
+            raise RuntimeError(f"shs holds {K} coefficients, too few for sh_degree {sh_degree}")
+        shs = _f32c(shs, "shs", (S, G, 3, K) if layout else (S, G, K, 3))
+    if not (0 <= sh_degree <= 4):
+        raise RuntimeError(f"sh_degree {sh_degree} outside 0..4")
+    return shs, shs_high, sh_mask, K, layout, bool(sh_band4)
+
+
 def _stream_ptr(device) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
@@ -258,35 +311,80 @@ def _early_verdict(dev: torch.device):
     return got
 
 
+_Inputs = namedtuple("_Inputs", [f for f, _ in _lib.SpfInputs._fields_], defaults=(None,) * 5)   # SpfInputs, field for field
+_State = namedtuple("_State", "rec radii rect tiles pairs pair_idx final_T n_contrib")            # what a forward leaves behind
+_Geometry = namedtuple("_Geometry", "S V G K sh_degree H W scale_modifier sh_layout sh_band4 plan_mode")   # (_plan_mode)
+_Plan = namedtuple("_Plan", "dense bin_cap capacity")   # dense-tile hint, bin size (0: packed lists), pair = record capacity
+_Forward = namedtuple("_Forward", "outs state plan")      # _forward_impl's; outs: (image, depth, alpha, radii [S,V,G])
+# every gradient under its input's name, None where absent (`view`: dL/dviewmatrix, or its per-block partial sums)
+_Grads = namedtuple("_Grads", "means3D scales rotations opacities shs colors view means2D shs_high raw cov3D",
+                    defaults=(None,) * 3)
+_SAVED = _Inputs._fields + _State._fields + ("cov3D", "near")    # save_for_backward's order, both autograd functions
+
+
+def _saved(ctx):
+    """ctx.saved_tensors by name: (dict, _Inputs, _State)."""
+    t = dict(zip(_SAVED, ctx.saved_tensors))
+    return t, _Inputs(*map(t.get, _Inputs._fields)), _State(*map(t.get, _State._fields))
+
+
+def _input_grads(args: tuple, g: _Grads, **other) -> tuple:
+    """backward's result, one slot per name in `args` (forward's inputs): `other`'s gradient, else `g`'s, else None."""
+    named = {**g._asdict(), **other}
+    return tuple(named.get(a) for a in args)
+
+
+def _sh_coefficients(shs, sh_layout: int, raw=None) -> int:
+    """SpfDims.K from the tensors of a call (raw rows: 7 + 3K channels; band split: 16 + 9 = 25; colours: 0)."""
+    if raw is not None:
+        return (raw.shape[-1] - 7) // 3
+    if shs is None:
+        return 0
+    return 25 if sh_layout == 2 else shs.shape[3 if sh_layout else 2]
+
+
+def _geometry(i: _Inputs, sh_degree, H, W, scale_modifier, sh_layout, sh_band4, max_pairs) -> _Geometry:
+    (S, G, _), V = i.means3D.shape, i.viewmatrix.shape[1]
+    return _Geometry(S, V, G, _sh_coefficients(i.shs, sh_layout, i.raw), sh_degree, H, W, float(scale_modifier),
+                     int(sh_layout), bool(sh_band4), _plan_mode(max_pairs))
+
+
+def _dims(g: _Geometry, bin_cap: int, rec_cap: int, raw=None, adapter_eps: float = 0.0):
+    return _lib.SpfDims(g.S, g.V, g.G, g.K, g.sh_degree, g.H, g.W, g.scale_modifier, g.sh_layout, int(g.sh_band4),
+                        int(bin_cap), int(rec_cap) if bin_cap else 0, 0 if raw is None else raw.stride(0), float(adapter_eps))
+
+
+def _inputs_struct(inputs: _Inputs):
+    return _lib.SpfInputs(*map(_ptr, inputs))
+
+
 @_on_device_of_first_arg
 def _forward_impl(means3D, scales, rotations, opacities, shs, colors, viewmatrix, projmatrix, tanfov, bg,
                   view_scale, H, W, sh_degree, scale_modifier, max_pairs, sh_layout=0, camera=None, sh_band4=False,
                   record=None, nothing_needs_grad=False, view64=None, shs_high=None, raw=None, sh_mask=None,
-                  adapter_eps=0.0, cov3D=None):
-    """Launch the forward chain.  Returns (outputs, saved state tensors).  `camera` (an SpfCamera whose outputs are
-    viewmatrix / projmatrix / tanfov / view_scale): the decoder fast path -- camera set-up and the clearing of the tile
-    counters are one kernel.  `cov3D` [S,G,6] (scales / rotations None): precomputed covariances, through the ctypes
-    path always (the compiled binding does not take them)."""
+                  adapter_eps=0.0, cov3D=None) -> _Forward:
+    """Launch the forward chain.  `camera` (an SpfCamera whose outputs are viewmatrix / projmatrix / tanfov / view_scale):
+    the decoder fast path -- camera set-up and the clearing of the tile counters are one kernel.  `cov3D` [S,G,6] (scales /
+    rotations None): precomputed covariances, through the ctypes path always (the compiled binding does not take them)."""
     lib = _lib.load()
-    S, G, _ = means3D.shape
-    V = viewmatrix.shape[1]
-    R = S * V
-    dev = means3D.device
+    inputs = _Inputs(means3D, scales, rotations, opacities, shs, colors, viewmatrix, projmatrix, tanfov, bg, view_scale,
+                     view64, shs_high, raw, sh_mask)
+    geom = _geometry(inputs, sh_degree, H, W, scale_modifier, sh_layout, sh_band4, max_pairs)
+    S, V, G, R, dev = geom.S, geom.V, geom.G, geom.S * geom.V, means3D.device
     rec_out = _last if record is None else record
+    T, nblk = lib.spf_raster_num_tiles(H, W), lib.spf_raster_view_partial_blocks(G)
     fast = _lib.fast() if (camera is None and cov3D is None) else None
     if fast is not None:
         # the same chain through the compiled binding (csrc/torch_binding.cpp): allocation, structs, launches and the
         # exact-mode read-back in C++ -- what a per-view caller of the drop-in surface pays b*v times per step
-        if max_pairs is None:
-            capacity, max_tile, dense = -1, 0, 0
-        else:
-            capacity, max_tile, dense = _plan_numbers(max_pairs, R * lib.spf_raster_num_tiles(H, W))
+        capacity, max_tile, dense = (-1, 0, 0) if max_pairs is None else _plan_numbers(max_pairs, R * T)
         with _spf_errors():
             ts, (D, max_tile, dense, RT) = fast.raster_forward(
                 means3D, scales, rotations, opacities, shs, colors, viewmatrix, projmatrix, tanfov, bg, view_scale,
                 view64, H, W, sh_degree, float(scale_modifier), int(sh_layout), bool(sh_band4), capacity, max_tile, dense)
         image, depth, alpha, radii_v, rec, rect, tiles, pairs, pair_idx, final_T, n_contrib = ts
-        counters = tiles[4 * RT + 1:4 * RT + 5]
+        lay = _layout(RT, R * G, R * nblk)
+        counters = tiles[lay.counters:lay.pair_cursor]
         if max_pairs is None:
             rec_out.update(num_pairs=D, max_tile_list=max_tile, dense_tiles=dense, tiles=RT, counters=None)
             if rec_out is not _last:
@@ -295,31 +393,25 @@ def _forward_impl(means3D, scales, rotations, opacities, shs, colors, viewmatrix
             rec_out["counters"] = counters
             _last["counters"] = counters
             early = isinstance(max_pairs, PairBudget) and max_pairs.check == "early"
-            if ((_plan_mode(max_pairs) == 1 and nothing_needs_grad) or early) and not torch.cuda.is_current_stream_capturing():
+            if ((geom.plan_mode == 1 and nothing_needs_grad) or early) and not torch.cuda.is_current_stream_capturing():
                 _raise_if_plan_failed(counters, pairs.numel())
-        return ((image, depth, alpha, radii_v),
-                (rec, radii_v.view(-1), rect, tiles, pairs, pair_idx, final_T, n_contrib), (dense, 0, pairs.numel()))
-    K = 0 if shs is None else (25 if sh_layout == 2 else shs.shape[3 if sh_layout else 2])
-    if raw is not None:                      # raw rows [S*G, 7 + 3K] (sh_layout 3): the adapter fused into the projection kernels
-        K = (raw.shape[1] - 7) // 3
-    T = lib.spf_raster_num_tiles(H, W)
-    P = H * W
+        return _Forward((image, depth, alpha, radii_v),
+                        _State(rec, radii_v.view(-1), rect, tiles, pairs, pair_idx, final_T, n_contrib),
+                        _Plan(dense, 0, pairs.numel()))
     # DIRECT BINS (planned calls): every tile owns a fixed bin of `bin_cap` keys that the projection kernel fills itself
     # -- no tile scan, no binning pass (SpfDims.bin_cap).  The bin size is the plan's list-length class.
     bin_cap = _direct_bin_cap(max_pairs, R * T, T)
     # gradient records the backward will allocate: the plan's capacity -- with headroom when the pair numbering is
     # sharded (each of 8 shards owns an eighth: see _record_capacity)
     rec_cap = _record_capacity(_plan_numbers(max_pairs, R * T)[0], S, G) if bin_cap else 0
-    dims = _lib.SpfDims(S, V, G, K, sh_degree, H, W, float(scale_modifier), int(sh_layout), int(bool(sh_band4)),
-                        bin_cap, rec_cap, 0 if raw is None else raw.stride(0), float(adapter_eps))
-    nblk = lib.spf_raster_view_partial_blocks(G)
-    rec, radii, rect, pair_idx, tiles, final_T, n_contrib, image, depth, alpha, _ = _alloc_forward(dev, S, V, G, H, W, T, nblk)
-    counters = tiles[4 * R * T + 1:4 * R * T + 5]
-
-    inp = _lib.SpfInputs(_ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(shs),
-                         _ptr(colors), _ptr(viewmatrix), _ptr(projmatrix), _ptr(tanfov), _ptr(bg),
-                         _ptr(view_scale), _ptr(view64), _ptr(shs_high), _ptr(raw), _ptr(sh_mask))
-    pairs = torch.empty((R * T * bin_cap,), dtype=torch.int64, device=dev) if bin_cap else None
+    dims = _dims(geom, bin_cap, rec_cap, raw, adapter_eps)
+    state, lay = _alloc_state(dev, R, G, T, nblk, H * W)
+    image, depth, alpha = _alloc_outputs(dev, S, V, H, W)
+    views = _slice_state(lay, state.rect, state.tiles, state.pair_idx)
+    tiles, counters = state.tiles, views.counters
+    inp = _inputs_struct(inputs)
+    if bin_cap:
+        state = state._replace(pairs=torch.empty((R * T * bin_cap,), dtype=torch.int64, device=dev))
     # check="early" with direct bins: the projection kernel mirrors a raised plan flag into a pinned word the host reads
     # behind an event -- no device->host copy on the stream (SpfState.verdict_host)
     early = None
@@ -329,31 +421,24 @@ def _forward_impl(means3D, scales, rotations, opacities, shs, colors, viewmatrix
     # (a caller that captures the call in a graph hands its own pinned word over in the call record: the decoder's
     #  evaluation graphs read it behind a stream synchronisation instead of copying counters[2] back)
     vh = early[0] if early is not None else rec_out.get("verdict_host")
-    st = _state_struct(rec, radii, rect, tiles, pairs, pair_idx, final_T, n_contrib, R * T, R * G, R * nblk,
-                       verdict_host=vh if bin_cap else None)
+    st = _state_struct(state, views, verdict_host=vh if bin_cap else None)
     rec_out["verdict_mirrored"] = bool(bin_cap and vh is not None)
     stream = _stream_ptr(dev)
+    # camera set-up, with the clearing of ALL the tile bookkeeping in the same kernel where the buffer's alignment allows
+    # it (the scan then needs no single-block pass: see spf_tile_scan_render_kernel); then the projection
+    cleared = 0
+    if camera is not None and tiles.data_ptr() % 16 == 0:
+        cleared = 4 * tiles.numel()
+        _lib.check(lib.spf_decoder_prepare(C.byref(camera), _ptr(tiles), cleared, stream), "spf_decoder_prepare")
+    elif camera is not None:
+        _lib.check(lib.spf_camera_forward(C.byref(camera), stream), "spf_camera_forward")
     if cov3D is not None:
-        cleared = 0
-        if camera is not None and tiles.data_ptr() % 16 == 0:
-            _lib.check(lib.spf_decoder_prepare(C.byref(camera), _ptr(tiles), 4 * tiles.numel(), stream),
-                       "spf_decoder_prepare")
-            cleared = 4 * tiles.numel()
-        elif camera is not None:
-            _lib.check(lib.spf_camera_forward(C.byref(camera), stream), "spf_camera_forward")
         _lib.check(lib.spf_raster_forward_project_cov3d(C.byref(dims), C.byref(inp), _ptr(cov3D), C.byref(st), cleared,
                                                         stream), "spf_raster_forward_project_cov3d")
-    elif camera is not None and tiles.data_ptr() % 16 == 0:
-        # camera set-up and the clearing of ALL the tile bookkeeping in one kernel (the scan then needs no single-block
-        # pass: see spf_tile_scan_render_kernel)
-        _lib.check(lib.spf_decoder_prepare(C.byref(camera), _ptr(tiles), 4 * tiles.numel(), stream),
-                   "spf_decoder_prepare")
-        _lib.check(lib.spf_raster_forward_project_prepared(C.byref(dims), C.byref(inp), C.byref(st),
-                                                           4 * tiles.numel(), stream),
+    elif cleared:
+        _lib.check(lib.spf_raster_forward_project_prepared(C.byref(dims), C.byref(inp), C.byref(st), cleared, stream),
                    "spf_raster_forward_project_prepared")
     else:
-        if camera is not None:
-            _lib.check(lib.spf_camera_forward(C.byref(camera), stream), "spf_camera_forward")
         _lib.check(lib.spf_raster_forward_project(C.byref(dims), C.byref(inp), C.byref(st), stream),
                    "spf_raster_forward_project")
     if max_pairs is None:
@@ -375,8 +460,8 @@ def _forward_impl(means3D, scales, rotations, opacities, shs, colors, viewmatrix
     if early is not None and bin_cap:      # direct bins: the projection kernel has binned -- the verdict is final behind it
         early[1].record()
     if not bin_cap:
-        pairs = torch.empty((max(capacity, 1),), dtype=torch.int64, device=dev)
-        st.pairs = _ptr(pairs)
+        state = state._replace(pairs=torch.empty((max(capacity, 1),), dtype=torch.int64, device=dev))
+        st.pairs = _ptr(state.pairs)
     out = _lib.SpfOutputs(_ptr(image), _ptr(depth), _ptr(alpha))
     _lib.check(lib.spf_raster_forward_render(C.byref(dims), C.byref(inp), C.byref(st), C.byref(out),
                                              capacity, max_tile, dense, stream),
@@ -388,37 +473,38 @@ def _forward_impl(means3D, scales, rotations, opacities, shs, colors, viewmatrix
         else:
             failed = True                            # classic chain: the binning kernel decides -- read it the slow way
         if failed:
-            _raise_if_plan_failed(tiles[4 * R * T + 1:], capacity, rec_out.get("plan"))
-    if max_pairs is not None and _plan_mode(max_pairs) == 1 and nothing_needs_grad \
-            and not torch.cuda.is_current_stream_capturing():
+            _raise_if_plan_failed(tiles[lay.counters:], capacity, rec_out.get("plan"))
+    if geom.plan_mode == 1 and nothing_needs_grad and not torch.cuda.is_current_stream_capturing():
         # check="backward" promises that a failed plan raises -- but no backward will come (evaluation under
         # no_grad, or nothing requires grad): verify now (one host sync; eval loops should use exact mode anyway)
-        _raise_if_plan_failed(tiles[4 * R * T + 1:], capacity, rec_out.get("plan"))
-    return ((image, depth, alpha, radii.view(S, V, G)),
-            (rec, radii, rect, tiles, pairs, pair_idx, final_T, n_contrib), (dense, bin_cap, max(int(capacity), 1)))
+        _raise_if_plan_failed(tiles[lay.counters:], capacity, rec_out.get("plan"))
+    return _Forward((image, depth, alpha, state.radii.view(S, V, G)), state, _Plan(dense, bin_cap, max(int(capacity), 1)))
 
 
-def _alloc_forward(dev, S: int, V: int, G: int, H: int, W: int, T: int, nblk: int):
-    """Everything a forward call writes besides the pair lists: (rec, radii, rect, pair_idx, tiles, final_T, n_contrib,
-    image, depth, alpha, the flat colour | depth allocation)."""
-    R, P = S * V, H * W
-    i32 = dict(dtype=torch.int32, device=dev)
+def _alloc_state(dev, R: int, G: int, T: int, nblk: int, P: int):
+    """What a forward keeps for its backward, sized by the library: (_State with `pairs` None, its SpfStateLayout)."""
+    lay = _layout(R * T, R * G, R * nblk)
+    i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+    rec, radii = torch.empty((R * G, _REC), **f32), torch.empty((R * G,), **i32)
+    rect, pair_idx = torch.empty((lay.rect_words,), **i32), torch.empty((lay.pair_idx_words,), **i32)
+    tiles = torch.empty((lay.tiles_words,), **i32)
+    return _State(rec, radii, rect, tiles, None, pair_idx, torch.empty((R * P,), **f32), torch.empty((R * P,), **i32)), lay
+
+
+def _alloc_camera(dev, S: int, V: int, scale_invariant: bool = True):
+    """What the camera kernel writes: (viewmatrix, projmatrix [S,V,4,4], tanfov [S,V,2], view_scale [S,V] or None, the pose
+    once more in float64 with the world scale folded in -- SpfInputs.viewmatrix64: the view-space position comes from it)."""
     f32 = dict(dtype=torch.float32, device=dev)
-    rec = torch.empty((R * G, _REC), **f32)
-    radii = torch.empty((R * G,), **i32)
-    rect = torch.empty((2 * R * G + (R * G + 3) // 4,), **i32)   # packed tile rect | depth key (float bits) | SH clamp masks (bytes)
-    pair_idx = torch.empty((2 * R * G + 2 * R * nblk,), **i32)   # pair_off (rect, first pair) | blk_total | blk_base
-    # tile_count | tile_flags | tile_start (+1) | tile_fill | counters (4) | pair cursors (8) | padding to 16 bytes
-    tiles = torch.empty((4 * R * T + 16,), **i32)
-    final_T = torch.empty((R * P,), **f32)
-    n_contrib = torch.empty((R * P,), **i32)
-    # colour and depth in ONE allocation, colour first (two contiguous tensors as ever: the decoder module's captured
-    # evaluation graphs copy both out with a single clone)
-    img_dep = torch.empty((R * 4 * P,), **f32)
-    image = img_dep[:R * 3 * P].view(S, V, 3, H, W)
-    depth = img_dep[R * 3 * P:].view(S, V, 1, H, W)
-    alpha = torch.empty((S, V, 1, H, W), **f32)
-    return rec, radii, rect, pair_idx, tiles, final_T, n_contrib, image, depth, alpha, img_dep
+    return (torch.empty((S, V, 4, 4), **f32), torch.empty((S, V, 4, 4), **f32), torch.empty((S, V, 2), **f32),
+            torch.empty((S, V), **f32) if scale_invariant else None, torch.empty((S, V, 4, 4), dtype=torch.float64, device=dev))
+
+
+def _alloc_outputs(dev, S: int, V: int, H: int, W: int):
+    """(image [S,V,3,H,W], depth [S,V,1,H,W], alpha [S,V,1,H,W]); colour and depth are two views of ONE allocation,
+    colour first (the decoder module's captured evaluation graphs copy both out with a single clone)."""
+    n, f32 = S * V * H * W, dict(dtype=torch.float32, device=dev)
+    img_dep = torch.empty((4 * n,), **f32)
+    return img_dep[:3 * n].view(S, V, 3, H, W), img_dep[3 * n:].view(S, V, 1, H, W), torch.empty((S, V, 1, H, W), **f32)
 
 
 def _direct_bin_cap(max_pairs, RT: int, T: int) -> int:
@@ -476,7 +562,7 @@ class _spf_errors:
 
 class StateViews(NamedTuple):
     """The fields of SpfState that share a buffer, as named views of the three tensors a forward call returns them in
-    (`rect`, `tiles`, `pair_idx`): the ONE place that knows where each field starts."""
+    (`rect`, `tiles`, `pair_idx`).  Where each field starts is the library's word (spf_raster_state_layout)."""
     rect: Tensor                    # [RG]      packed tile rect
     zkey: Tensor                    # [RG...]   depth key (float bits), then the SH clamp bytes
     sh_clamp: Optional[Tensor]      # [..]      SH clamp masks (None: the buffer holds none)
@@ -485,34 +571,41 @@ class StateViews(NamedTuple):
     tile_start: Tensor              # [RT + 1]  (direct bins, >= 2,048 tiles: the launch order [RT][2] starts here)
     tile_fill: Tensor               # [RT]
     counters: Tensor                # [4]
-    pair_cursor: Optional[Tensor]   # [8]       (None: the compiled binding's buffer has none)
+    pair_cursor: Optional[Tensor]   # [8]       (None: the buffer is too short to hold them)
     pair_off: Tensor                # [2 RG]    (rect, first pair) per (render, Gaussian)
     blk_total: Tensor               # [RB]
     blk_base: Tensor                # [RB...]
 
 
-def _state_views(rect, tiles, pair_idx, RT: int, RG: int, RB: int) -> StateViews:
-    """Slice `rect` (packed rect | depth key | SH clamp bytes), `tiles` (tile_count | tile_flags | tile_start (+1) |
-    tile_fill | counters (4) [| pair cursors (8) | padding]) and `pair_idx` (pair_off | blk_total | blk_base) into their
-    fields.  Pure indexing: works on device tensors and on host copies alike (the tests audit host copies with it)."""
+def _layout(RT: int, RG: int, RB: int):
+    lay = _lib.SpfStateLayout()
+    _lib.check(_lib.load().spf_raster_state_layout(RT, RG, RB, C.byref(lay)), "spf_raster_state_layout")
+    return lay
+
+
+def _slice_state(lay, rect, tiles, pair_idx) -> StateViews:
     return StateViews(
-        rect=rect[:RG], zkey=rect[RG:], sh_clamp=rect[2 * RG:] if rect.numel() > 2 * RG else None,
-        tile_count=tiles[:RT], tile_flags=tiles[RT:2 * RT], tile_start=tiles[2 * RT:3 * RT + 1],
-        tile_fill=tiles[3 * RT + 1:4 * RT + 1], counters=tiles[4 * RT + 1:4 * RT + 5],
-        pair_cursor=tiles[4 * RT + 5:4 * RT + 13] if tiles.numel() >= 4 * RT + 13 else None,
-        pair_off=pair_idx[:2 * RG], blk_total=pair_idx[2 * RG:2 * RG + RB], blk_base=pair_idx[2 * RG + RB:])
+        rect=rect[:lay.zkey], zkey=rect[lay.zkey:], sh_clamp=rect[lay.sh_clamp:] if rect.numel() > lay.sh_clamp else None,
+        tile_count=tiles[:lay.tile_flags], tile_flags=tiles[lay.tile_flags:lay.tile_start],
+        tile_start=tiles[lay.tile_start:lay.tile_fill], tile_fill=tiles[lay.tile_fill:lay.counters],
+        counters=tiles[lay.counters:lay.pair_cursor],
+        pair_cursor=tiles[lay.pair_cursor:lay.pair_cursor + 8] if tiles.numel() >= lay.pair_cursor + 8 else None,
+        pair_off=pair_idx[:lay.blk_total], blk_total=pair_idx[lay.blk_total:lay.blk_base], blk_base=pair_idx[lay.blk_base:])
 
 
-def _state_struct(rec, radii, rect, tiles, pairs, pair_idx, final_T, n_contrib, RT, RG, RB, verdict_host=None):
-    v = _state_views(rect, tiles, pair_idx, RT, RG, RB)
-    return _lib.SpfState(_ptr(rec), _ptr(radii), _ptr(v.rect), _ptr(v.zkey), _ptr(v.tile_count), _ptr(v.tile_start),
-                         _ptr(v.tile_fill), _ptr(v.tile_flags), _ptr(v.counters), _ptr(pairs),
-                         _ptr(v.pair_off), _ptr(v.blk_total), _ptr(v.blk_base),
-                         _ptr(final_T), _ptr(n_contrib), _ptr(v.pair_cursor), _ptr(v.sh_clamp), _ptr(verdict_host))
+def _state_views(rect, tiles, pair_idx, RT: int, RG: int, RB: int) -> StateViews:
+    """Slice the three shared state buffers into their fields, at the library's offsets (SpfStateLayout).  Pure indexing:
+    works on device tensors and on host copies alike (the tests audit host copies with it)."""
+    return _slice_state(_layout(RT, RG, RB), rect, tiles, pair_idx)
+
+
+def _state_struct(state: _State, v: StateViews, verdict_host=None):
+    named = {**state._asdict(), **v._asdict(), "verdict_host": verdict_host}     # (SpfState.rect: the view, not the buffer)
+    return _lib.SpfState(*(_ptr(named[f]) for f, _ in _lib.SpfState._fields_))
 
 
 def _raise_if_plan_failed(counters: Tensor, capacity: int, plan=None) -> None:
-    """`plan` = (bin_cap, record capacity, shards) of a direct-bins call (its counters[0] / [1] are not maintained: the
+    """`counters`: the tiles buffer from its counters on (the pair cursors too, where it holds them).  `plan` = (bin_cap, record capacity, shards) of a direct-bins call (its counters[0] / [1] are not maintained: the
     message then names what the device actually checked), None for the classic chain."""
     host = counters.cpu()
     flag = int(host[2])
@@ -541,25 +634,24 @@ def _plan_mode(max_pairs) -> int:
 
 
 @_on_device_of_first_arg
-def _backward_impl(inputs, state, geom, grads_out, want, shs_high=None, raw=None, sh_mask=None, adapter_eps=0.0,
-                   cov3D=None):
-    """Launch the backward chain.  `want`: dict of booleans (scales_rot, shs, colors, view, means2D[, cov]).  `shs_high`:
-    the band-4 plane of the band-split harmonics (sh_layout 2); its gradient is appended to the result -- None unless band 4
-    was evaluated (a degree-3 evaluation neither reads the plane nor writes its gradient).  `raw` [S*G, 7+3K] (sh_layout
-    3): scales / rotations / shs are None and the result carries dL/draw [S*G, 7+3K] as its LAST element.  `cov3D`
-    [S,G,6]: precomputed covariances (scales / rotations None); the result carries dL/dcov3D [S,G,6] (None unless
-    want["cov"]) as its LAST element."""
+def _backward_impl(i: _Inputs, state: _State, geom: _Geometry, plan: _Plan, grads_out, want, adapter_eps=0.0,
+                   cov3D=None) -> _Grads:
+    """Launch the backward chain.  `want`: dict of booleans (scales_rot, shs, colors, view, means2D[, cov]).  Band-split
+    harmonics (i.shs_high): the band-4 plane's gradient is None unless band 4 was evaluated (a degree-3 evaluation
+    neither reads the plane nor writes its gradient); raw rows (i.raw [S*G, 7+3K]; scales / rotations / shs None):
+    dL/draw [S*G, 7+3K]; `cov3D` [S,G,6] (scales / rotations None): dL/dcov3D [S,G,6] when want["cov"]."""
     lib = _lib.load()
-    means3D, scales, rotations, opacities, shs, colors, viewmatrix, projmatrix, tanfov, bg, view_scale, view64 = inputs
-    rec, radii, rect, tiles, pairs, pair_idx, final_T, n_contrib = state
-    S, V, G, K, sh_degree, H, W, scale_modifier, capacity_mode, (dense, bin_cap, capacity), sh_layout, sh_band4 = geom
-    R = S * V
-    dev = means3D.device
-    T = lib.spf_raster_num_tiles(H, W)
+    means3D, scales, rotations, opacities, shs, colors = i.means3D, i.scales, i.rotations, i.opacities, i.shs, i.colors
+    shs_high, raw = i.shs_high, i.raw
+    S, V, G, H, W = geom.S, geom.V, geom.G, geom.H, geom.W
+    dense, bin_cap, capacity = plan
+    R, dev = S * V, means3D.device
+    nblk = lib.spf_raster_view_partial_blocks(G)
+    lay = _layout(R * lib.spf_raster_num_tiles(H, W), R * G, R * nblk)
     # (a device->host read is illegal while a HIP graph is being captured: graph users check the flag themselves
     # with `pair_buffer_overflowed` after a replay)
-    if capacity_mode == 1 and not torch.cuda.is_current_stream_capturing():
-        _raise_if_plan_failed(tiles[4 * R * T + 1:], capacity,
+    if geom.plan_mode == 1 and not torch.cuda.is_current_stream_capturing():
+        _raise_if_plan_failed(state.tiles[lay.counters:], capacity,
                               (bin_cap, capacity, lib.spf_raster_pair_shards(S, G)) if bin_cap else None)
     from .shard import active_bucket
     bucket = active_bucket()
@@ -571,19 +663,15 @@ def _backward_impl(inputs, state, geom, grads_out, want, shs_high=None, raw=None
     if fast is not None:
         wv = want["view"]
         with _spf_errors():
-            out = fast.raster_backward(
-                means3D, scales, rotations, opacities, shs, colors, viewmatrix, projmatrix, tanfov, bg, view_scale,
-                view64, rec, radii, rect, tiles, pairs, pair_idx, final_T, n_contrib, H, W, sh_degree,
-                float(scale_modifier), int(sh_layout), bool(sh_band4), int(dense), int(bin_cap), int(capacity),
-                grads_out[0], grads_out[1],
-                grads_out[2], bool(want["scales_rot"]), bool(want["shs"]), bool(want["colors"]),
-                2 if wv == "partials" else (1 if wv else 0), bool(want["means2D"]))
-        return tuple(out)
-    dims = _lib.SpfDims(S, V, G, K, sh_degree, H, W, scale_modifier, int(sh_layout), int(sh_band4), int(bin_cap),
-                        int(capacity) if bin_cap else 0, 0 if raw is None else raw.stride(0), float(adapter_eps))
+            return _Grads(*fast.raster_backward(
+                means3D, scales, rotations, opacities, shs, colors, i.viewmatrix, i.projmatrix, i.tanfov, i.bg, i.view_scale,
+                i.viewmatrix64, *state, H, W, geom.sh_degree, geom.scale_modifier, geom.sh_layout, geom.sh_band4,
+                int(dense), int(bin_cap), int(capacity), grads_out[0], grads_out[1], grads_out[2],
+                bool(want["scales_rot"]), bool(want["shs"]), bool(want["colors"]),
+                2 if wv == "partials" else (1 if wv else 0), bool(want["means2D"])))
+    dims = _dims(geom, bin_cap, capacity, raw, adapter_eps)
     f32 = dict(dtype=torch.float32, device=dev)
     g_image, g_depth, g_alpha = (None if g is None else g.contiguous().float() for g in grads_out)
-    nblk = lib.spf_raster_view_partial_blocks(G)
     gpair = torch.empty((capacity, 10), **f32)     # packed gradient records: 9 (+1 with a depth gradient) floats
     def out(name, like):          # a view of the caller's flat gradient bucket (shard.GradBucket) or a fresh buffer
         v = bucket.take(name, like) if bucket is not None else None
@@ -596,18 +684,16 @@ def _backward_impl(inputs, state, geom, grads_out, want, shs_high=None, raw=None
     d_cov = torch.empty_like(cov3D) if (cov3D is not None and want.get("cov")) else None
     d_shs = out("harmonics", shs) if (shs is not None and want["shs"]) else None
     d_shs_high = None
-    if d_shs is not None and sh_layout == 2 and sh_band4 and sh_degree == 4:
+    if d_shs is not None and geom.sh_layout == 2 and geom.sh_band4 and geom.sh_degree == 4:
         d_shs_high = out("harmonics_band4", shs_high)
     d_col = torch.empty_like(colors) if (colors is not None and want["colors"]) else None
     # want["view"] == "partials": leave the viewmatrix gradient as per-block partial sums (the decoder chains them to
     # the poses in one kernel, spf_camera_backward_partials); returned in place of d_view
-    d_view = torch.empty_like(viewmatrix) if want["view"] is True else None
+    d_view = torch.empty_like(i.viewmatrix) if want["view"] is True else None
     vpartial = torch.empty((R, nblk, 12), **f32) if want["view"] else None
     d_m2d = torch.zeros((R, G, 3), **f32) if want["means2D"] else None
-    inp = _lib.SpfInputs(_ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(shs),
-                         _ptr(colors), _ptr(viewmatrix), _ptr(projmatrix), _ptr(tanfov), _ptr(bg),
-                         _ptr(view_scale), _ptr(view64), _ptr(shs_high), _ptr(raw), _ptr(sh_mask))
-    st = _state_struct(rec, radii, rect, tiles, pairs, pair_idx, final_T, n_contrib, R * T, R * G, R * nblk)
+    inp = _inputs_struct(i)
+    st = _state_struct(state, _slice_state(lay, state.rect, state.tiles, state.pair_idx))
     gr = _lib.SpfGrads(_ptr(g_image), _ptr(g_depth), _ptr(g_alpha), _ptr(gpair), _ptr(vpartial),
                        _ptr(d_means), _ptr(d_scales), _ptr(d_rot), _ptr(d_opac), _ptr(d_shs), _ptr(d_col),
                        _ptr(d_view), _ptr(d_m2d), _ptr(d_shs_high), _ptr(d_raw))
@@ -618,12 +704,8 @@ def _backward_impl(inputs, state, geom, grads_out, want, shs_high=None, raw=None
     else:
         _lib.check(lib.spf_raster_backward(C.byref(dims), C.byref(inp), C.byref(st), C.byref(gr), capacity, dense,
                                            _stream_ptr(dev)), "spf_raster_backward")
-    res = (d_means, d_scales, d_rot, d_opac, d_shs, d_col, (vpartial if want["view"] == "partials" else d_view), d_m2d)
-    if cov3D is not None:
-        return res + (d_cov,)
-    if raw is not None:
-        return res + (d_raw,)
-    return res if shs_high is None else res + (d_shs_high,)
+    return _Grads(d_means, d_scales, d_rot, d_opac, d_shs, d_col, vpartial if want["view"] == "partials" else d_view, d_m2d,
+                  d_shs_high, d_raw, d_cov)
 
 
 class _RasterizeBatch(torch.autograd.Function):
@@ -634,36 +716,31 @@ class _RasterizeBatch(torch.autograd.Function):
         # `grad_mode`: torch.is_grad_enabled() AT THE CALL SITE (inside Function.forward it is always False, and
         # ctx.needs_input_grad stays True under no_grad): a backward will come only if both say so
         ctx.set_materialize_grads(False)
-        outs, state, dense = _forward_impl(means3D, scales, rotations, opacities, shs, colors, viewmatrix,
-                                           projmatrix, tanfov, bg, view_scale, H, W, sh_degree, scale_modifier,
-                                           max_pairs, sh_band4=sh_band4, record=record,
-                                           nothing_needs_grad=not (grad_mode and any(ctx.needs_input_grad)),
-                                           cov3D=cov3D)
-        S, G, _ = means3D.shape
-        ctx.geom = (S, viewmatrix.shape[1], G, 0 if shs is None else shs.shape[2], sh_degree, H, W,
-                    float(scale_modifier), _plan_mode(max_pairs), dense, 0, bool(sh_band4))
+        fw = _forward_impl(means3D, scales, rotations, opacities, shs, colors, viewmatrix, projmatrix, tanfov, bg,
+                           view_scale, H, W, sh_degree, scale_modifier, max_pairs, sh_band4=sh_band4, record=record,
+                           nothing_needs_grad=not (grad_mode and any(ctx.needs_input_grad)), cov3D=cov3D)
+        inputs = _Inputs(means3D, scales, rotations, opacities, shs, colors, viewmatrix, projmatrix, tanfov, bg, view_scale)
+        ctx.geom, ctx.plan = _geometry(inputs, sh_degree, H, W, scale_modifier, 0, sh_band4, max_pairs), fw.plan
         ctx.flags = (bool(enable_cov_grad), bool(enable_sh_grad))
         ctx.means2D_shape = None if means2D is None else tuple(means2D.shape)
-        ctx.save_for_backward(means3D, scales, rotations, opacities, shs, colors, viewmatrix, projmatrix,
-                              tanfov, bg, view_scale, None, *state, cov3D)
-        ctx.mark_non_differentiable(outs[3])
-        return outs
+        ctx.save_for_backward(*inputs, *fw.state, cov3D)
+        ctx.mark_non_differentiable(fw.outs[3])
+        return fw.outs
+
+    ARGS = tuple(inspect.signature(forward.__func__).parameters)[1:]       # forward's inputs, in order
 
     @staticmethod
     def backward(ctx, g_image, g_depth, g_alpha, _g_radii):
-        saved = ctx.saved_tensors
-        need = ctx.needs_input_grad
+        t, inputs, state = _saved(ctx)
+        need = dict(zip(_RasterizeBatch.ARGS, ctx.needs_input_grad))
         enable_cov_grad, enable_sh_grad = ctx.flags
-        cov3D = saved[20]
-        want = dict(scales_rot=enable_cov_grad and (need[1] or need[2]), shs=enable_sh_grad and need[4],
-                    colors=need[5], view=need[6], means2D=ctx.means2D_shape is not None and need[17],
-                    cov=enable_cov_grad and len(need) > 22 and need[22])
-        d_means, d_scales, d_rot, d_opac, d_shs, d_col, d_view, d_m2d, *d_cov = _backward_impl(
-            saved[:12], saved[12:20], ctx.geom, (g_image, g_depth, g_alpha), want, cov3D=cov3D)
-        if d_m2d is not None:
-            d_m2d = d_m2d.view(ctx.means2D_shape)
-        return (d_means, d_scales, d_rot, d_opac, d_shs, d_col, d_view, None, None, None, None,
-                None, None, None, None, None, None, d_m2d, None, None, None, None, d_cov[0] if d_cov else None)
+        want = dict(scales_rot=enable_cov_grad and (need["scales"] or need["rotations"]),
+                    shs=enable_sh_grad and need["shs"], colors=need["colors"], view=need["viewmatrix"],
+                    means2D=ctx.means2D_shape is not None and need["means2D"],
+                    cov=enable_cov_grad and need.get("cov3D", False))
+        g = _backward_impl(inputs, state, ctx.geom, ctx.plan, (g_image, g_depth, g_alpha), want, cov3D=t["cov3D"])
+        return _input_grads(_RasterizeBatch.ARGS, g, viewmatrix=g.view,
+                            means2D=None if g.means2D is None else g.means2D.view(ctx.means2D_shape))
 
 
 class _DecoderRender(torch.autograd.Function):
@@ -675,17 +752,8 @@ class _DecoderRender(torch.autograd.Function):
                 H, W, sh_degree, scale_invariant, enable_cov_grad, enable_sh_grad, max_pairs, sh_layout, sh_band4,
                 record, grad_mode, shs_high=None, raw=None, sh_mask=None, adapter_eps=0.0, cov3D=None):
         ctx.set_materialize_grads(False)
-        lib = _lib.load()
         S, V = extrinsics.shape[:2]
-        dev = means3D.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        view = torch.empty((S, V, 4, 4), **f32)
-        proj = torch.empty((S, V, 4, 4), **f32)
-        tanfov = torch.empty((S, V, 2), **f32)
-        vscale = torch.empty((S, V), **f32) if scale_invariant else None
-        # the pose once more in float64, world scale folded in: the projection kernels form the view-space position
-        # from it (SpfInputs.viewmatrix64)
-        view64 = torch.empty((S, V, 4, 4), dtype=torch.float64, device=dev)
+        view, proj, tanfov, vscale, view64 = _alloc_camera(means3D.device, S, V, scale_invariant)
         # raw rows (sh_layout 3): the caller's tensor, whatever its shape; its [S*G, 7+3K] rows are taken HERE, outside
         # autograd's view (an as_strided under autograd costs a zero fill and a scatter of the whole tensor in backward)
         rows = None
@@ -694,57 +762,44 @@ class _DecoderRender(torch.autograd.Function):
             ctx.raw_shape = tuple(raw.shape)
         cam = _lib.SpfCamera(_ptr(extrinsics), _ptr(intrinsics), _ptr(near), _ptr(far), _ptr(view), _ptr(proj),
                              _ptr(tanfov), _ptr(vscale), S * V, 1 if scale_invariant else 0, _ptr(view64))
-        outs, state, dense = _forward_impl(means3D, scales, rotations, opacities, shs, colors, view, proj, tanfov,
-                                           bg, vscale, H, W, sh_degree, 1.0, max_pairs, sh_layout, camera=cam,
-                                           sh_band4=sh_band4, record=record,
-                                           nothing_needs_grad=not (grad_mode and any(ctx.needs_input_grad)),
-                                           view64=view64, shs_high=shs_high, raw=rows, sh_mask=sh_mask,
-                                           adapter_eps=adapter_eps, cov3D=cov3D)
-        G = means3D.shape[1]
-        K = 0 if shs is None else (25 if sh_layout == 2 else shs.shape[3 if sh_layout else 2])
-        if rows is not None:
-            K = (rows.shape[1] - 7) // 3
+        fw = _forward_impl(means3D, scales, rotations, opacities, shs, colors, view, proj, tanfov, bg, vscale, H, W,
+                           sh_degree, 1.0, max_pairs, sh_layout, camera=cam, sh_band4=sh_band4, record=record,
+                           nothing_needs_grad=not (grad_mode and any(ctx.needs_input_grad)), view64=view64,
+                           shs_high=shs_high, raw=rows, sh_mask=sh_mask, adapter_eps=adapter_eps, cov3D=cov3D)
         ctx.adapter_eps = float(adapter_eps)
-        ctx.geom = (S, V, G, K, sh_degree, H, W, 1.0, _plan_mode(max_pairs), dense, int(sh_layout), bool(sh_band4))
+        inputs = _Inputs(means3D, scales, rotations, opacities, shs, colors, view, proj, tanfov, bg, vscale, view64,
+                         shs_high, rows, sh_mask)
+        ctx.geom, ctx.plan = _geometry(inputs, sh_degree, H, W, 1.0, sh_layout, sh_band4, max_pairs), fw.plan
         ctx.flags = (bool(enable_cov_grad), bool(enable_sh_grad), bool(scale_invariant))
-        ctx.save_for_backward(means3D, scales, rotations, opacities, shs, colors, view, proj, tanfov, bg, vscale,
-                              view64, *state, near, shs_high, rows, sh_mask, cov3D)
-        ctx.mark_non_differentiable(outs[3])
-        return outs
+        ctx.save_for_backward(*inputs, *fw.state, cov3D, near)
+        ctx.mark_non_differentiable(fw.outs[3])
+        return fw.outs
+
+    ARGS = tuple(inspect.signature(forward.__func__).parameters)[1:]
 
     @staticmethod
     def backward(ctx, g_image, g_depth, g_alpha, _g_radii):
-        lib = _lib.load()
-        saved = ctx.saved_tensors
-        need = ctx.needs_input_grad
+        t, inputs, state = _saved(ctx)
+        need = dict(zip(_DecoderRender.ARGS, ctx.needs_input_grad))
         enable_cov_grad, enable_sh_grad, scale_invariant = ctx.flags
-        want = dict(scales_rot=enable_cov_grad and (need[5] or need[6]), shs=enable_sh_grad and need[8],
-                    colors=need[9], view="partials" if need[0] else False, means2D=False,
-                    cov=enable_cov_grad and len(need) > 26 and need[26])
-        shs_high, rows, sh_mask, cov3D = saved[21], saved[22], saved[23], saved[24]
-        if rows is not None:
-            want = dict(want, scales_rot=True, shs=True)
-        d_means, d_scales, d_rot, d_opac, d_shs, d_col, vpartial, _, *d_high = _backward_impl(
-            saved[:12], saved[12:20], ctx.geom, (g_image, g_depth, g_alpha), want, shs_high=shs_high, raw=rows,
-            sh_mask=sh_mask, adapter_eps=ctx.adapter_eps, cov3D=cov3D)
-        d_raw = d_cov = None
-        if rows is not None:
-            d_raw, d_high = d_high[0].view(ctx.raw_shape), []
-        elif cov3D is not None:
-            d_cov, d_high = d_high[0], []
+        fused = inputs.raw is not None                     # (raw rows: the pair and the harmonics are inside dL/draw)
+        want = dict(scales_rot=fused or (enable_cov_grad and (need["scales"] or need["rotations"])),
+                    shs=fused or (enable_sh_grad and need["shs"]), colors=need["colors"],
+                    view="partials" if need["extrinsics"] else False, means2D=False,
+                    cov=enable_cov_grad and need.get("cov3D", False))
+        g = _backward_impl(inputs, state, ctx.geom, ctx.plan, (g_image, g_depth, g_alpha), want,
+                           adapter_eps=ctx.adapter_eps, cov3D=t["cov3D"])
         d_ext = None
-        if need[0]:
-            view, near = saved[6], saved[20]
+        if need["extrinsics"]:
+            view = inputs.viewmatrix
             d_ext = torch.empty_like(view)
-            cam = _lib.SpfCamera(None, None, _ptr(near), None, _ptr(view), None, None, None,
+            cam = _lib.SpfCamera(None, None, _ptr(t["near"]), None, _ptr(view), None, None, None,
                                  view.shape[0] * view.shape[1], 1 if scale_invariant else 0)
             with torch.cuda.device(view.device):
-                _lib.check(lib.spf_camera_backward_partials(C.byref(cam), _ptr(vpartial), vpartial.shape[1],
-                                                            _ptr(d_ext), _stream_ptr(view.device)),
+                _lib.check(_lib.load().spf_camera_backward_partials(C.byref(cam), _ptr(g.view), g.view.shape[1],
+                                                                    _ptr(d_ext), _stream_ptr(view.device)),
                            "spf_camera_backward_partials")
-        return (d_ext, None, None, None, d_means, d_scales, d_rot, d_opac, d_shs, d_col, None,
-                None, None, None, None, None, None, None, None, None, None, None, d_high[0] if d_high else None,
-                d_raw, None, None, d_cov)
+        return _input_grads(_DecoderRender.ARGS, g, extrinsics=d_ext, raw=None if g.raw is None else g.raw.view(ctx.raw_shape))
 
 
 class StaticStep:
@@ -778,39 +833,34 @@ class StaticStep:
         if not bin_cap:
             raise RuntimeError("StaticStep needs a plan that runs with direct bins")
         layout = 2 if shs_high is not None else 1
-        K = 25 if layout == 2 else shs.shape[3]
         rec_cap = _record_capacity(int(plan.capacity), S, G)
-        self.dims = _lib.SpfDims(S, V, G, K, sh_degree, H, W, 1.0, layout, int(bool(sh_band4)), bin_cap, rec_cap)
+        geom = _Geometry(S, V, G, _sh_coefficients(shs, layout), sh_degree, H, W, 1.0, layout, bool(sh_band4), _plan_mode(plan))
+        self.dims = _dims(geom, bin_cap, rec_cap)
         self.shape = (S, V, G, H, W)
         f32 = dict(dtype=torch.float32, device=dev)
         self.f32 = f32
-        self.view, self.proj = torch.empty((S, V, 4, 4), **f32), torch.empty((S, V, 4, 4), **f32)
-        self.tanfov = torch.empty((S, V, 2), **f32)
-        self.vscale = torch.empty((S, V), **f32) if scale_invariant else None
-        self.view64 = torch.empty((S, V, 4, 4), dtype=torch.float64, device=dev)
+        self.view, self.proj, self.tanfov, self.vscale, self.view64 = _alloc_camera(dev, S, V, scale_invariant)
         nblk = lib.spf_raster_view_partial_blocks(G)
-        (self.rec, self.radii, self.rect, self.pair_idx, self.tiles, self.final_T, self.n_contrib, _i, _d, _a,
-         _f) = _alloc_forward(dev, S, V, G, 1, 1, T, nblk)       # (state only: the H x W outputs are the calls' own)
-        self.final_T = torch.empty((R * H * W,), **f32)
-        self.n_contrib = torch.empty((R * H * W,), dtype=torch.int32, device=dev)
-        if self.tiles.data_ptr() % 16:
+        state, lay = _alloc_state(dev, R, G, T, nblk, H * W)     # (state only: the outputs are the calls' own)
+        if state.tiles.data_ptr() % 16:
             raise RuntimeError("StaticStep: the tile bookkeeping buffer is not 16-byte aligned")
-        self.pairs = torch.empty((R * T * bin_cap,), dtype=torch.int64, device=dev)
-        self.counters = self.tiles[4 * R * T + 1:4 * R * T + 5]
-        self.capacity, self.bin_cap, self.RT = rec_cap, bin_cap, R * T
+        self.state = state = state._replace(pairs=torch.empty((R * T * bin_cap,), dtype=torch.int64, device=dev))
+        self.tiles, self.radii = state.tiles, state.radii
+        views = _slice_state(lay, state.rect, state.tiles, state.pair_idx)
+        self.counters, self.plan_words = views.counters, state.tiles[lay.counters:]
+        self.capacity, self.bin_cap = rec_cap, bin_cap
         self.plan_info = (int(bin_cap), int(rec_cap), lib.spf_raster_pair_shards(S, G))
         self.bgx = _background(bg, S, V)
         self.scale_invariant = bool(scale_invariant)
         self.cam = _lib.SpfCamera(None, None, None, None, _ptr(self.view), _ptr(self.proj), _ptr(self.tanfov),
                                   _ptr(self.vscale), R, 1 if scale_invariant else 0, _ptr(self.view64))
-        self.inp = _lib.SpfInputs(None, None, None, None, None, None, _ptr(self.view), _ptr(self.proj), _ptr(self.tanfov),
-                                  _ptr(self.bgx), _ptr(self.vscale), _ptr(self.view64), None)
+        self.inp = _inputs_struct(_Inputs(None, None, None, None, None, None, self.view, self.proj, self.tanfov, self.bgx,
+                                          self.vscale, self.view64))
         self.cam_b = _lib.SpfCamera(None, None, None, None, _ptr(self.view), None, None, None, R,
                                     1 if scale_invariant else 0)
         self.verdict = torch.zeros(1, dtype=torch.int32, pin_memory=True)      # SpfState.verdict_host
         self.verdict_event = torch.cuda.Event()
-        self.st = _state_struct(self.rec, self.radii, self.rect, self.tiles, self.pairs, self.pair_idx, self.final_T,
-                                self.n_contrib, R * T, R * G, R * nblk, verdict_host=self.verdict)
+        self.st = _state_struct(state, views, verdict_host=self.verdict)
         self.out = _lib.SpfOutputs(None, None, None)
         self.max_tile = int(plan.max_tile_list)
         # ---- backward ----
@@ -829,9 +879,7 @@ class StaticStep:
         self.vpartial = torch.empty((R, nblk, 12), **f32) if want["view"] else None
         self.gr = _lib.SpfGrads(None, None, None, _ptr(self.gpair), _ptr(self.vpartial))
         self.nblk = nblk
-        self.nbytes = sum(t.numel() * t.element_size() for t in
-                          (self.rec, self.radii, self.rect, self.pair_idx, self.tiles, self.final_T, self.n_contrib,
-                           self.pairs, self.gpair) if t is not None)
+        self.nbytes = sum(t.numel() * t.element_size() for t in state + (self.gpair,) if t is not None)
         # the same step driven from the compiled binding when it has been built (csrc/torch_binding.cpp::PreparedStep takes
         # the structs over by value): bind / forward / backward are then one C++ call each
         mod = _lib.fast()
@@ -942,7 +990,7 @@ class StaticStep:
         return [g.get(name) for name in self.GRADS]
 
     def raise_if_failed(self) -> None:
-        _raise_if_plan_failed(self.tiles[4 * self.RT + 1:], self.capacity, self.plan_info)
+        _raise_if_plan_failed(self.plan_words, self.capacity, self.plan_info)
 
 
 def camera_forward(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, scale_invariant: bool = True):
@@ -950,15 +998,10 @@ def camera_forward(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Te
     projmatrix [S,V,4,4], tanfov [S,V,2], view_scale [S,V]) exactly as ``render_batch`` feeds the rasterizer."""
     lib = _lib.load()
     S, V = extrinsics.shape[:2]
-    extrinsics = _f32c(extrinsics.detach(), "extrinsics", (S, V, 4, 4))
-    intrinsics = _f32c(intrinsics, "intrinsics", (S, V, 3, 3))
-    near = _f32c(near, "near", (S, V))
-    far = _f32c(far, "far", (S, V))
-    f32 = dict(dtype=torch.float32, device=extrinsics.device)
-    view, proj = torch.empty((S, V, 4, 4), **f32), torch.empty((S, V, 4, 4), **f32)
-    tanfov, vscale = torch.empty((S, V, 2), **f32), torch.empty((S, V), **f32)
+    extrinsics, intrinsics, near, far = _check_camera(extrinsics.detach(), intrinsics, near, far, S, V)
+    view, proj, tanfov, vscale, view64 = _alloc_camera(extrinsics.device, S, V)
     cam = _lib.SpfCamera(_ptr(extrinsics), _ptr(intrinsics), _ptr(near), _ptr(far), _ptr(view), _ptr(proj),
-                         _ptr(tanfov), _ptr(vscale), S * V, 1 if scale_invariant else 0)
+                         _ptr(tanfov), _ptr(vscale), S * V, 1 if scale_invariant else 0, _ptr(view64))
     with torch.cuda.device(extrinsics.device):
         _lib.check(lib.spf_camera_forward(C.byref(cam), _stream_ptr(extrinsics.device)), "spf_camera_forward")
     return view, proj, tanfov, vscale
@@ -983,6 +1026,10 @@ def render_batch(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tens
     band 4 when ``sh_degree`` is 4 (None = ``sh_band4_default()``).  ``record``: a ``CallRecord`` that receives this
     call's statistics / plan counters.  ``cov3D`` ([S,G,6] or [S,G,3,3], with ``scales`` and ``rotations`` None):
     precomputed covariances, as in ``rasterize_batch`` (with ``scale_invariant`` render (s,v) sees ``Sigma * k^2``).
+    ``raw`` (RAW ROWS, SpfDims.sh_layout 3: [S,G,7+3K] -- any leading shape with S*G rows and unit stride along the channels,
+    e.g. a view of the encoder's 83-channel head output) is what UnifiedGaussianAdapter.forward takes (gaussian_adapter.py:
+    122-150), ``sh_mask`` [K] and ``adapter_eps`` the adapter's: the projection kernels apply its activations as they read a
+    row and chain the backward into dL/draw -- adapter -> decoder to float32 rounding, without the adapter's two passes.
     Returns image [S,V,3,H,W], depth [S,V,1,H,W] (rasterizer units), alpha [S,V,1,H,W], radii [S,V,G]."""
     if cov3D is not None:
         if scales is not None or rotations is not None:
@@ -990,88 +1037,26 @@ def render_batch(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tens
         if raw is not None or shs_high is not None:
             raise RuntimeError("precomputed covariances (cov3D) are not supported with raw rows or band-split harmonics "
                                "(shs_high)")
-    if raw is not None:
-        return _render_batch_raw(extrinsics, intrinsics, near, far, means3D, opacities, raw, sh_mask, adapter_eps, bg,
-                                 image_height, image_width, sh_degree, scale_invariant, max_pairs, sh_band4, record)
-    if (shs is None) == (colors_precomp is None):
+    fused = raw is not None
+    if not fused and (shs is None) == (colors_precomp is None):
         raise RuntimeError("provide exactly one of shs / colors_precomp")
     S, G, _ = means3D.shape
     V = extrinsics.shape[1]
-    extrinsics = _f32c(extrinsics, "extrinsics", (S, V, 4, 4))
-    intrinsics = _f32c(intrinsics, "intrinsics", (S, V, 3, 3))
-    near = _f32c(near, "near", (S, V))
-    far = _f32c(far, "far", (S, V))
-    means3D = _f32c(means3D, "means3D", (S, G, 3))
-    if cov3D is not None:
-        cov3D = _cov6(cov3D, S, G)
-    else:
-        scales = _f32c(scales, "scales", (S, G, 3))
-        rotations = _f32c(rotations, "rotations", (S, G, 4))
-    opacities = _f32c(opacities.reshape(S, G), "opacities", (S, G))
-    if sh_layout not in ("gk3", "g3k"):
-        raise RuntimeError(f"sh_layout must be 'gk3' or 'g3k', got {sh_layout!r}")
-    native = sh_layout == "g3k"
-    layout = 1 if native else 0
-    if sh_band4 is None:
-        sh_band4 = sh_band4_default()
-        _note_band4_not_evaluated(sh_degree, sh_band4)
-    if shs_high is not None:
-        if shs is None or not native:
-            raise RuntimeError("shs_high (band 4 of the band-split layout) goes with shs [S,G,3,16] and sh_layout='g3k'")
-        shs = _f32c(shs, "shs", (S, G, 3, 16))
-        shs_high = _f32c(shs_high, "shs_high", (S, G, 3, 9))
-        layout = 2
-    elif shs is not None:
-        K = shs.shape[3 if native else 2]
-        if K < (min(sh_degree, 4 if sh_band4 else 3) + 1) ** 2:
-            raise RuntimeError(f"shs holds {K} coefficients, too few for sh_degree {sh_degree}")
-        shs = _f32c(shs, "shs", (S, G, 3, K) if native else (S, G, K, 3))
-    else:
+    extrinsics, intrinsics, near, far = _check_camera(extrinsics, intrinsics, near, far, S, V)
+    if fused:          # (the rows carry the pair and the harmonics: whatever else was passed for them is not looked at)
+        scales = rotations = shs = colors_precomp = shs_high = None
+        sh_layout, enable_cov_grad, enable_sh_grad = "g3k", True, True
+    means3D, scales, rotations, opacities, cov3D = _check_gaussians(means3D, scales, rotations, opacities, cov3D, S, G,
+                                                                    pair=not fused)
+    shs, shs_high, sh_mask, _, layout, sh_band4 = _check_sh(S, G, sh_degree, sh_band4, shs, sh_layout, shs_high, raw, sh_mask)
+    if colors_precomp is not None:
         colors_precomp = _f32c(colors_precomp, "colors_precomp", (S, G, 3))
-    if not (0 <= sh_degree <= 4):
-        raise RuntimeError(f"sh_degree {sh_degree} outside 0..4")
     bg = _background(bg, S, V)
     return _DecoderRender.apply(extrinsics, intrinsics, near, far, means3D, scales, rotations, opacities, shs,
                                 colors_precomp, bg, int(image_height), int(image_width), int(sh_degree),
-                                bool(scale_invariant), enable_cov_grad, enable_sh_grad, max_pairs, layout,
-                                bool(sh_band4), record, torch.is_grad_enabled(), shs_high, None, None, 0.0, cov3D)
-
-
-def _render_batch_raw(extrinsics, intrinsics, near, far, means3D, opacities, raw, sh_mask, adapter_eps, bg, image_height,
-                      image_width, sh_degree, scale_invariant, max_pairs, sh_band4, record):
-    """render_batch on RAW ROWS (SpfDims.sh_layout 3): `raw` [S, G, 7+3K] -- any leading shape with S*G rows, unit stride
-    along the channels, e.g. a view of the encoder's 83-channel head output -- holds what UnifiedGaussianAdapter.forward
-    takes (gaussian_adapter.py:122-150); `sh_mask` [K] and `adapter_eps` are the adapter's.  The projection kernels
-    apply the adapter's activations as they read a row and chain the backward through them into dL/draw: same images
-    and gradients as adapter -> decoder (to float32 rounding), without the adapter's pass over the tensor in either
-    direction."""
-    S, G, _ = means3D.shape
-    V = extrinsics.shape[1]
-    extrinsics = _f32c(extrinsics, "extrinsics", (S, V, 4, 4))
-    intrinsics = _f32c(intrinsics, "intrinsics", (S, V, 3, 3))
-    near = _f32c(near, "near", (S, V))
-    far = _f32c(far, "far", (S, V))
-    means3D = _f32c(means3D, "means3D", (S, G, 3))
-    opacities = _f32c(opacities.reshape(S, G), "opacities", (S, G))
-    if not isinstance(raw, Tensor) or not raw.is_cuda or raw.dtype != torch.float32:
-        raise RuntimeError("raw must be a float32 tensor on a HIP device (there is no CPU fallback)")
-    C_ = raw.shape[-1]
-    K = (C_ - 7) // 3
-    if C_ != 7 + 3 * K or K < 1 or raw.numel() != S * G * C_:
-        raise RuntimeError(f"raw must hold S*G = {S * G} rows of 7 + 3*d_sh channels, got {tuple(raw.shape)}")
-    if not (0 <= sh_degree <= 4) or K < (min(sh_degree, 4 if sh_band4 else 3) + 1) ** 2:
-        raise RuntimeError(f"raw holds {K} coefficients per channel, too few for sh_degree {sh_degree}")
-    if sh_mask is None:
-        raise RuntimeError("raw rows need the adapter's sh_mask")
-    sh_mask = _f32c(sh_mask, "sh_mask", (K,))
-    if sh_band4 is None:
-        sh_band4 = sh_band4_default()
-        _note_band4_not_evaluated(sh_degree, sh_band4)
-    bg = _background(bg, S, V)
-    return _DecoderRender.apply(extrinsics, intrinsics, near, far, means3D, None, None, opacities, None, None, bg,
-                                int(image_height), int(image_width), int(sh_degree), bool(scale_invariant), True, True,
-                                max_pairs, 3, bool(sh_band4), record, torch.is_grad_enabled(), None, raw, sh_mask,
-                                float(adapter_eps))
+                                bool(scale_invariant), enable_cov_grad, enable_sh_grad, max_pairs, layout, sh_band4, record,
+                                torch.is_grad_enabled(), shs_high, raw, sh_mask if fused else None,
+                                float(adapter_eps) if fused else 0.0, cov3D)
 
 
 def rasterize_batch(means3D: Tensor, scales: Tensor, rotations: Tensor, opacities: Tensor,
@@ -1116,34 +1101,18 @@ def rasterize_batch(means3D: Tensor, scales: Tensor, rotations: Tensor, opacitie
     if means3D.dim() != 3 or means3D.shape[-1] != 3:
         raise RuntimeError(f"means3D must be [S,G,3], got {tuple(means3D.shape)}")
     S, G, _ = means3D.shape
-    if sh_band4 is None:
-        sh_band4 = sh_band4_default()
-        _note_band4_not_evaluated(sh_degree, sh_band4)
     if viewmatrix.dim() != 4:
         raise RuntimeError(f"viewmatrix must be [S,V,4,4], got {tuple(viewmatrix.shape)}")
     V = viewmatrix.shape[1]
-    means3D = _f32c(means3D, "means3D", (S, G, 3))
-    if cov3D is not None:
-        cov3D = _cov6(cov3D, S, G)
-    else:
-        scales = _f32c(scales, "scales", (S, G, 3))
-        rotations = _f32c(rotations, "rotations", (S, G, 4))
-    opacities = _f32c(opacities.reshape(S, G), "opacities", (S, G))
-    if shs is not None:
-        if shs.dim() != 4 or shs.shape[-1] != 3:
-            raise RuntimeError(f"shs must be [S,G,K,3], got {tuple(shs.shape)}")
-        K = shs.shape[2]
-        if K < (min(sh_degree, 4 if sh_band4 else 3) + 1) ** 2:
-            raise RuntimeError(f"shs holds {K} coefficients, too few for sh_degree {sh_degree}")
-        shs = _f32c(shs, "shs", (S, G, K, 3))
-    else:
+    means3D, scales, rotations, opacities, cov3D = _check_gaussians(means3D, scales, rotations, opacities, cov3D, S, G)
+    if shs is not None and (shs.dim() != 4 or shs.shape[-1] != 3):
+        raise RuntimeError(f"shs must be [S,G,K,3], got {tuple(shs.shape)}")
+    shs, _, _, _, _, sh_band4 = _check_sh(S, G, sh_degree, sh_band4, shs)
+    if shs is None:
         colors_precomp = _f32c(colors_precomp, "colors_precomp", (S, G, 3))
-    viewmatrix = _f32c(viewmatrix, "viewmatrix", (S, V, 4, 4))
-    projmatrix = _f32c(projmatrix, "projmatrix", (S, V, 4, 4))
+    viewmatrix, projmatrix = _f32c(viewmatrix, "viewmatrix", (S, V, 4, 4)), _f32c(projmatrix, "projmatrix", (S, V, 4, 4))
     tanfov = _f32c(tanfov, "tanfov", (S, V, 2))
     bg = _background(bg, S, V)
-    if not (0 <= sh_degree <= 4):
-        raise RuntimeError(f"sh_degree {sh_degree} outside 0..4")
     if view_scale is not None:
         view_scale = _f32c(view_scale.detach(), "view_scale", (S, V))
     if means2D is not None and means2D.numel() != S * V * G * 3:

@@ -29,6 +29,7 @@ def test_struct_sizes_match_header():
     assert C.sizeof(_lib.SpfState) == 18 * 8            # + verdict_host (ABI 6)
     assert C.sizeof(_lib.SpfOutputs) == 3 * 8
     assert C.sizeof(_lib.SpfGrads) == 15 * 8           # + dL_dshs_high, dL_draw (ABI 6)
+    assert C.sizeof(_lib.SpfStateLayout) == 12 * 8     # three sizes, nine offsets, int64 each
 
 
 def test_host_helpers_no_gpu(hip_lib):
@@ -37,6 +38,40 @@ def test_host_helpers_no_gpu(hip_lib):
     assert hip_lib.spf_raster_view_partial_blocks(65536) == 256
     assert hip_lib.spf_raster_view_partial_blocks(257) == 2
     assert hip_lib.spf_stage_kernel_name(5) == b"spf_render_bwd_lists_kernel"
+
+
+def test_state_layout_is_the_headers(hip_lib):
+    """spf_raster_state_layout against the three buffers as include/spfsplat_hip.h words them (formulas written out here,
+    not taken from product code): rect (RG) | zkey (RG) | sh_clamp (RG bytes, whole words); tile_count (RT) | tile_flags
+    (RT) | tile_start (RT + 1) | tile_fill (RT) | counters (4) | pair_cursor (8) | padding to 16 bytes; pair_off (2 RG) |
+    blk_total (RB) | blk_base (RB).  (6, 903, 6): one scene, three views of 301 Gaussians at 40 x 24 px -- a partial last
+    block, partial edge tiles and RG % 4 == 3, so the clamp bytes round up."""
+    from spfsplatv2_amd import _lib
+    for RT, RG, RB in ((1, 1, 1), (6, 903, 6), (2048, 524288, 2048)):
+        lay = _lib.SpfStateLayout()
+        assert hip_lib.spf_raster_state_layout(RT, RG, RB, C.byref(lay)) == 0
+        got = {f: getattr(lay, f) for f, _ in _lib.SpfStateLayout._fields_}
+        assert got == dict(rect_words=2 * RG + (RG + 3) // 4, tiles_words=4 * RT + 16, pair_idx_words=2 * RG + 2 * RB,
+                           zkey=RG, sh_clamp=2 * RG, tile_flags=RT, tile_start=2 * RT, tile_fill=3 * RT + 1,
+                           counters=4 * RT + 1, pair_cursor=4 * RT + 5, blk_total=2 * RG, blk_base=2 * RG + RB), (RT, RG, RB)
+        # every field's extent (in words) ends at or before the next field of its buffer, and the last inside the buffer
+        buffers = ((("rect", 0, RG), ("zkey", lay.zkey, RG), ("sh_clamp", lay.sh_clamp, (RG + 3) // 4), lay.rect_words),
+                   (("tile_count", 0, RT), ("tile_flags", lay.tile_flags, RT), ("tile_start", lay.tile_start, RT + 1),
+                    ("tile_fill", lay.tile_fill, RT), ("counters", lay.counters, 4), ("pair_cursor", lay.pair_cursor, 8),
+                    lay.tiles_words),
+                   (("pair_off", 0, 2 * RG), ("blk_total", lay.blk_total, RB), ("blk_base", lay.blk_base, RB),
+                    lay.pair_idx_words))
+        for *fields, words in buffers:
+            starts = [off for _, off, _ in fields] + [words]
+            for (name, off, extent), nxt in zip(fields, starts[1:]):
+                assert off < nxt and off + extent <= nxt, (RT, RG, RB, name)
+        assert (4 * lay.tiles_words) % 16 == 0 and lay.pair_cursor + 8 <= lay.tiles_words
+    lay = _lib.SpfStateLayout()
+    for bad in ((0, 1, 1), (1, 0, 1), (1, 1, 0), (-6, 903, 6)):
+        assert hip_lib.spf_raster_forward_project(None, None, None, None) == -1          # (another error in between)
+        assert hip_lib.spf_raster_state_layout(*bad, C.byref(lay)) == -1                 # SPF_E_INVALID
+        assert b"state_layout" in hip_lib.spf_last_error() and b"positive" in hip_lib.spf_last_error(), bad
+    assert hip_lib.spf_raster_state_layout(1, 1, 1, None) == -1
 
 
 def test_launch_slots_cover_every_tile_once(hip_lib):
