@@ -58,7 +58,8 @@ extern "C" {
 #define SPF_ABI_VERSION 7   /* unchanged by the spf_regr3d_* family: it only ADDS a struct and three entry points; no
                               existing struct, signature or meaning moved, so a caller built against 7 still fits.
                               The same holds for the pose path (spf_pose_compose_*, spf_depth_project_*, spf_pose_error,
-                              spf_focal_*): eight entry points added, nothing moved; spf_raster_state_layout likewise */
+                              spf_focal_*): eight entry points added, nothing moved; spf_raster_state_layout likewise; and for the
+                              fused attention (SpfAttn, SpfAttnGrads, spf_attn_forward, spf_attn_backward) */
 
 #define SPF_OK 0
 #define SPF_E_INVALID (-1)   /* bad argument (null pointer, size, unsupported degree ...) */
@@ -666,6 +667,38 @@ int spf_rope2d(void* tokens, const int64_t* positions, int32_t B, int32_t N, int
 int spf_rope2d_pair(void* tokens, void* tokens2, const int64_t* positions, int32_t B, int32_t N, int32_t H, int32_t D,
                     int64_t stride_b, int64_t stride_n, int64_t stride_h, int32_t pos_div, int32_t dtype, float base,
                     float fwd, void* stream);
+
+/* Fused RoPE attention, head dim 64 (croco/blocks.py Attention.forward:94-113 and CrossAttention.forward:150-179
+ * without mask and dropout):  out = softmax(scale * R(qpos) q * (R(kpos) k)^T) * v.
+ * q [B,H,Nq,64] and k, v [B,H,Nk,64] are read through element strides (batch, token, head; stride(D) == 1), so the
+ * views of a packed [B,N,3,H,D] projection are read in place.  Every row must be 16-byte aligned (pointers and
+ * strides * element size).  dtype: 0 = float32, 1 = float16, 2 = bfloat16 (one float32 compute path).  qpos [B,Nq,2],
+ * kpos [B,Nk,2]: int64 contiguous (y, x), rotation of spf_rope2d with (base, F0); both null: no rotation. */
+typedef struct SpfAttn {
+    const void* q;
+    const void* k;
+    const void* v;
+    const int64_t* qpos;
+    const int64_t* kpos;
+    int64_t q_stride[3], k_stride[3], v_stride[3];
+    int32_t B, H, Nq, Nk, D, dtype;
+    float base, F0, scale;
+} SpfAttn;
+/* Where the backward writes: dq [B,H,Nq,64], dk, dv [B,H,Nk,64] through strides of their own (the three may be views of
+ * one packed gradient), same dtype as the inputs; delta: B*H*Nq floats of scratch. */
+typedef struct SpfAttnGrads {
+    void* dq;
+    void* dk;
+    void* dv;
+    int64_t dq_stride[3], dk_stride[3], dv_stride[3];
+    float* delta;
+} SpfAttnGrads;
+/* out [B,Nq,H*64] contiguous (dtype), lse [B,H,Nq] float32 (log-sum-exp of the scaled scores, for the backward).
+ * Nothing is allocated or synchronised. */
+int spf_attn_forward(const SpfAttn* args, void* out, float* lse, void* stream);
+/* out, lse: what the forward wrote; dout [B,Nq,H*64] contiguous.  No atomics: bitwise reproducible. */
+int spf_attn_backward(const SpfAttn* args, const SpfAttnGrads* grads, const void* out, const float* lse,
+                      const void* dout, void* stream);
 
 /* Per-stage device timing with HIP events recorded on the launch stream around every kernel
  * stage.  spf_stage_timing_enable(mask) clears the log and starts recording the stages whose bit

@@ -82,6 +82,18 @@ class SpfLpips(C.Structure):
                 ("lin", C.c_void_p), ("shift_scale", C.c_void_p)]
 
 
+class SpfAttn(C.Structure):
+    _fields_ = [("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("qpos", C.c_void_p), ("kpos", C.c_void_p),
+                ("q_stride", C.c_int64 * 3), ("k_stride", C.c_int64 * 3), ("v_stride", C.c_int64 * 3),
+                ("B", C.c_int32), ("H", C.c_int32), ("Nq", C.c_int32), ("Nk", C.c_int32), ("D", C.c_int32),
+                ("dtype", C.c_int32), ("base", C.c_float), ("F0", C.c_float), ("scale", C.c_float)]
+
+
+class SpfAttnGrads(C.Structure):
+    _fields_ = [("dq", C.c_void_p), ("dk", C.c_void_p), ("dv", C.c_void_p), ("dq_stride", C.c_int64 * 3),
+                ("dk_stride", C.c_int64 * 3), ("dv_stride", C.c_int64 * 3), ("delta", C.c_void_p)]
+
+
 # Every symbol include/spfsplat_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "spf_abi_version": (C.c_int, []),
@@ -169,6 +181,9 @@ SYMBOLS = {
     "spf_rope2d_pair": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                   C.c_void_p]),
+    "spf_attn_forward": (C.c_int, [C.POINTER(SpfAttn), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_attn_backward": (C.c_int, [C.POINTER(SpfAttn), C.POINTER(SpfAttnGrads),
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_stage_timing_enable": (C.c_int, [C.c_int32]),
     "spf_stage_timing_sample_every": (C.c_int, [C.c_int32]),
     "spf_stage_times_ms": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_int32)]),

@@ -1,0 +1,300 @@
+"""Fused RoPE attention on the HIP library: the core of the reference's ``Attention`` and ``CrossAttention``.
+
+=========================  ============================================================================
+here                       reference (src/model/encoder/backbone/croco/blocks.py)
+=========================  ============================================================================
+``rope_attention``         lines 102-110 / 161-176: rope(q), rope(k), q @ k^T * scale, softmax, @ v,
+                           ``.transpose(1, 2).reshape(B, N, C)``
+``rope_attention_packed``  the same on the three views of one ``[B,N,3,H,D]`` projection (lines 97-98)
+``Attention``              ``Attention`` (81-113)
+``CrossAttention``         ``CrossAttention`` (133-179)
+=========================  ============================================================================
+
+One kernel per direction of the data flow (csrc/attention.hip): the score matrix never exists in memory, q and k are
+rotated while they are staged, strided views are read in place.  Head dim 64 only; no mask, no dropout on the
+probabilities, no CPU path -- each of these raises before anything is launched.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+from torch import nn
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+from .rope import _DTYPES
+
+HEAD_DIM = 64
+
+
+def _check_tokens(t: torch.Tensor) -> None:
+    if t.dim() != 4:
+        raise RuntimeError("tokens must have 4 dimensions")
+    if t.shape[3] != HEAD_DIM:
+        raise ValueError(f"rope_attention: head dim must be {HEAD_DIM}, got {t.shape[3]}")
+    if t.dtype not in _DTYPES:
+        raise RuntimeError(f"rope_attention: unsupported dtype {t.dtype}")
+
+
+def _check_positions(tokens: torch.Tensor, positions: torch.Tensor) -> None:
+    """rope._check's position checks, same messages (tokens here are [B,H,N,D])."""
+    if positions.dim() != 3:
+        raise RuntimeError("positions must have 3 dimensions")
+    if tokens.size(0) != positions.size(0):
+        raise RuntimeError("batch size differs between tokens & positions")
+    if tokens.size(2) != positions.size(1):
+        raise RuntimeError("seq_length differs between tokens & positions")
+    if positions.size(2) != 2:
+        raise RuntimeError("positions.shape[2] must be equal to 2")
+    if tokens.is_cuda != positions.is_cuda or (positions.is_cuda and positions.device != tokens.device):
+        raise RuntimeError("tokens and positions are not on the same device")
+    if not positions.is_contiguous():
+        raise RuntimeError("positions are not contiguous")
+    if positions.dtype != torch.int64:
+        raise RuntimeError("positions must be int64")
+
+
+def _check(q, k, v, qpos, kpos) -> None:
+    for t in (q, k, v):
+        _check_tokens(t)
+    if not (q.dtype == k.dtype == v.dtype):
+        raise RuntimeError(f"rope_attention: q, k and v differ in dtype ({q.dtype}, {k.dtype}, {v.dtype})")
+    if not (q.device == k.device == v.device):
+        raise RuntimeError("rope_attention: q, k and v are not on the same device")
+    if k.shape != v.shape or q.shape[:2] != k.shape[:2]:
+        raise RuntimeError(f"rope_attention: shapes differ: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}")
+    if (qpos is None) != (kpos is None):
+        raise RuntimeError("rope_attention: qpos and kpos must both be given or both be None")
+    if qpos is not None:
+        _check_positions(q, qpos)
+        _check_positions(k, kpos)
+    if not q.is_cuda:
+        raise RuntimeError("rope_attention: q, k and v are on the CPU; this build only runs on a HIP device "
+                           "(no CPU fallback)")
+
+
+def _rows(t: torch.Tensor) -> torch.Tensor:
+    """``t`` itself when the kernels can read it in place (unit stride along D, 16-byte aligned rows), else a copy."""
+    es = t.element_size()
+    if t.stride(3) == 1 and t.data_ptr() % 16 == 0 and all((t.stride(i) * es) % 16 == 0 for i in range(3)):
+        return t
+    return t.contiguous()
+
+
+def _strides(t: torch.Tensor):
+    """(batch, token, head) element strides of a [B,H,N,D] tensor."""
+    return (C.c_int64 * 3)(t.stride(0), t.stride(2), t.stride(1))
+
+
+def _args(q, k, v, qpos, kpos, base, F0, scale) -> _lib.SpfAttn:
+    B, H, Nq, D = q.shape
+    a = _lib.SpfAttn()
+    a.q, a.k, a.v = q.data_ptr(), k.data_ptr(), v.data_ptr()
+    a.qpos = qpos.data_ptr() if qpos is not None else None
+    a.kpos = kpos.data_ptr() if kpos is not None else None
+    a.q_stride, a.k_stride, a.v_stride = _strides(q), _strides(k), _strides(v)
+    a.B, a.H, a.Nq, a.Nk, a.D, a.dtype = B, H, Nq, k.shape[2], D, _DTYPES[q.dtype]
+    a.base, a.F0, a.scale = float(base), float(F0), float(scale)
+    return a
+
+
+def attention_forward(q, k, v, qpos, kpos, base, F0, scale):
+    """The forward launch: (out [B,Nq,H*D], lse [B,H,Nq] float32).  q, k, v: [B,H,N,64] views, read in place."""
+    _check(q, k, v, qpos, kpos)
+    q, k, v = _rows(q), _rows(k), _rows(v)
+    B, H, Nq, D = q.shape
+    out = torch.empty(B, Nq, H * D, dtype=q.dtype, device=q.device)
+    lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
+    lib = _lib.load()
+    with torch.cuda.device(q.device):
+        stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        a = _args(q, k, v, qpos, kpos, base, F0, scale)
+        _lib.check(lib.spf_attn_forward(C.byref(a), C.c_void_p(out.data_ptr()), C.c_void_p(lse.data_ptr()), stream),
+                   "spf_attn_forward")
+    return out, lse
+
+
+def attention_backward(q, k, v, qpos, kpos, base, F0, scale, out, lse, dout, dq, dk, dv) -> None:
+    """The backward launches: writes dq [B,H,Nq,64], dk, dv [B,H,Nk,64] (any views with 16-byte aligned rows, e.g. the
+    three slices of one packed gradient) from what the forward saved."""
+    _check(q, k, v, qpos, kpos)
+    q, k, v = _rows(q), _rows(k), _rows(v)
+    out, dout = out.contiguous(), dout.contiguous()
+    if dout.dtype != q.dtype or out.dtype != q.dtype:
+        raise RuntimeError(f"rope_attention: gradient dtype {dout.dtype} differs from the inputs' {q.dtype}")
+    B, H, Nq, D = q.shape
+    delta = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
+    lib = _lib.load()
+    with torch.cuda.device(q.device):
+        stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        a = _args(q, k, v, qpos, kpos, base, F0, scale)
+        g = _lib.SpfAttnGrads()
+        g.dq, g.dk, g.dv, g.delta = dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr()
+        g.dq_stride, g.dk_stride, g.dv_stride = _strides(dq), _strides(dk), _strides(dv)
+        _lib.check(lib.spf_attn_backward(C.byref(a), C.byref(g), C.c_void_p(out.data_ptr()), C.c_void_p(lse.data_ptr()),
+                                         C.c_void_p(dout.data_ptr()), stream), "spf_attn_backward")
+
+
+class _RopeAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, qpos, kpos, base, F0, scale):
+        out, lse = attention_forward(q, k, v, qpos, kpos, base, F0, scale)
+        ctx.save_for_backward(q, k, v, qpos, kpos, out, lse)
+        ctx.cfg = (base, F0, scale)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        q, k, v, qpos, kpos, out, lse = ctx.saved_tensors
+        B, H, Nq, D = q.shape
+        Nk = k.shape[2]
+        # token-major buffers: the [B,H,N,D] views of them are what a following reshape(B, N, C) wants
+        dq = torch.empty(B, Nq, H, D, dtype=q.dtype, device=q.device).transpose(1, 2)
+        dk = torch.empty(B, Nk, H, D, dtype=q.dtype, device=q.device).transpose(1, 2)
+        dv = torch.empty(B, Nk, H, D, dtype=q.dtype, device=q.device).transpose(1, 2)
+        attention_backward(q, k, v, qpos, kpos, *ctx.cfg, out, lse, dout, dq, dk, dv)
+        need = ctx.needs_input_grad
+        return (dq if need[0] else None, dk if need[1] else None, dv if need[2] else None,
+                None, None, None, None, None)
+
+
+class _RopeAttentionPacked(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, pos, base, F0, scale):
+        q, k, v = _views(qkv)
+        out, lse = attention_forward(q, k, v, pos, pos, base, F0, scale)
+        ctx.save_for_backward(qkv, pos, out, lse)
+        ctx.cfg = (base, F0, scale)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        qkv, pos, out, lse = ctx.saved_tensors
+        q, k, v = _views(qkv)
+        dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
+        dq, dk, dv = _views(dqkv)
+        attention_backward(q, k, v, pos, pos, *ctx.cfg, out, lse, dout, dq, dk, dv)
+        return dqkv, None, None, None, None
+
+
+def _views(qkv: torch.Tensor):
+    """q, k, v [B,H,N,D] of a packed [B,N,3,H,D] buffer (blocks.py:97-98)."""
+    t = qkv.transpose(1, 3)
+    return t[:, :, 0], t[:, :, 1], t[:, :, 2]
+
+
+def rope_attention(q, k, v, qpos=None, kpos=None, *, base: float = 100.0, F0: float = 1.0, scale=None):
+    """softmax(scale * rope(q, qpos) @ rope(k, kpos)^T) @ v, returned as [B,Nq,H*D].
+
+    q [B,H,Nq,64], k and v [B,H,Nk,64]: any views with unit stride along D and 16-byte aligned rows are read in place
+    (anything else is copied first).  qpos [B,Nq,2], kpos [B,Nk,2]: int64 (y, x), contiguous; both None: no rotation.
+    """
+    _check(q, k, v, qpos, kpos)
+    if scale is None:
+        scale = q.shape[3] ** -0.5
+    return _RopeAttention.apply(q, k, v, qpos, kpos, float(base), float(F0), float(scale))
+
+
+def rope_attention_packed(qkv, pos=None, *, base: float = 100.0, F0: float = 1.0, scale=None):
+    """Self-attention on a packed projection qkv [B,N,3,H,64] (what ``self.qkv(x).reshape(B, N, 3, H, D)`` yields):
+    the same result as ``rope_attention`` on its three views, and ONE gradient of the packed shape out of the backward
+    instead of three that autograd would have to add up."""
+    if qkv.dim() != 5 or qkv.shape[2] != 3:
+        raise RuntimeError(f"rope_attention_packed: qkv must be [B,N,3,H,D], got {tuple(qkv.shape)}")
+    _check(*_views(qkv), pos, pos)
+    if not qkv.is_contiguous():
+        qkv = qkv.contiguous()
+    if scale is None:
+        scale = qkv.shape[4] ** -0.5
+    return _RopeAttentionPacked.apply(qkv, pos, float(base), float(F0), float(scale))
+
+
+def _rope_cfg(rope):
+    if rope is None:
+        return None
+    if not (hasattr(rope, "base") and hasattr(rope, "F0")):
+        raise TypeError(f"rope must be a cuRoPE2D (base, F0) or None, got {type(rope).__name__}")
+    return float(rope.base), float(rope.F0)
+
+
+def _check_module(mod, mask=None) -> None:
+    if mask is not None:
+        raise NotImplementedError("attention masks are not supported by the fused kernel (the reference's live path, "
+                                  "'mask v2', passes none)")
+    if mod.training and mod.attn_drop.p > 0:
+        raise NotImplementedError("attn_drop > 0 in training mode is not supported by the fused kernel")
+
+
+class Attention(nn.Module):
+    """blocks.py:81-113 with the fused core; same parameters, same state dict."""
+
+    def __init__(self, dim, rope=None, num_heads=8, qkv_bias=False, attn_drop=0., proj_drop=0.):
+        super().__init__()
+        self.num_heads = num_heads
+        head_dim = dim // num_heads
+        self.scale = head_dim ** -0.5
+        self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
+        self.attn_drop = nn.Dropout(attn_drop)
+        self.proj = nn.Linear(dim, dim)
+        self.proj_drop = nn.Dropout(proj_drop)
+        self.rope = rope
+
+    def forward(self, x, xpos):
+        B, N, C = x.shape
+        _check_module(self)
+        if C // self.num_heads != HEAD_DIM:
+            raise ValueError(f"rope_attention: head dim must be {HEAD_DIM}, got {C // self.num_heads}")
+        cfg = _rope_cfg(self.rope)
+        if not x.is_cuda:
+            raise RuntimeError("Attention: x is on the CPU; this build only runs on a HIP device (no CPU fallback)")
+        qkv = self.qkv(x).reshape(B, N, 3, self.num_heads, C // self.num_heads)
+        if cfg is None:
+            x = rope_attention_packed(qkv, None, scale=self.scale)
+        else:
+            x = rope_attention_packed(qkv, xpos, base=cfg[0], F0=cfg[1], scale=self.scale)
+        x = self.proj(x)
+        x = self.proj_drop(x)
+        return x
+
+
+class CrossAttention(nn.Module):
+    """blocks.py:133-179 with the fused core; same parameters, same state dict."""
+
+    def __init__(self, dim, rope=None, num_heads=8, qkv_bias=False, attn_drop=0., proj_drop=0.):
+        super().__init__()
+        self.num_heads = num_heads
+        head_dim = dim // num_heads
+        self.scale = head_dim ** -0.5
+        self.projq = nn.Linear(dim, dim, bias=qkv_bias)
+        self.projk = nn.Linear(dim, dim, bias=qkv_bias)
+        self.projv = nn.Linear(dim, dim, bias=qkv_bias)
+        self.attn_drop = nn.Dropout(attn_drop)
+        self.proj = nn.Linear(dim, dim)
+        self.proj_drop = nn.Dropout(proj_drop)
+        self.rope = rope
+
+    def forward(self, query, key, value, qpos, kpos, mask=None):
+        B, Nq, C = query.shape
+        Nk = key.shape[1]
+        Nv = value.shape[1]
+        _check_module(self, mask)
+        H, D = self.num_heads, C // self.num_heads
+        if D != HEAD_DIM:
+            raise ValueError(f"rope_attention: head dim must be {HEAD_DIM}, got {D}")
+        cfg = _rope_cfg(self.rope)
+        if not query.is_cuda:
+            raise RuntimeError("CrossAttention: query is on the CPU; this build only runs on a HIP device "
+                               "(no CPU fallback)")
+        q = self.projq(query).reshape(B, Nq, H, D).permute(0, 2, 1, 3)
+        k = self.projk(key).reshape(B, Nk, H, D).permute(0, 2, 1, 3)
+        v = self.projv(value).reshape(B, Nv, H, D).permute(0, 2, 1, 3)
+        if cfg is None:
+            x = rope_attention(q, k, v, scale=self.scale)
+        else:
+            x = rope_attention(q, k, v, qpos, kpos, base=cfg[0], F0=cfg[1], scale=self.scale)
+        x = self.proj(x)
+        x = self.proj_drop(x)
+        return x

@@ -70,6 +70,8 @@ hipError_t launch_camera_fwd(const SpfCamera&, hipStream_t);
 hipError_t launch_camera_bwd(const SpfCamera&, const float*, float*, hipStream_t);
 hipError_t launch_camera_fwd_zero(const SpfCamera&, void*, uint64_t, hipStream_t);
 hipError_t launch_camera_bwd_reduce(const SpfCamera&, const float*, int, float*, hipStream_t);
+hipError_t launch_attn_forward(const SpfAttn&, void*, float*, hipStream_t);
+hipError_t launch_attn_backward(const SpfAttn&, const SpfAttnGrads&, const void*, const float*, const void*, hipStream_t);
 hipError_t launch_rope2d(void*, void*, const int64_t*, int, int, int, int, int64_t, int64_t, int64_t, int, int, float,
                          float, hipStream_t);
 }  // namespace spf
@@ -1025,6 +1027,52 @@ int spf_rope2d_pair(void* tokens, void* tokens2, const int64_t* positions, int32
     if (!tokens2) return fail(SPF_E_INVALID, "tokens2 is null");
     return rope2d_impl(tokens, tokens2, positions, B, N, H, D, stride_b, stride_n, stride_h, pos_div, dtype, base, fwd,
                        stream_);
+}
+
+// arguments of an attention call: 0, or the message of the first one that is wrong
+static bool attn_rows_aligned(const void* p, const int64_t* stride, int esize) {
+    if (reinterpret_cast<uintptr_t>(p) % 16 != 0) return false;
+    for (int i = 0; i < 3; ++i)
+        if ((stride[i] * esize) % 16 != 0) return false;
+    return true;
+}
+static const char* attn_args_error(const SpfAttn* a) {
+    if (!a) return "attention: args is null";
+    if (!a->q || !a->k || !a->v) return "attention: q / k / v is null";
+    if ((a->qpos == nullptr) != (a->kpos == nullptr)) return "attention: qpos and kpos must both be given or both be null";
+    if (a->D != 64) return "attention: head dim must be 64";
+    if (a->B < 1 || a->H < 1 || a->Nq < 1 || a->Nk < 1) return "attention: B, H, Nq and Nk must be positive";
+    if (a->B > 65535 || a->H > 65535) return "attention: B and H must not exceed 65535";
+    if (a->dtype < 0 || a->dtype > 2) return "attention: dtype must be 0 (f32), 1 (f16) or 2 (bf16)";
+    const int es = a->dtype == 0 ? 4 : 2;
+    if (!attn_rows_aligned(a->q, a->q_stride, es) || !attn_rows_aligned(a->k, a->k_stride, es) ||
+        !attn_rows_aligned(a->v, a->v_stride, es))
+        return "attention: rows of q, k and v must be 16-byte aligned";
+    return nullptr;
+}
+
+int spf_attn_forward(const SpfAttn* args, void* out, float* lse, void* stream_) {
+    if (const char* e = attn_args_error(args)) return fail(SPF_E_INVALID, "%s", e);
+    if (!out || !lse) return fail(SPF_E_INVALID, "attention: out / lse is null");
+    if (reinterpret_cast<uintptr_t>(out) % 16 != 0) return fail(SPF_E_INVALID, "attention: rows of out must be 16-byte aligned");
+    SPF_HIP(spf::launch_attn_forward(*args, out, lse, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_attn_backward(const SpfAttn* args, const SpfAttnGrads* g, const void* out, const float* lse, const void* dout,
+                      void* stream_) {
+    if (const char* e = attn_args_error(args)) return fail(SPF_E_INVALID, "%s", e);
+    if (!g) return fail(SPF_E_INVALID, "attention: grads is null");
+    if (!out || !lse || !dout) return fail(SPF_E_INVALID, "attention: out / lse / dout is null");
+    if (!g->dq || !g->dk || !g->dv || !g->delta) return fail(SPF_E_INVALID, "attention: dq / dk / dv / delta is null");
+    const int es = args->dtype == 0 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(out) % 16 != 0 || reinterpret_cast<uintptr_t>(dout) % 16 != 0)
+        return fail(SPF_E_INVALID, "attention: rows of out and dout must be 16-byte aligned");
+    if (!attn_rows_aligned(g->dq, g->dq_stride, es) || !attn_rows_aligned(g->dk, g->dk_stride, es) ||
+        !attn_rows_aligned(g->dv, g->dv_stride, es))
+        return fail(SPF_E_INVALID, "attention: rows of dq, dk and dv must be 16-byte aligned");
+    SPF_HIP(spf::launch_attn_backward(*args, *g, out, lse, dout, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
 }
 
 // sizes of an LPIPS call: 0, or the message of the first one that is wrong

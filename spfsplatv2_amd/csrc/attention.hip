@@ -1,0 +1,499 @@
+// Fused RoPE attention for gfx950, head dim 64: forward and backward of
+//   out = softmax(scale * R(qpos) q * (R(kpos) k)^T) * v
+// (croco/blocks.py Attention.forward / CrossAttention.forward without mask and dropout).  The score matrix never
+// exists in memory and the rotation costs no pass of its own: q and k are rotated while they are staged.
+//
+// Arithmetic: every product runs on v_mfma_f32_32x32x2_f32 (exact float32 fma chains), the softmax in float32;
+// float16 / bfloat16 operands are converted when they are loaded and stored -- one compute path.
+//
+// Tiles.  A block is 4 waves; a wave owns 32 rows of the block's 128 ("owner" rows: queries in the forward and in
+// the dq pass, keys in the dk/dv pass) and keeps them, rotated, in 32 registers per operand as the B operand of the
+// matrix instruction (lane l: row l & 31, elements d = 2 s + (l >> 5), s < 32).  The other side is walked in tiles of
+// 32 rows staged in LDS (pitch 65 floats: a column read by 32 lanes and a row read by 32 lanes are both free of bank
+// conflicts); the next tile's global loads are in flight under the current tile's matrix instructions.
+//
+// The score tile is computed TRANSPOSED with respect to the owner: X = staged * owner^T, so the owner's row is the
+// accumulator's column, which lives on ONE lane (and its partner l ^ 32): C/D map of the 32 x 32 tile: column =
+// lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  Row-wise softmax statistics are then per lane (one exchange
+// with lane ^ 32), and the second product Y = staged^T * X sums over X's ROW index, so X's registers are its B operand
+// as they are: register r of lane half h is row rowbase(r) + 4 h, i.e. k-step r pairs rows (i, i + 4).  No LDS round
+// trip for the probabilities.
+//
+// Backward: no atomics.  spf_attn_dkdv_kernel owns key rows and loops over query tiles; spf_attn_dq_kernel owns query
+// rows and loops over key tiles; both recompute the probabilities from the saved log-sum-exp.  The row term
+// delta = sum_d dout * out is a small pre-pass, which the dq pass (run first) refines to sum_j p dP for the dk/dv pass.
+// Every sum has a fixed order: results are bitwise reproducible.
+#include "rope_math.h"
+
+namespace spf {
+
+namespace {
+
+typedef float f16v __attribute__((ext_vector_type(16)));
+
+constexpr int kAttnD = 64;          // head dim (the only one)
+constexpr int kAttnT = 32;          // rows of a staged tile = rows a wave owns
+constexpr int kAttnOwn = 128;       // rows a block owns
+constexpr int kAttnLd = 65;         // LDS pitch of a staged row, floats
+
+struct AttnArgs {
+    const void *q, *k, *v;
+    const int64_t *qpos, *kpos;
+    int64_t qs[3], ks[3], vs[3];    // element strides: batch, token, head
+    int B, H, Nq, Nk;
+    float scale;
+    RopeFreq f;                     // +F0 / base^(q/16)
+};
+struct AttnGradArgs {
+    void *dq, *dk, *dv;
+    int64_t dqs[3], dks[3], dvs[3];
+};
+
+template <typename T> __device__ __forceinline__ void load4(const T* p, float* f);
+template <> __device__ __forceinline__ void load4<float>(const float* p, float* f) {
+    const f4a v = *reinterpret_cast<const f4a*>(p);
+    f[0] = v[0]; f[1] = v[1]; f[2] = v[2]; f[3] = v[3];
+}
+template <typename H> struct __attribute__((aligned(8))) Half4 { H h[4]; };
+template <typename H> __device__ __forceinline__ void load4h(const H* p, float* f) {
+    const Half4<H> v = *reinterpret_cast<const Half4<H>*>(p);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f[i] = to_f<H>(v.h[i]);
+}
+template <> __device__ __forceinline__ void load4<__half>(const __half* p, float* f) { load4h(p, f); }
+template <> __device__ __forceinline__ void load4<__hip_bfloat16>(const __hip_bfloat16* p, float* f) { load4h(p, f); }
+
+template <typename T> __device__ __forceinline__ void store4(T* p, float a, float b, float c, float d);
+template <> __device__ __forceinline__ void store4<float>(float* p, float a, float b, float c, float d) {
+    *reinterpret_cast<f4a*>(p) = f4a{a, b, c, d};
+}
+template <typename H> __device__ __forceinline__ void store4h(H* p, float a, float b, float c, float d) {
+    Half4<H> v;
+    v.h[0] = from_f<H>(a); v.h[1] = from_f<H>(b); v.h[2] = from_f<H>(c); v.h[3] = from_f<H>(d);
+    *reinterpret_cast<Half4<H>*>(p) = v;
+}
+template <> __device__ __forceinline__ void store4<__half>(__half* p, float a, float b, float c, float d) { store4h(p, a, b, c, d); }
+template <> __device__ __forceinline__ void store4<__hip_bfloat16>(__hip_bfloat16* p, float a, float b, float c, float d) { store4h(p, a, b, c, d); }
+
+// One lane's share of a staged tile of 32 rows x 64: row tid >> 3, and of that row the four (u, v) pairs with
+// frequencies q0 .. q0 + 3 of half x (y positions rotate d < 32, x positions d >= 32; u at 32 x + q, v at 32 x + 16 + q).
+struct Stage {
+    float u[4], v[4], p;
+};
+template <typename T>
+__device__ __forceinline__ void stage_load(Stage& r, const T* __restrict__ base, int64_t stride_n,
+                                           const int64_t* __restrict__ pos, int row0, int N, int tid) {
+    const int row = row0 + (tid >> 3), part = tid & 7, x = part >> 2, q0 = (part & 3) * 4;
+    r.p = 0.f;
+    if (row < N) {
+        const T* __restrict__ s = base + (int64_t)row * stride_n + 32 * x + q0;
+        load4<T>(s, r.u);
+        load4<T>(s + 16, r.v);
+        if (pos) r.p = (float)pos[(int64_t)row * 2 + x];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r.u[k] = r.v[k] = 0.f;
+    }
+}
+// rotate (rot) by +angle, scale by mult, write into the LDS image
+__device__ __forceinline__ void stage_commit(const Stage& r, float* __restrict__ s_t, bool rot, const RopeFreq& f,
+                                             float mult, int tid) {
+    const int part = tid & 7, x = part >> 2, q0 = (part & 3) * 4;
+    float* __restrict__ d = s_t + (tid >> 3) * kAttnLd + 32 * x + q0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float u = r.u[k], v = r.v[k];
+        if (rot) {
+            float sn, cs;
+            rope_sincos(r.p * f.inv[q0 + k], sn, cs);
+            // (explicit fused steps: every element type must round the rotation the same way)
+            const float uo = fmaf(u, cs, -(v * sn)), vo = fmaf(v, cs, u * sn);
+            u = uo; v = vo;
+        }
+        d[k] = u * mult;
+        d[16 + k] = v * mult;
+    }
+}
+
+__device__ __forceinline__ int acc_row(int r, int kl) { return (r & 3) + 8 * (r >> 2) + 4 * kl; }
+
+// The rows a wave owns, as B operands: stage the block's 128 rows 32 at a time through s_a (and s_b for a second
+// operand with the same rows), each wave keeps its own chunk.
+template <typename T>
+__device__ __forceinline__ void own_rows(float (&ra)[32], const T* __restrict__ a, int64_t a_sn, const int64_t* __restrict__ pos,
+                                         float mult, float (&rb)[32], const T* __restrict__ b, int64_t b_sn, int row0, int N,
+                                         float* __restrict__ s_a, float* __restrict__ s_b, const RopeFreq& f, int tid) {
+    const int lane = tid & 63, wave = tid >> 6, il = lane & 31, kl = lane >> 5;
+#pragma unroll 1
+    for (int w = 0; w < 4; ++w) {
+        Stage sa, sb;
+        stage_load<T>(sa, a, a_sn, pos, row0 + kAttnT * w, N, tid);
+        if (b) stage_load<T>(sb, b, b_sn, nullptr, row0 + kAttnT * w, N, tid);
+        __syncthreads();
+        stage_commit(sa, s_a, pos != nullptr, f, mult, tid);
+        if (b) stage_commit(sb, s_b, false, f, 1.f, tid);
+        __syncthreads();
+        if (w == wave) {
+#pragma unroll
+            for (int s = 0; s < 32; ++s) {
+                ra[s] = s_a[il * kAttnLd + 2 * s + kl];
+                if (b) rb[s] = s_b[il * kAttnLd + 2 * s + kl];
+            }
+        }
+    }
+}
+
+// gradient of a rotated row back to the unrotated one (rotation by -angle) and its store: acc0 / acc1 hold d < 32 / d >= 32
+// of the row on this lane (rows of the accumulator = d), `g` = its address, pos = the row's (y, x) or null
+template <typename T>
+__device__ __forceinline__ void store_row(T* __restrict__ g, f16v acc0, f16v acc1, float mult, const int64_t* __restrict__ pos,
+                                          const RopeFreq& f, int kl) {
+#pragma unroll
+    for (int x = 0; x < 2; ++x) {
+        f16v a = x ? acc1 : acc0;
+        if (pos) {
+            const float p = (float)pos[x];
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {       // u: registers 0..7 (d < 16 of the half), v: registers 8..15 (d + 16)
+                float sn, cs;
+                rope_sincos(p * f.inv[(r & 3) + 8 * (r >> 2) + 4 * kl], sn, cs);
+                const float u = a[r], v = a[r + 8];
+                a[r] = fmaf(u, cs, v * sn);
+                a[r + 8] = fmaf(v, cs, -(u * sn));
+            }
+        }
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq)
+            store4<T>(g + 32 * x + 8 * gq + 4 * kl, a[4 * gq] * mult, a[4 * gq + 1] * mult, a[4 * gq + 2] * mult,
+                      a[4 * gq + 3] * mult);
+    }
+}
+
+// ---- forward -------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(kBlock) void spf_attn_fwd_kernel(AttnArgs a, T* __restrict__ out, float* __restrict__ lse) {
+    __shared__ float s_k[kAttnT * kAttnLd];
+    __shared__ float s_v[kAttnT * kAttnLd];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, il = lane & 31, kl = lane >> 5;
+    const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * kAttnOwn;
+    const T* __restrict__ qb = static_cast<const T*>(a.q) + b * a.qs[0] + h * a.qs[2];
+    const T* __restrict__ kb = static_cast<const T*>(a.k) + b * a.ks[0] + h * a.ks[2];
+    const T* __restrict__ vb = static_cast<const T*>(a.v) + b * a.vs[0] + h * a.vs[2];
+    const int64_t* __restrict__ qp = a.qpos ? a.qpos + (int64_t)b * a.Nq * 2 : nullptr;
+    const int64_t* __restrict__ kp = a.kpos ? a.kpos + (int64_t)b * a.Nk * 2 : nullptr;
+
+    float qr[32], unused[32];
+    own_rows<T>(qr, qb, a.qs[1], qp, a.scale, unused, nullptr, 0, q0, a.Nq, s_k, s_v, a.f, tid);
+    const bool active = q0 + kAttnT * wave < a.Nq;      // wave-uniform: a wave without queries only helps staging
+
+    f16v o0, o1;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o0[e] = o1[e] = 0.f;
+    float m = -INFINITY, l = 0.f;
+    Stage sk, sv;
+    stage_load<T>(sk, kb, a.ks[1], kp, 0, a.Nk, tid);
+    stage_load<T>(sv, vb, a.vs[1], nullptr, 0, a.Nk, tid);
+#pragma unroll 1
+    for (int k0 = 0; k0 < a.Nk; k0 += kAttnT) {
+        __syncthreads();                                // the previous tile's readers are done
+        stage_commit(sk, s_k, kp != nullptr, a.f, 1.f, tid);
+        stage_commit(sv, s_v, false, a.f, 1.f, tid);
+        __syncthreads();
+        if (k0 + kAttnT < a.Nk) {                       // in flight under the matrix instructions below
+            stage_load<T>(sk, kb, a.ks[1], kp, k0 + kAttnT, a.Nk, tid);
+            stage_load<T>(sv, vb, a.vs[1], nullptr, k0 + kAttnT, a.Nk, tid);
+        }
+        if (!active) continue;
+        f16v s;                                         // S^T: rows = keys, column = this lane's query
+#pragma unroll
+        for (int e = 0; e < 16; ++e) s[e] = 0.f;
+#pragma unroll
+        for (int st = 0; st < 32; ++st)
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(s_k[il * kAttnLd + 2 * st + kl], qr[st], s, 0, 0, 0);
+        if (k0 + kAttnT > a.Nk) {                       // padded keys: probability 0
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if (k0 + acc_row(r, kl) >= a.Nk) s[r] = -INFINITY;
+        }
+        float tmax = s[0];
+#pragma unroll
+        for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, s[r]);
+        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, kWave));
+        const float mn = fmaxf(m, tmax);                // finite: every tile holds at least one key
+        const float alpha = expf(m - mn);
+        m = mn;
+        float ps = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            s[r] = expf(s[r] - mn);
+            ps += s[r];
+        }
+        l = l * alpha + ps;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) { o0[e] *= alpha; o1[e] *= alpha; }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {                  // O^T += V^T P^T: k-step r pairs keys (i, i + 4)
+            const float* __restrict__ vrow = s_v + acc_row(r, kl) * kAttnLd + il;
+            o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[0], s[r], o0, 0, 0, 0);
+            o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[32], s[r], o1, 0, 0, 0);
+        }
+    }
+    if (!active) return;
+    const float lt = l + __shfl_xor(l, 32, kWave);
+    const int qi = q0 + kAttnT * wave + il;
+    if (qi >= a.Nq) return;
+    if (kl == 0) lse[((int64_t)b * a.H + h) * a.Nq + qi] = m + logf(lt);
+    store_row<T>(out + (((int64_t)b * a.Nq + qi) * a.H + h) * kAttnD, o0, o1, 1.f / lt, nullptr, a.f, kl);
+}
+
+// ---- backward ------------------------------------------------------------------------------------------------------
+// delta[b,h,q] = sum_d dout[b,q,h,d] * out[b,q,h,d], one lane per row: ONE fma chain over d in ascending order, which
+// is bit for bit how the matrix instruction accumulates dP = dout . v in the two passes below -- where a row attends
+// to a single key (out = v exactly) dP - delta is then exactly zero, as it is in exact arithmetic.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void spf_attn_delta_kernel(const T* __restrict__ out, const T* __restrict__ dout,
+                                                                float* __restrict__ delta, int B, int H, int Nq) {
+    const int64_t rows = (int64_t)B * Nq * H, row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (row >= rows) return;
+    float acc = 0.f;
+#pragma unroll
+    for (int part = 0; part < 16; ++part) {
+        float o[4], g[4];
+        load4<T>(out + row * kAttnD + 4 * part, o);
+        load4<T>(dout + row * kAttnD + 4 * part, g);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc = fmaf(g[e], o[e], acc);
+    }
+    const int64_t bq = row / H;
+    const int h = (int)(row - bq * H);
+    const int64_t b = bq / Nq;
+    delta[(b * H + h) * Nq + (bq - b * Nq)] = acc;
+}
+
+// dk, dv: the block owns 128 keys, walks the queries.
+template <typename T>
+__global__ __launch_bounds__(kBlock, 2) void spf_attn_dkdv_kernel(AttnArgs a, AttnGradArgs g, const T* __restrict__ dout,
+                                                               const float* __restrict__ lse,
+                                                               const float* __restrict__ delta) {
+    __shared__ float s_q[kAttnT * kAttnLd];
+    __shared__ float s_do[kAttnT * kAttnLd];
+    __shared__ float s_lse[kAttnT], s_dl[kAttnT];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, il = lane & 31, kl = lane >> 5;
+    const int b = blockIdx.z, h = blockIdx.y, k0 = blockIdx.x * kAttnOwn;
+    const T* __restrict__ qb = static_cast<const T*>(a.q) + b * a.qs[0] + h * a.qs[2];
+    const T* __restrict__ kb = static_cast<const T*>(a.k) + b * a.ks[0] + h * a.ks[2];
+    const T* __restrict__ vb = static_cast<const T*>(a.v) + b * a.vs[0] + h * a.vs[2];
+    const T* __restrict__ gb = dout + ((int64_t)b * a.Nq * a.H + h) * kAttnD;
+    const int64_t g_sn = (int64_t)a.H * kAttnD;
+    const int64_t* __restrict__ qp = a.qpos ? a.qpos + (int64_t)b * a.Nq * 2 : nullptr;
+    const int64_t* __restrict__ kp = a.kpos ? a.kpos + (int64_t)b * a.Nk * 2 : nullptr;
+    const float* __restrict__ lse_r = lse + ((int64_t)b * a.H + h) * a.Nq;
+    const float* __restrict__ dl_r = delta + ((int64_t)b * a.H + h) * a.Nq;
+
+    float kr[32], vr[32];
+    own_rows<T>(kr, kb, a.ks[1], kp, 1.f, vr, vb, a.vs[1], k0, a.Nk, s_q, s_do, a.f, tid);
+    const bool active = k0 + kAttnT * wave < a.Nk;
+
+    f16v dk0, dk1, dv0, dv1;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) dk0[e] = dk1[e] = dv0[e] = dv1[e] = 0.f;
+    Stage sq, sd;
+    float rl = INFINITY, rd = 0.f;                      // a padded query: probability 0
+    stage_load<T>(sq, qb, a.qs[1], qp, 0, a.Nq, tid);
+    stage_load<T>(sd, gb, g_sn, nullptr, 0, a.Nq, tid);
+    if (tid < kAttnT && tid < a.Nq) { rl = lse_r[tid]; rd = dl_r[tid]; }
+#pragma unroll 1
+    for (int q0 = 0; q0 < a.Nq; q0 += kAttnT) {
+        __syncthreads();
+        stage_commit(sq, s_q, qp != nullptr, a.f, a.scale, tid);
+        stage_commit(sd, s_do, false, a.f, 1.f, tid);
+        if (tid < kAttnT) { s_lse[tid] = rl; s_dl[tid] = rd; }
+        __syncthreads();
+        if (q0 + kAttnT < a.Nq) {
+            stage_load<T>(sq, qb, a.qs[1], qp, q0 + kAttnT, a.Nq, tid);
+            stage_load<T>(sd, gb, g_sn, nullptr, q0 + kAttnT, a.Nq, tid);
+            rl = INFINITY; rd = 0.f;
+            if (tid < kAttnT && q0 + kAttnT + tid < a.Nq) { rl = lse_r[q0 + kAttnT + tid]; rd = dl_r[q0 + kAttnT + tid]; }
+        }
+        if (!active) continue;
+        f16v s, dp;                                     // S, dP: rows = queries, column = this lane's key
+#pragma unroll
+        for (int e = 0; e < 16; ++e) s[e] = dp[e] = 0.f;
+#pragma unroll
+        for (int st = 0; st < 32; ++st) {
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(s_q[il * kAttnLd + 2 * st + kl], kr[st], s, 0, 0, 0);
+            dp = __builtin_amdgcn_mfma_f32_32x32x2f32(s_do[il * kAttnLd + 2 * st + kl], vr[st], dp, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = acc_row(r, kl);
+            const float p = expf(s[r] - s_lse[row]);
+            s[r] = p;
+            dp[r] = p * (dp[r] - s_dl[row]);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {                  // dV^T += dO^T P, dK^T += Qs^T dS
+            const int row = acc_row(r, kl);
+            const float* __restrict__ grow = s_do + row * kAttnLd + il;
+            const float* __restrict__ qrow = s_q + row * kAttnLd + il;
+            dv0 = __builtin_amdgcn_mfma_f32_32x32x2f32(grow[0], s[r], dv0, 0, 0, 0);
+            dv1 = __builtin_amdgcn_mfma_f32_32x32x2f32(grow[32], s[r], dv1, 0, 0, 0);
+            dk0 = __builtin_amdgcn_mfma_f32_32x32x2f32(qrow[0], dp[r], dk0, 0, 0, 0);
+            dk1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qrow[32], dp[r], dk1, 0, 0, 0);
+        }
+    }
+    if (!active) return;
+    const int key = k0 + kAttnT * wave + il;
+    if (key >= a.Nk) return;
+    store_row<T>(static_cast<T*>(g.dv) + b * g.dvs[0] + (int64_t)key * g.dvs[1] + h * g.dvs[2], dv0, dv1, 1.f, nullptr, a.f, kl);
+    store_row<T>(static_cast<T*>(g.dk) + b * g.dks[0] + (int64_t)key * g.dks[1] + h * g.dks[2], dk0, dk1, 1.f,
+                 kp ? kp + (int64_t)key * 2 : nullptr, a.f, kl);
+}
+
+// dq: the block owns 128 queries, walks the keys.  It also settles the row term.  `delta` comes in as sum_d dout * out
+// (delta~), whose rounding is independent of the roundings of the recomputed dP[j]; where a row's probability sits on few
+// keys with large |k|, p (dP - delta~) then keeps an error that sum_j p[j] (dP[j] - delta) k[j] would cancel.  So the pass
+// accumulates c = sum_j p[j] (dP[j] - delta~) (tiny: the residual of delta~) and B = sum_j p[j] k[j] next to
+// A = sum_j p[j] (dP[j] - delta~) k[j], returns dq = scale (A - c B) -- the gradient with delta = sum_j p[j] dP[j], the
+// softmax backward's own row sum -- and writes delta~ + c back for the dk/dv pass, which recomputes the same dP bits.
+template <typename T>
+__global__ __launch_bounds__(kBlock, 2) void spf_attn_dq_kernel(AttnArgs a, AttnGradArgs g, const T* __restrict__ dout,
+                                                             const float* __restrict__ lse,
+                                                             float* __restrict__ delta) {
+    __shared__ float s_k[kAttnT * kAttnLd];
+    __shared__ float s_v[kAttnT * kAttnLd];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, il = lane & 31, kl = lane >> 5;
+    const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * kAttnOwn;
+    const T* __restrict__ qb = static_cast<const T*>(a.q) + b * a.qs[0] + h * a.qs[2];
+    const T* __restrict__ kb = static_cast<const T*>(a.k) + b * a.ks[0] + h * a.ks[2];
+    const T* __restrict__ vb = static_cast<const T*>(a.v) + b * a.vs[0] + h * a.vs[2];
+    const T* __restrict__ gb = dout + ((int64_t)b * a.Nq * a.H + h) * kAttnD;
+    const int64_t* __restrict__ qp = a.qpos ? a.qpos + (int64_t)b * a.Nq * 2 : nullptr;
+    const int64_t* __restrict__ kp = a.kpos ? a.kpos + (int64_t)b * a.Nk * 2 : nullptr;
+
+    float qr[32], gr[32];
+    own_rows<T>(qr, qb, a.qs[1], qp, a.scale, gr, gb, (int64_t)a.H * kAttnD, q0, a.Nq, s_k, s_v, a.f, tid);
+    const bool active = q0 + kAttnT * wave < a.Nq;
+    const int qi = q0 + kAttnT * wave + il;
+    float my_lse = INFINITY, my_dl = 0.f;
+    if (qi < a.Nq) {
+        my_lse = lse[((int64_t)b * a.H + h) * a.Nq + qi];
+        my_dl = delta[((int64_t)b * a.H + h) * a.Nq + qi];
+    }
+
+    f16v dq0, dq1, pk0, pk1;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) dq0[e] = dq1[e] = pk0[e] = pk1[e] = 0.f;
+    float cres = 0.f;
+    Stage sk, sv;
+    stage_load<T>(sk, kb, a.ks[1], kp, 0, a.Nk, tid);
+    stage_load<T>(sv, vb, a.vs[1], nullptr, 0, a.Nk, tid);
+#pragma unroll 1
+    for (int k0 = 0; k0 < a.Nk; k0 += kAttnT) {
+        __syncthreads();
+        stage_commit(sk, s_k, kp != nullptr, a.f, 1.f, tid);
+        stage_commit(sv, s_v, false, a.f, 1.f, tid);
+        __syncthreads();
+        if (k0 + kAttnT < a.Nk) {
+            stage_load<T>(sk, kb, a.ks[1], kp, k0 + kAttnT, a.Nk, tid);
+            stage_load<T>(sv, vb, a.vs[1], nullptr, k0 + kAttnT, a.Nk, tid);
+        }
+        if (!active) continue;
+        f16v s, dp;                                     // S^T, dP^T: rows = keys, column = this lane's query
+#pragma unroll
+        for (int e = 0; e < 16; ++e) s[e] = dp[e] = 0.f;
+#pragma unroll
+        for (int st = 0; st < 32; ++st) {
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(s_k[il * kAttnLd + 2 * st + kl], qr[st], s, 0, 0, 0);
+            dp = __builtin_amdgcn_mfma_f32_32x32x2f32(s_v[il * kAttnLd + 2 * st + kl], gr[st], dp, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float p = expf(s[r] - my_lse);
+            if (k0 + acc_row(r, kl) >= a.Nk) p = 0.f;   // padded keys
+            s[r] = p;
+            dp[r] = p * (dp[r] - my_dl);
+            cres += dp[r];
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {                  // A^T += Kr^T dS^T, B^T += Kr^T P^T
+            const float* __restrict__ krow = s_k + acc_row(r, kl) * kAttnLd + il;
+            const float k0v = krow[0], k1v = krow[32];
+            dq0 = __builtin_amdgcn_mfma_f32_32x32x2f32(k0v, dp[r], dq0, 0, 0, 0);
+            dq1 = __builtin_amdgcn_mfma_f32_32x32x2f32(k1v, dp[r], dq1, 0, 0, 0);
+            pk0 = __builtin_amdgcn_mfma_f32_32x32x2f32(k0v, s[r], pk0, 0, 0, 0);
+            pk1 = __builtin_amdgcn_mfma_f32_32x32x2f32(k1v, s[r], pk1, 0, 0, 0);
+        }
+    }
+    if (!active) return;
+    const float c = cres + __shfl_xor(cres, 32, kWave);
+    if (qi >= a.Nq) return;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        dq0[e] = fmaf(-c, pk0[e], dq0[e]);
+        dq1[e] = fmaf(-c, pk1[e], dq1[e]);
+    }
+    if (kl == 0) delta[((int64_t)b * a.H + h) * a.Nq + qi] = my_dl + c;
+    store_row<T>(static_cast<T*>(g.dq) + b * g.dqs[0] + (int64_t)qi * g.dqs[1] + h * g.dqs[2], dq0, dq1, a.scale,
+                 qp ? qp + (int64_t)qi * 2 : nullptr, a.f, kl);
+}
+
+AttnArgs make_args(const SpfAttn& p) {
+    AttnArgs a;
+    a.q = p.q; a.k = p.k; a.v = p.v;
+    a.qpos = p.qpos; a.kpos = p.kpos;
+    for (int i = 0; i < 3; ++i) { a.qs[i] = p.q_stride[i]; a.ks[i] = p.k_stride[i]; a.vs[i] = p.v_stride[i]; }
+    a.B = p.B; a.H = p.H; a.Nq = p.Nq; a.Nk = p.Nk;
+    a.scale = p.scale;
+    a.f = rope_freq(kAttnD, p.base, p.F0);
+    return a;
+}
+
+template <typename T>
+hipError_t attn_forward_t(const SpfAttn& p, void* out, float* lse, hipStream_t stream) {
+    const dim3 grid((p.Nq + kAttnOwn - 1) / kAttnOwn, p.H, p.B);
+    spf_attn_fwd_kernel<T><<<grid, kBlock, 0, stream>>>(make_args(p), static_cast<T*>(out), lse);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t attn_backward_t(const SpfAttn& p, const SpfAttnGrads& gr, const void* out, const float* lse, const void* dout,
+                           hipStream_t stream) {
+    const AttnArgs a = make_args(p);
+    AttnGradArgs g;
+    g.dq = gr.dq; g.dk = gr.dk; g.dv = gr.dv;
+    for (int i = 0; i < 3; ++i) { g.dqs[i] = gr.dq_stride[i]; g.dks[i] = gr.dk_stride[i]; g.dvs[i] = gr.dv_stride[i]; }
+    const int64_t rows = (int64_t)p.B * p.Nq * p.H;
+    spf_attn_delta_kernel<T><<<(unsigned)((rows + kBlock - 1) / kBlock), kBlock, 0, stream>>>(
+        static_cast<const T*>(out), static_cast<const T*>(dout), gr.delta, p.B, p.H, p.Nq);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    spf_attn_dq_kernel<T><<<dim3((p.Nq + kAttnOwn - 1) / kAttnOwn, p.H, p.B), kBlock, 0, stream>>>(
+        a, g, static_cast<const T*>(dout), lse, gr.delta);                  // (settles delta: before the dk/dv pass)
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    spf_attn_dkdv_kernel<T><<<dim3((p.Nk + kAttnOwn - 1) / kAttnOwn, p.H, p.B), kBlock, 0, stream>>>(
+        a, g, static_cast<const T*>(dout), lse, gr.delta);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_attn_forward(const SpfAttn& p, void* out, float* lse, hipStream_t stream) {
+    switch (p.dtype) {
+        case 0: return attn_forward_t<float>(p, out, lse, stream);
+        case 1: return attn_forward_t<__half>(p, out, lse, stream);
+        default: return attn_forward_t<__hip_bfloat16>(p, out, lse, stream);
+    }
+}
+
+hipError_t launch_attn_backward(const SpfAttn& p, const SpfAttnGrads& g, const void* out, const float* lse,
+                                const void* dout, hipStream_t stream) {
+    switch (p.dtype) {
+        case 0: return attn_backward_t<float>(p, g, out, lse, dout, stream);
+        case 1: return attn_backward_t<__half>(p, g, out, lse, dout, stream);
+        default: return attn_backward_t<__hip_bfloat16>(p, g, out, lse, dout, stream);
+    }
+}
+
+}  // namespace spf

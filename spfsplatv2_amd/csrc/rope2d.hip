@@ -11,27 +11,9 @@
 // then the half, so a group of lanes covers whole contiguous head rows.  The Q inverse frequencies are computed
 // on the host with libm powf (exactly what the reference's CPU path evaluates,
 // curope/curope.cpp:35) and travel in the kernel-argument segment -- no device powf, no table in HBM.
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
-
-#include "spf_common.h"
+#include "rope_math.h"
 
 namespace spf {
-
-struct RopeFreq {
-    float inv[64];  // fwd / base^(q/Q), q < Q <= 64
-};
-
-template <typename T>
-__device__ __forceinline__ float to_f(T v);
-template <> __device__ __forceinline__ float to_f<float>(float v) { return v; }
-template <> __device__ __forceinline__ float to_f<__half>(__half v) { return __half2float(v); }
-template <> __device__ __forceinline__ float to_f<__hip_bfloat16>(__hip_bfloat16 v) { return __bfloat162float(v); }
-template <typename T>
-__device__ __forceinline__ T from_f(float v);
-template <> __device__ __forceinline__ float from_f<float>(float v) { return v; }
-template <> __device__ __forceinline__ __half from_f<__half>(float v) { return __float2half(v); }
-template <> __device__ __forceinline__ __hip_bfloat16 from_f<__hip_bfloat16>(float v) { return __float2bfloat16(v); }
 
 // 16 bytes per lane whatever the type: 4 floats, 8 halves / bfloat16s.
 template <typename T> struct Wide;
@@ -62,29 +44,6 @@ template <typename H> struct WideHalf {
 };
 template <> struct Wide<__half> : WideHalf<__half> {};
 template <> struct Wide<__hip_bfloat16> : WideHalf<__hip_bfloat16> {};
-
-// sin and cos of a rotation angle: Cody-Waite reduction by pi/2 in three fused steps (pi/2 = hi + mid + lo to ~72 bits;
-// the fma keeps each partial product exact, so the reduced argument is good to half an ulp for |k| < 2^15) and the
-// cephes minimax polynomials on [-pi/4, pi/4]: max abs error 8.9e-8 against float64 over positions 0..30000 x every
-// frequency (checked on the CPU with emulated float32 fmas) -- the libm sincosf this replaces is good to 1 ulp too, at
-// three times the instructions (its Payne-Hanek path for huge arguments is kept for exactly those).  The angle's
-// evaluation was what made the half types compute-bound.
-__device__ __forceinline__ void rope_sincos(float x, float& s, float& c) {
-    if (!(fabsf(x) < 30000.f)) { sincosf(x, &s, &c); return; }           // (huge positions, inf, nan: libm)
-    const float kf = rintf(x * 0.63661977236758134f);
-    float r = fmaf(-kf, 1.5707963705062866f, x);
-    r = fmaf(-kf, -4.371138828673793e-08f, r);
-    r = fmaf(-kf, -1.7763568394002505e-15f, r);
-    const float z = r * r;
-    const float ps = fmaf(fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f);
-    const float sr = fmaf(ps * z, r, r);
-    const float pc = fmaf(fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f);
-    const float cr = fmaf(pc * z, z, fmaf(-0.5f, z, 1.0f));
-    const int k = (int)kf;
-    const float a = (k & 1) ? cr : sr, b = (k & 1) ? sr : cr;            // quadrant: (s, c) = (sr, cr), (cr, -sr), (-sr, -cr), (-cr, sr)
-    s = (k & 2) ? -a : a;
-    c = ((k + 1) & 2) ? -b : b;
-}
 
 // Vector path.  One lane owns EPL = 16 bytes / sizeof(T) consecutive frequencies of one (token, half) and walks HEADS
 // heads with them: the rotation angle depends on (token, half, frequency) only, so it is evaluated once per HEADS head
@@ -223,9 +182,7 @@ static hipError_t launch_rope_t(void* tokens, void* tokens2, const int64_t* pos,
 
 hipError_t launch_rope2d(void* tokens, void* tokens2, const int64_t* pos, int B, int N, int H, int D, int64_t sb,
                          int64_t sn, int64_t sh, int pos_div, int dtype, float base, float fwd, hipStream_t stream) {
-    RopeFreq f;
-    const int Q = D / 4;
-    for (int q = 0; q < 64; ++q) f.inv[q] = q < Q ? fwd / powf(base, q / float(Q)) : 0.f;
+    const RopeFreq f = rope_freq(D, base, fwd);
     switch (dtype) {
         case 0: return launch_rope_t<float>(tokens, tokens2, pos, B, N, H, D, sb, sn, sh, pos_div, f, stream);
         case 1: return launch_rope_t<__half>(tokens, tokens2, pos, B, N, H, D, sb, sn, sh, pos_div, f, stream);
