@@ -59,7 +59,9 @@ extern "C" {
                               existing struct, signature or meaning moved, so a caller built against 7 still fits.
                               The same holds for the pose path (spf_pose_compose_*, spf_depth_project_*, spf_pose_error,
                               spf_focal_*): eight entry points added, nothing moved; spf_raster_state_layout likewise; and for the
-                              fused attention (SpfAttn, SpfAttnGrads, spf_attn_forward, spf_attn_backward) */
+                              fused attention (SpfAttn, SpfAttnGrads, spf_attn_forward, spf_attn_backward) and its
+                              mask / q-k-LayerNorm extras (SpfAttnExt, spf_attn_forward_ext, spf_attn_backward_ext,
+                              spf_attn_ext_scratch_floats) */
 
 #define SPF_OK 0
 #define SPF_E_INVALID (-1)   /* bad argument (null pointer, size, unsupported degree ...) */
@@ -699,6 +701,43 @@ int spf_attn_forward(const SpfAttn* args, void* out, float* lse, void* stream);
 /* out, lse: what the forward wrote; dout [B,Nq,H*64] contiguous.  No atomics: bitwise reproducible. */
 int spf_attn_backward(const SpfAttn* args, const SpfAttnGrads* grads, const void* out, const float* lse,
                       const void* dout, void* stream);
+
+/* The same attention with the two things vggt/layers/attention.py adds (an additive family: SpfAttn, SpfAttnGrads and
+ * the two entry points above do not move):
+ *   score = scale * R(qpos) LN_q(q) * (R(kpos) LN_k(k))^T + mask[b,h,q,k]
+ * mask (null: none): read in place through four element strides (batch, head, query, key); a stride of 0 broadcasts
+ * that axis, the key stride must be 1, nothing else about its alignment is assumed.  mask_dtype 0: float32, added to
+ * the score (-inf excludes a key); 1: bool / uint8, nonzero = the key takes part, zero = -inf.  A row whose keys are
+ * all excluded gives out = 0 and lse = -inf and contributes exactly zero to every gradient.  The mask has no gradient.
+ * q_weight, q_bias, k_weight, k_bias (all four or none): float32[64] each, LayerNorm over the 64 elements of every q
+ * and every k row with `eps` (biased variance, float32, two passes), applied while the row is staged, before the
+ * rotation; q and k are never written back normalised.
+ * Backward only: dq_weight, dq_bias, dk_weight, dk_bias float32[64] each (written, not accumulated) and `partials`,
+ * spf_attn_ext_scratch_floats(B, H, Nq, Nk) floats of scratch: every block writes its rows' sums there and one small
+ * kernel adds them in block order in double -- no atomics, bitwise reproducible.  dq and dk are the gradients of the
+ * rows BEFORE the normalisation. */
+typedef struct SpfAttnExt {
+    const void* mask;
+    int32_t mask_dtype;
+    int64_t mask_stride[4];
+    const float* q_weight;
+    const float* q_bias;
+    const float* k_weight;
+    const float* k_bias;
+    float eps;
+    float* dq_weight;
+    float* dq_bias;
+    float* dk_weight;
+    float* dk_bias;
+    float* partials;
+} SpfAttnExt;
+/* Floats of SpfAttnExt.partials for a backward call of these sizes (-1: invalid sizes). */
+int64_t spf_attn_ext_scratch_floats(int32_t B, int32_t H, int32_t Nq, int32_t Nk);
+/* spf_attn_forward / spf_attn_backward with the extras; ext without a mask and without norm parameters is the plain
+ * call.  Argument errors return SPF_E_INVALID before anything is launched. */
+int spf_attn_forward_ext(const SpfAttn* args, const SpfAttnExt* ext, void* out, float* lse, void* stream);
+int spf_attn_backward_ext(const SpfAttn* args, const SpfAttnGrads* grads, const SpfAttnExt* ext, const void* out,
+                          const float* lse, const void* dout, void* stream);
 
 /* Per-stage device timing with HIP events recorded on the launch stream around every kernel
  * stage.  spf_stage_timing_enable(mask) clears the log and starts recording the stages whose bit

@@ -94,6 +94,13 @@ class SpfAttnGrads(C.Structure):
                 ("dk_stride", C.c_int64 * 3), ("dv_stride", C.c_int64 * 3), ("delta", C.c_void_p)]
 
 
+class SpfAttnExt(C.Structure):
+    _fields_ = [("mask", C.c_void_p), ("mask_dtype", C.c_int32), ("mask_stride", C.c_int64 * 4),
+                ("q_weight", C.c_void_p), ("q_bias", C.c_void_p), ("k_weight", C.c_void_p), ("k_bias", C.c_void_p),
+                ("eps", C.c_float), ("dq_weight", C.c_void_p), ("dq_bias", C.c_void_p), ("dk_weight", C.c_void_p),
+                ("dk_bias", C.c_void_p), ("partials", C.c_void_p)]
+
+
 # Every symbol include/spfsplat_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "spf_abi_version": (C.c_int, []),
@@ -184,6 +191,10 @@ SYMBOLS = {
     "spf_attn_forward": (C.c_int, [C.POINTER(SpfAttn), C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_attn_backward": (C.c_int, [C.POINTER(SpfAttn), C.POINTER(SpfAttnGrads),
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_attn_ext_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "spf_attn_forward_ext": (C.c_int, [C.POINTER(SpfAttn), C.POINTER(SpfAttnExt), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_attn_backward_ext": (C.c_int, [C.POINTER(SpfAttn), C.POINTER(SpfAttnGrads), C.POINTER(SpfAttnExt),
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_stage_timing_enable": (C.c_int, [C.c_int32]),
     "spf_stage_timing_sample_every": (C.c_int, [C.c_int32]),
     "spf_stage_times_ms": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_int32)]),

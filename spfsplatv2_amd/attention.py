@@ -11,8 +11,13 @@ here                       reference (src/model/encoder/backbone/croco/blocks.py
 =========================  ============================================================================
 
 One kernel per direction of the data flow (csrc/attention.hip): the score matrix never exists in memory, q and k are
-rotated while they are staged, strided views are read in place.  Head dim 64 only; no mask, no dropout on the
-probabilities, no CPU path -- each of these raises before anything is launched.
+rotated while they are staged, strided views are read in place.  Head dim 64 only; no dropout on the probabilities, no
+CPU path -- each of these raises before anything is launched.
+
+``rope_attention`` and ``rope_attention_packed`` take two keyword-only extras, which the VGGT backbone needs
+(vggt_attention.py) and CroCo's two classes here do not use: ``mask`` (additive float32 or bool, broadcast to
+[B,H,Nq,Nk], read in place) and ``q_norm`` / ``k_norm`` (``(weight, bias, eps)`` of a LayerNorm over the 64 elements of
+every q / k row, applied before the rotation).  With all three None the launch is the one it always was.
 """
 from __future__ import annotations
 
@@ -55,7 +60,39 @@ def _check_positions(tokens: torch.Tensor, positions: torch.Tensor) -> None:
         raise RuntimeError("positions must be int64")
 
 
-def _check(q, k, v, qpos, kpos) -> None:
+def _check_mask(mask, shape) -> None:
+    """What can be said about a mask without touching it; ``shape`` = (B, H, Nq, Nk)."""
+    if not isinstance(mask, torch.Tensor):
+        raise TypeError(f"rope_attention: mask must be a tensor or None, got {type(mask).__name__}")
+    if mask.dtype not in (torch.float32, torch.bool):
+        raise RuntimeError(f"rope_attention: mask must be float32 (additive) or bool, got {mask.dtype}")
+    if mask.requires_grad:
+        raise RuntimeError("rope_attention: the mask is not differentiable (it requires grad)")
+    if not 2 <= mask.dim() <= 4:
+        raise RuntimeError(f"rope_attention: mask must have 2 to 4 dimensions, got {mask.dim()}")
+    full = (1,) * (4 - mask.dim()) + tuple(mask.shape)
+    if any(m != 1 and m != n for m, n in zip(full, shape)):
+        raise RuntimeError(f"rope_attention: mask of shape {tuple(mask.shape)} does not broadcast to [B,H,Nq,Nk] = "
+                           f"{list(shape)}")
+
+
+def _check_norms(q_norm, k_norm) -> None:
+    if (q_norm is None) != (k_norm is None):
+        raise RuntimeError("rope_attention: q_norm and k_norm must both be given or both be None")
+    if q_norm is None:
+        return
+    for name, n in (("q_norm", q_norm), ("k_norm", k_norm)):
+        if not (isinstance(n, (tuple, list)) and len(n) == 3):
+            raise TypeError(f"rope_attention: {name} must be (weight, bias, eps)")
+        for t in n[:2]:
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != (HEAD_DIM,) or t.dtype != torch.float32:
+                raise RuntimeError(f"rope_attention: {name}'s weight and bias must be float32 tensors of shape "
+                                   f"[{HEAD_DIM}]")
+    if float(q_norm[2]) != float(k_norm[2]):
+        raise ValueError("rope_attention: q_norm and k_norm must share one eps")
+
+
+def _check(q, k, v, qpos, kpos, mask=None, q_norm=None, k_norm=None) -> None:
     for t in (q, k, v):
         _check_tokens(t)
     if not (q.dtype == k.dtype == v.dtype):
@@ -69,9 +106,15 @@ def _check(q, k, v, qpos, kpos) -> None:
     if qpos is not None:
         _check_positions(q, qpos)
         _check_positions(k, kpos)
+    if mask is not None:
+        _check_mask(mask, (q.shape[0], q.shape[1], q.shape[2], k.shape[2]))
+    _check_norms(q_norm, k_norm)
     if not q.is_cuda:
         raise RuntimeError("rope_attention: q, k and v are on the CPU; this build only runs on a HIP device "
                            "(no CPU fallback)")
+    extras = ([mask] if mask is not None else []) + (list(q_norm[:2]) + list(k_norm[:2]) if q_norm is not None else [])
+    if any(t.device != q.device for t in extras):
+        raise RuntimeError("rope_attention: the mask and the norm parameters must be on the tokens' device")
 
 
 def _rows(t: torch.Tensor) -> torch.Tensor:
@@ -99,9 +142,40 @@ def _args(q, k, v, qpos, kpos, base, F0, scale) -> _lib.SpfAttn:
     return a
 
 
-def attention_forward(q, k, v, qpos, kpos, base, F0, scale):
+def _mask_view(mask, shape):
+    """The mask as a [B,H,Nq,Nk] view the kernels read in place: broadcast axes get stride 0; the key axis must have
+    stride 1, so a mask that is strided or broadcast along it is copied once (as ``_rows`` does for tokens)."""
+    if mask is None:
+        return None
+    m = mask.reshape((1,) * (4 - mask.dim()) + tuple(mask.shape))
+    if shape[3] > 1 and (m.shape[3] == 1 or m.stride(3) != 1):
+        m = m.expand(*m.shape[:3], shape[3]).contiguous()
+    return m.expand(shape)
+
+
+def _ext(mask, q_norm, k_norm, dnorm=None, partials=None) -> _lib.SpfAttnExt:
+    """SpfAttnExt of a call; ``mask``: what ``_mask_view`` returned; ``dnorm`` [4,64] float32 and ``partials``: the
+    backward's outputs and scratch."""
+    e = _lib.SpfAttnExt()
+    if mask is not None:
+        e.mask, e.mask_dtype = mask.data_ptr(), int(mask.dtype == torch.bool)
+        e.mask_stride = (C.c_int64 * 4)(mask.stride(0), mask.stride(1), mask.stride(2), 1)
+    if q_norm is not None:
+        e.q_weight, e.q_bias, e.k_weight, e.k_bias = (t.data_ptr() for t in (*q_norm[:2], *k_norm[:2]))
+        e.eps = float(q_norm[2])
+    if dnorm is not None:
+        e.dq_weight, e.dq_bias, e.dk_weight, e.dk_bias = (dnorm[i].data_ptr() for i in range(4))
+        e.partials = partials.data_ptr()
+    return e
+
+
+def _norm_tensors(n):
+    return None if n is None else (n[0].detach().contiguous(), n[1].detach().contiguous(), float(n[2]))
+
+
+def attention_forward(q, k, v, qpos, kpos, base, F0, scale, *, mask=None, q_norm=None, k_norm=None):
     """The forward launch: (out [B,Nq,H*D], lse [B,H,Nq] float32).  q, k, v: [B,H,N,64] views, read in place."""
-    _check(q, k, v, qpos, kpos)
+    _check(q, k, v, qpos, kpos, mask, q_norm, k_norm)
     q, k, v = _rows(q), _rows(k), _rows(v)
     B, H, Nq, D = q.shape
     out = torch.empty(B, Nq, H * D, dtype=q.dtype, device=q.device)
@@ -110,15 +184,24 @@ def attention_forward(q, k, v, qpos, kpos, base, F0, scale):
     with torch.cuda.device(q.device):
         stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
         a = _args(q, k, v, qpos, kpos, base, F0, scale)
-        _lib.check(lib.spf_attn_forward(C.byref(a), C.c_void_p(out.data_ptr()), C.c_void_p(lse.data_ptr()), stream),
-                   "spf_attn_forward")
+        if mask is None and q_norm is None:
+            _lib.check(lib.spf_attn_forward(C.byref(a), C.c_void_p(out.data_ptr()), C.c_void_p(lse.data_ptr()), stream),
+                       "spf_attn_forward")
+        else:
+            mask = _mask_view(mask, (B, H, Nq, k.shape[2]))
+            q_norm, k_norm = _norm_tensors(q_norm), _norm_tensors(k_norm)
+            e = _ext(mask, q_norm, k_norm)
+            _lib.check(lib.spf_attn_forward_ext(C.byref(a), C.byref(e), C.c_void_p(out.data_ptr()),
+                                                C.c_void_p(lse.data_ptr()), stream), "spf_attn_forward_ext")
     return out, lse
 
 
-def attention_backward(q, k, v, qpos, kpos, base, F0, scale, out, lse, dout, dq, dk, dv) -> None:
+def attention_backward(q, k, v, qpos, kpos, base, F0, scale, out, lse, dout, dq, dk, dv, *, mask=None, q_norm=None,
+                       k_norm=None):
     """The backward launches: writes dq [B,H,Nq,64], dk, dv [B,H,Nk,64] (any views with 16-byte aligned rows, e.g. the
-    three slices of one packed gradient) from what the forward saved."""
-    _check(q, k, v, qpos, kpos)
+    three slices of one packed gradient) from what the forward saved.  With q_norm / k_norm it returns the gradients of
+    the four norm parameters as one [4,64] float32 tensor (q weight, q bias, k weight, k bias), else None."""
+    _check(q, k, v, qpos, kpos, mask, q_norm, k_norm)
     q, k, v = _rows(q), _rows(k), _rows(v)
     out, dout = out.contiguous(), dout.contiguous()
     if dout.dtype != q.dtype or out.dtype != q.dtype:
@@ -132,8 +215,25 @@ def attention_backward(q, k, v, qpos, kpos, base, F0, scale, out, lse, dout, dq,
         g = _lib.SpfAttnGrads()
         g.dq, g.dk, g.dv, g.delta = dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr()
         g.dq_stride, g.dk_stride, g.dv_stride = _strides(dq), _strides(dk), _strides(dv)
-        _lib.check(lib.spf_attn_backward(C.byref(a), C.byref(g), C.c_void_p(out.data_ptr()), C.c_void_p(lse.data_ptr()),
-                                         C.c_void_p(dout.data_ptr()), stream), "spf_attn_backward")
+        if mask is None and q_norm is None:
+            _lib.check(lib.spf_attn_backward(C.byref(a), C.byref(g), C.c_void_p(out.data_ptr()),
+                                             C.c_void_p(lse.data_ptr()), C.c_void_p(dout.data_ptr()), stream),
+                       "spf_attn_backward")
+            return None
+        mask = _mask_view(mask, (B, H, Nq, k.shape[2]))
+        q_norm, k_norm = _norm_tensors(q_norm), _norm_tensors(k_norm)
+        dnorm = partials = None
+        if q_norm is not None:
+            n = lib.spf_attn_ext_scratch_floats(B, H, Nq, k.shape[2])       # (the library's grid arithmetic, not ours)
+            if n < 0:
+                raise _lib.SpfError("spf_attn_ext_scratch_floats rejected the sizes")
+            dnorm = torch.empty(4, HEAD_DIM, dtype=torch.float32, device=q.device)
+            partials = torch.empty(n, dtype=torch.float32, device=q.device)
+        e = _ext(mask, q_norm, k_norm, dnorm, partials)
+        _lib.check(lib.spf_attn_backward_ext(C.byref(a), C.byref(g), C.byref(e), C.c_void_p(out.data_ptr()),
+                                             C.c_void_p(lse.data_ptr()), C.c_void_p(dout.data_ptr()), stream),
+                   "spf_attn_backward_ext")
+        return dnorm
 
 
 class _RopeAttention(torch.autograd.Function):
@@ -180,36 +280,117 @@ class _RopeAttentionPacked(torch.autograd.Function):
         return dqkv, None, None, None, None
 
 
+def _norm_args(q_norm, k_norm):
+    """The autograd functions' flat arguments of the two norms: (q weight, q bias, k weight, k bias, eps)."""
+    if q_norm is None:
+        return None, None, None, None, 0.0
+    return q_norm[0], q_norm[1], k_norm[0], k_norm[1], float(q_norm[2])
+
+
+def _norm_grads(ctx, first, dnorm):
+    """Gradients of the four norm parameters at needs_input_grad[first:first + 4]."""
+    if dnorm is None:
+        return (None,) * 4
+    return tuple(dnorm[i] if ctx.needs_input_grad[first + i] else None for i in range(4))
+
+
+class _RopeAttentionExt(torch.autograd.Function):
+    """_RopeAttention with a mask, the q / k LayerNorm or both (the flagged kernels)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, qpos, kpos, mask, qw, qb, kw, kb, eps, base, F0, scale):
+        norms = ((qw, qb, eps), (kw, kb, eps)) if qw is not None else (None, None)
+        out, lse = attention_forward(q, k, v, qpos, kpos, base, F0, scale, mask=mask, q_norm=norms[0], k_norm=norms[1])
+        ctx.save_for_backward(q, k, v, qpos, kpos, mask, qw, qb, kw, kb, out, lse)
+        ctx.cfg = (base, F0, scale)
+        ctx.eps = eps
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        q, k, v, qpos, kpos, mask, qw, qb, kw, kb, out, lse = ctx.saved_tensors
+        norms = ((qw, qb, ctx.eps), (kw, kb, ctx.eps)) if qw is not None else (None, None)
+        B, H, Nq, D = q.shape
+        Nk = k.shape[2]
+        dq = torch.empty(B, Nq, H, D, dtype=q.dtype, device=q.device).transpose(1, 2)
+        dk = torch.empty(B, Nk, H, D, dtype=q.dtype, device=q.device).transpose(1, 2)
+        dv = torch.empty(B, Nk, H, D, dtype=q.dtype, device=q.device).transpose(1, 2)
+        dnorm = attention_backward(q, k, v, qpos, kpos, *ctx.cfg, out, lse, dout, dq, dk, dv, mask=mask, q_norm=norms[0],
+                                   k_norm=norms[1])
+        need = ctx.needs_input_grad
+        return (dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None, None,
+                *_norm_grads(ctx, 6, dnorm), None, None, None, None)
+
+
+class _RopeAttentionPackedExt(torch.autograd.Function):
+    """_RopeAttentionPacked with a mask, the q / k LayerNorm or both."""
+
+    @staticmethod
+    def forward(ctx, qkv, pos, mask, qw, qb, kw, kb, eps, base, F0, scale):
+        q, k, v = _views(qkv)
+        norms = ((qw, qb, eps), (kw, kb, eps)) if qw is not None else (None, None)
+        out, lse = attention_forward(q, k, v, pos, pos, base, F0, scale, mask=mask, q_norm=norms[0], k_norm=norms[1])
+        ctx.save_for_backward(qkv, pos, mask, qw, qb, kw, kb, out, lse)
+        ctx.cfg = (base, F0, scale)
+        ctx.eps = eps
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        qkv, pos, mask, qw, qb, kw, kb, out, lse = ctx.saved_tensors
+        norms = ((qw, qb, ctx.eps), (kw, kb, ctx.eps)) if qw is not None else (None, None)
+        q, k, v = _views(qkv)
+        dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
+        dq, dk, dv = _views(dqkv)
+        dnorm = attention_backward(q, k, v, pos, pos, *ctx.cfg, out, lse, dout, dq, dk, dv, mask=mask, q_norm=norms[0],
+                                   k_norm=norms[1])
+        return (dqkv, None, None, *_norm_grads(ctx, 3, dnorm), None, None, None, None)
+
+
 def _views(qkv: torch.Tensor):
     """q, k, v [B,H,N,D] of a packed [B,N,3,H,D] buffer (blocks.py:97-98)."""
     t = qkv.transpose(1, 3)
     return t[:, :, 0], t[:, :, 1], t[:, :, 2]
 
 
-def rope_attention(q, k, v, qpos=None, kpos=None, *, base: float = 100.0, F0: float = 1.0, scale=None):
-    """softmax(scale * rope(q, qpos) @ rope(k, kpos)^T) @ v, returned as [B,Nq,H*D].
+def rope_attention(q, k, v, qpos=None, kpos=None, *, base: float = 100.0, F0: float = 1.0, scale=None, mask=None,
+                   q_norm=None, k_norm=None):
+    """softmax(scale * rope(norm(q), qpos) @ rope(norm(k), kpos)^T + mask) @ v, returned as [B,Nq,H*D].
 
     q [B,H,Nq,64], k and v [B,H,Nk,64]: any views with unit stride along D and 16-byte aligned rows are read in place
     (anything else is copied first).  qpos [B,Nq,2], kpos [B,Nk,2]: int64 (y, x), contiguous; both None: no rotation.
+    mask: float32 (added to the scaled score; -inf excludes a key) or bool (True: the key takes part), 2 to 4
+    dimensions broadcast to [B,H,Nq,Nk] and read in place (broadcast axes cost nothing); no gradient.  A row with
+    every key excluded returns zeros and has zero gradients.  q_norm, k_norm: ``(weight, bias, eps)`` of a LayerNorm
+    over the 64 elements of every row, float32 [64] each, both or neither; their gradients come out of the backward.
     """
-    _check(q, k, v, qpos, kpos)
+    _check(q, k, v, qpos, kpos, mask, q_norm, k_norm)
     if scale is None:
         scale = q.shape[3] ** -0.5
-    return _RopeAttention.apply(q, k, v, qpos, kpos, float(base), float(F0), float(scale))
+    if mask is None and q_norm is None:
+        return _RopeAttention.apply(q, k, v, qpos, kpos, float(base), float(F0), float(scale))
+    return _RopeAttentionExt.apply(q, k, v, qpos, kpos, mask, *_norm_args(q_norm, k_norm), float(base), float(F0),
+                                   float(scale))
 
 
-def rope_attention_packed(qkv, pos=None, *, base: float = 100.0, F0: float = 1.0, scale=None):
+def rope_attention_packed(qkv, pos=None, *, base: float = 100.0, F0: float = 1.0, scale=None, mask=None, q_norm=None,
+                          k_norm=None):
     """Self-attention on a packed projection qkv [B,N,3,H,64] (what ``self.qkv(x).reshape(B, N, 3, H, D)`` yields):
     the same result as ``rope_attention`` on its three views, and ONE gradient of the packed shape out of the backward
-    instead of three that autograd would have to add up."""
+    instead of three that autograd would have to add up.  mask, q_norm, k_norm: as in ``rope_attention``."""
     if qkv.dim() != 5 or qkv.shape[2] != 3:
         raise RuntimeError(f"rope_attention_packed: qkv must be [B,N,3,H,D], got {tuple(qkv.shape)}")
-    _check(*_views(qkv), pos, pos)
+    _check(*_views(qkv), pos, pos, mask, q_norm, k_norm)
     if not qkv.is_contiguous():
         qkv = qkv.contiguous()
     if scale is None:
         scale = qkv.shape[4] ** -0.5
-    return _RopeAttentionPacked.apply(qkv, pos, float(base), float(F0), float(scale))
+    if mask is None and q_norm is None:
+        return _RopeAttentionPacked.apply(qkv, pos, float(base), float(F0), float(scale))
+    return _RopeAttentionPackedExt.apply(qkv, pos, mask, *_norm_args(q_norm, k_norm), float(base), float(F0),
+                                         float(scale))
 
 
 def _rope_cfg(rope):

@@ -72,6 +72,10 @@ hipError_t launch_camera_fwd_zero(const SpfCamera&, void*, uint64_t, hipStream_t
 hipError_t launch_camera_bwd_reduce(const SpfCamera&, const float*, int, float*, hipStream_t);
 hipError_t launch_attn_forward(const SpfAttn&, void*, float*, hipStream_t);
 hipError_t launch_attn_backward(const SpfAttn&, const SpfAttnGrads&, const void*, const float*, const void*, hipStream_t);
+int64_t attn_ext_scratch_floats(int, int, int, int);
+hipError_t launch_attn_forward_ext(const SpfAttn&, const SpfAttnExt&, void*, float*, hipStream_t);
+hipError_t launch_attn_backward_ext(const SpfAttn&, const SpfAttnGrads&, const SpfAttnExt&, const void*, const float*,
+                                    const void*, hipStream_t);
 hipError_t launch_rope2d(void*, void*, const int64_t*, int, int, int, int, int64_t, int64_t, int64_t, int, int, float,
                          float, hipStream_t);
 }  // namespace spf
@@ -1072,6 +1076,57 @@ int spf_attn_backward(const SpfAttn* args, const SpfAttnGrads* g, const void* ou
         !attn_rows_aligned(g->dv, g->dv_stride, es))
         return fail(SPF_E_INVALID, "attention: rows of dq, dk and dv must be 16-byte aligned");
     SPF_HIP(spf::launch_attn_backward(*args, *g, out, lse, dout, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+// the extras of an attention call: 0, or the message of the first one that is wrong
+static const char* attn_ext_error(const SpfAttnExt* e) {
+    if (!e) return "attention: ext is null";
+    if (e->mask) {
+        if (e->mask_dtype != 0 && e->mask_dtype != 1) return "attention: mask_dtype must be 0 (float32) or 1 (bool / uint8)";
+        if (e->mask_stride[3] != 1) return "attention: the mask's key stride must be 1";
+        for (int i = 0; i < 3; ++i)
+            if (e->mask_stride[i] < 0) return "attention: mask strides must not be negative";
+        if (e->mask_dtype == 0 && reinterpret_cast<uintptr_t>(e->mask) % 4 != 0) return "attention: a float32 mask must be 4-byte aligned";
+    }
+    const int given = (e->q_weight != nullptr) + (e->q_bias != nullptr) + (e->k_weight != nullptr) + (e->k_bias != nullptr);
+    if (given != 0 && given != 4) return "attention: q_weight, q_bias, k_weight and k_bias must all be given or all be null";
+    if (given == 4 && !(e->eps >= 0.f)) return "attention: eps must not be negative";
+    return nullptr;
+}
+
+int64_t spf_attn_ext_scratch_floats(int32_t B, int32_t H, int32_t Nq, int32_t Nk) {
+    if (B < 1 || H < 1 || Nq < 1 || Nk < 1 || B > 65535 || H > 65535) return -1;
+    return spf::attn_ext_scratch_floats(B, H, Nq, Nk);
+}
+
+int spf_attn_forward_ext(const SpfAttn* args, const SpfAttnExt* ext, void* out, float* lse, void* stream_) {
+    if (const char* e = attn_ext_error(ext)) return fail(SPF_E_INVALID, "%s", e);
+    if (!ext->mask && !ext->q_weight) return spf_attn_forward(args, out, lse, stream_);
+    if (const char* e = attn_args_error(args)) return fail(SPF_E_INVALID, "%s", e);
+    if (!out || !lse) return fail(SPF_E_INVALID, "attention: out / lse is null");
+    if (reinterpret_cast<uintptr_t>(out) % 16 != 0) return fail(SPF_E_INVALID, "attention: rows of out must be 16-byte aligned");
+    SPF_HIP(spf::launch_attn_forward_ext(*args, *ext, out, lse, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_attn_backward_ext(const SpfAttn* args, const SpfAttnGrads* g, const SpfAttnExt* ext, const void* out, const float* lse,
+                          const void* dout, void* stream_) {
+    if (const char* e = attn_ext_error(ext)) return fail(SPF_E_INVALID, "%s", e);
+    if (!ext->mask && !ext->q_weight) return spf_attn_backward(args, g, out, lse, dout, stream_);
+    if (const char* e = attn_args_error(args)) return fail(SPF_E_INVALID, "%s", e);
+    if (!g) return fail(SPF_E_INVALID, "attention: grads is null");
+    if (!out || !lse || !dout) return fail(SPF_E_INVALID, "attention: out / lse / dout is null");
+    if (!g->dq || !g->dk || !g->dv || !g->delta) return fail(SPF_E_INVALID, "attention: dq / dk / dv / delta is null");
+    if (ext->q_weight && (!ext->dq_weight || !ext->dq_bias || !ext->dk_weight || !ext->dk_bias || !ext->partials))
+        return fail(SPF_E_INVALID, "attention: dq_weight / dq_bias / dk_weight / dk_bias / partials is null");
+    const int es = args->dtype == 0 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(out) % 16 != 0 || reinterpret_cast<uintptr_t>(dout) % 16 != 0)
+        return fail(SPF_E_INVALID, "attention: rows of out and dout must be 16-byte aligned");
+    if (!attn_rows_aligned(g->dq, g->dq_stride, es) || !attn_rows_aligned(g->dk, g->dk_stride, es) ||
+        !attn_rows_aligned(g->dv, g->dv_stride, es))
+        return fail(SPF_E_INVALID, "attention: rows of dq, dk and dv must be 16-byte aligned");
+    SPF_HIP(spf::launch_attn_backward_ext(*args, *g, *ext, out, lse, dout, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
 

@@ -23,6 +23,12 @@
 // rows and loops over key tiles; both recompute the probabilities from the saved log-sum-exp.  The row term
 // delta = sum_d dout * out is a small pre-pass, which the dq pass (run first) refines to sum_j p dP for the dk/dv pass.
 // Every sum has a fixed order: results are bitwise reproducible.
+//
+// Two compile-time features serve vggt/layers/attention.py (template flags: without them the kernels are the code above):
+// MASK adds mask[b,h,q,k] (float32, or bool as 0 / -inf; read in place through strides) to the score, with -inf safe in
+// the online softmax and in both recomputations -- a row without any key gives out = 0, lse = -inf and zero gradients;
+// NORM applies LayerNorm(64) with weight and bias to every q and k row while it is staged, before the rotation, and its
+// backward in the epilogues of the two backward passes, with the parameter gradients summed from per-block partials.
 #include "rope_math.h"
 
 namespace spf {
@@ -48,6 +54,23 @@ struct AttnGradArgs {
     void *dq, *dk, *dv;
     int64_t dqs[3], dks[3], dvs[3];
 };
+// What the flagged instantiations read on top of AttnArgs.  MASK: score += mask[b,h,q,k], read in place through element
+// strides (0: broadcast; the key stride is 1), float32 additive or uint8 (nonzero: the key takes part, zero: -inf).
+// NORM: LayerNorm(64) with weight and bias of every q and every k row while it is staged, before the rotation.
+// The unflagged instantiations keep AttnArgs as their argument: they are the code they were.
+struct AttnExt {
+    const void* mask;
+    int64_t ms[3];                  // batch, head, query
+    int mask_bool;
+    const float *qw, *qb, *kw, *kb; // float[64] each
+    float eps;
+    float* part;                    // backward: this pass's [blocks][2][64] partial sums of (dweight, dbias)
+};
+struct AttnArgsX : AttnArgs {
+    AttnExt x;
+};
+template <bool X> struct ArgsOf { typedef AttnArgs type; };
+template <> struct ArgsOf<true> { typedef AttnArgsX type; };
 
 template <typename T> __device__ __forceinline__ void load4(const T* p, float* f);
 template <> __device__ __forceinline__ void load4<float>(const float* p, float* f) {
@@ -117,12 +140,118 @@ __device__ __forceinline__ void stage_commit(const Stage& r, float* __restrict__
 
 __device__ __forceinline__ int acc_row(int r, int kl) { return (r & 3) + 8 * (r >> 2) + 4 * kl; }
 
+// ---- NORM ----------------------------------------------------------------------------------------------------------
+// The four parameter vectors in LDS: [0] q weight, [1] q bias, [2] k weight, [3] k bias (only kernels that call this
+// carry the 1 KB).
+__device__ __forceinline__ float* norm_lds() {
+    __shared__ __attribute__((aligned(16))) float s_n[4 * kAttnD];
+    return s_n;
+}
+__device__ __forceinline__ void norm_lds_fill(const AttnExt& x, int tid) {
+    const float* __restrict__ src = tid < 64 ? x.qw : tid < 128 ? x.qb : tid < 192 ? x.kw : x.kb;
+    norm_lds()[tid] = src[tid & 63];                    // (visible after the first barrier of own_rows)
+}
+// LayerNorm of the staged row in place: the 8 lanes that hold a row (tid & 7) exchange their sums; two passes (mean,
+// then the squared distances to it), float32.  A row past the end becomes zeros, as it is without the norm.
+__device__ __forceinline__ void stage_norm(Stage& r, const float* __restrict__ w, const float* __restrict__ b, float eps,
+                                           bool valid, int tid) {
+    const int part = tid & 7, x = part >> 2, q0 = (part & 3) * 4;
+    float sum = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) sum += r.u[k] + r.v[k];
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) sum += __shfl_xor(sum, o, kWave);
+    const float mean = sum * (1.f / kAttnD);
+    float d2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float du = r.u[k] - mean, dv = r.v[k] - mean;
+        d2 = fmaf(du, du, d2);
+        d2 = fmaf(dv, dv, d2);
+    }
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) d2 += __shfl_xor(d2, o, kWave);
+    const float rstd = 1.f / sqrtf(d2 * (1.f / kAttnD) + eps);
+    const int d = 32 * x + q0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        r.u[k] = valid ? fmaf((r.u[k] - mean) * rstd, w[d + k], b[d + k]) : 0.f;
+        r.v[k] = valid ? fmaf((r.v[k] - mean) * rstd, w[d + 16 + k], b[d + 16 + k]) : 0.f;
+    }
+}
+
+// ---- MASK ----------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float mask_value(float m) { return m; }
+__device__ __forceinline__ float mask_value(uint8_t m) { return m ? 0.f : -INFINITY; }
+
+// A lane's 16 mask entries of a tile are loaded before the tile is committed to LDS (in flight under that work), parked
+// in LDS (mask_park: every lane has 16 words of its own, [r][tid], free of bank conflicts) and added to the finished score
+// (mask_add): the matrix instructions in between run without 16 more live registers, and the score is
+// round(scale q . k) + mask as the reference forms it -- a zero mask leaves the bits of the unmasked product.
+__device__ __forceinline__ float* mask_lds() {
+    __shared__ float s_m[16 * kBlock];
+    return s_m;
+}
+__device__ __forceinline__ void mask_park(const f16v& mv, int tid) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) mask_lds()[r * kBlock + tid] = mv[r];
+}
+__device__ __forceinline__ void mask_add(f16v& s, int tid) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[r] += mask_lds()[r * kBlock + tid];
+}
+// Forward and dq pass: register r is key i0 + acc_row(r, kl) of the lane's mask row `row` (runs of 4 consecutive keys).
+// Dwords (or bytes): no alignment is assumed.  FULL: the tile lies inside the matrix and the loads are unconditional; else entries past the end are 0 (the
+// padding rules of the passes deal with those).  A lane without a row of its own is handed an existing one: what it
+// computes is never stored.
+template <typename M, bool FULL>
+__device__ __forceinline__ void mask_tile_t(f16v& mv, const M* __restrict__ row, int i0, int n, int kl) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int i = i0 + acc_row(r, kl);
+        mv[r] = (FULL || i < n) ? mask_value(row[i]) : 0.f;
+    }
+}
+__device__ __forceinline__ void mask_tile(f16v& mv, const AttnExt& x, int64_t off, int i0, int n, int kl) {
+    const bool full = i0 + kAttnT <= n;                 // (both conditions are wave-uniform)
+    if (x.mask_bool) {
+        const uint8_t* __restrict__ row = static_cast<const uint8_t*>(x.mask) + off;
+        if (full) mask_tile_t<uint8_t, true>(mv, row, i0, n, kl);
+        else mask_tile_t<uint8_t, false>(mv, row, i0, n, kl);
+    } else {
+        const float* __restrict__ row = static_cast<const float*>(x.mask) + off;
+        if (full) mask_tile_t<float, true>(mv, row, i0, n, kl);
+        else mask_tile_t<float, false>(mv, row, i0, n, kl);
+    }
+}
+// The same for a lane that owns a key and walks queries (dk/dv pass): register r is query i0 + acc_row(r, kl) at the
+// lane's key.  A mask row starts at a wave-uniform address; a lane picks the row of its half (kl) and adds its key, so
+// lanes consecutive in k coalesce.  No branch per load: a query past the end reads the last row instead (its
+// probability is 0 through its log-sum-exp of +inf, whatever the mask says), a lane past the last key the last key
+// (what it computes is never stored).
+template <typename M>
+__device__ __forceinline__ void mask_tile_cols_t(f16v& mv, const M* __restrict__ base, int64_t step, int key, int i0, int n,
+                                                 int kl) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int rr = i0 + (r & 3) + 8 * (r >> 2);
+        const M* __restrict__ r0 = base + min(rr, n - 1) * step;
+        const M* __restrict__ r1 = base + min(rr + 4, n - 1) * step;
+        mv[r] = mask_value((kl ? r1 : r0)[key]);
+    }
+}
+__device__ __forceinline__ void mask_tile_cols(f16v& mv, const AttnExt& x, int64_t off, int key, int i0, int n, int kl) {
+    if (x.mask_bool) mask_tile_cols_t(mv, static_cast<const uint8_t*>(x.mask) + off, x.ms[2], key, i0, n, kl);
+    else mask_tile_cols_t(mv, static_cast<const float*>(x.mask) + off, x.ms[2], key, i0, n, kl);
+}
+
 // The rows a wave owns, as B operands: stage the block's 128 rows 32 at a time through s_a (and s_b for a second
 // operand with the same rows), each wave keeps its own chunk.
-template <typename T>
+template <typename T, bool NORM = false>
 __device__ __forceinline__ void own_rows(float (&ra)[32], const T* __restrict__ a, int64_t a_sn, const int64_t* __restrict__ pos,
                                          float mult, float (&rb)[32], const T* __restrict__ b, int64_t b_sn, int row0, int N,
-                                         float* __restrict__ s_a, float* __restrict__ s_b, const RopeFreq& f, int tid) {
+                                         float* __restrict__ s_a, float* __restrict__ s_b, const RopeFreq& f, int tid,
+                                         const float* __restrict__ nw = nullptr, float eps = 0.f) {
     const int lane = tid & 63, wave = tid >> 6, il = lane & 31, kl = lane >> 5;
 #pragma unroll 1
     for (int w = 0; w < 4; ++w) {
@@ -130,6 +259,7 @@ __device__ __forceinline__ void own_rows(float (&ra)[32], const T* __restrict__ 
         stage_load<T>(sa, a, a_sn, pos, row0 + kAttnT * w, N, tid);
         if (b) stage_load<T>(sb, b, b_sn, nullptr, row0 + kAttnT * w, N, tid);
         __syncthreads();
+        if constexpr (NORM) stage_norm(sa, nw, nw + kAttnD, eps, row0 + kAttnT * w + (tid >> 3) < N, tid);
         stage_commit(sa, s_a, pos != nullptr, f, mult, tid);
         if (b) stage_commit(sb, s_b, false, f, 1.f, tid);
         __syncthreads();
@@ -143,6 +273,18 @@ __device__ __forceinline__ void own_rows(float (&ra)[32], const T* __restrict__ 
     }
 }
 
+// one half (y or x) of a row's gradient rotated by -angle; p = the row's position along that axis
+__device__ __forceinline__ void unrotate_half(f16v& a, float p, const RopeFreq& f, int kl) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {               // u: registers 0..7 (d < 16 of the half), v: registers 8..15 (d + 16)
+        float sn, cs;
+        rope_sincos(p * f.inv[(r & 3) + 8 * (r >> 2) + 4 * kl], sn, cs);
+        const float u = a[r], v = a[r + 8];
+        a[r] = fmaf(u, cs, v * sn);
+        a[r + 8] = fmaf(v, cs, -(u * sn));
+    }
+}
+
 // gradient of a rotated row back to the unrotated one (rotation by -angle) and its store: acc0 / acc1 hold d < 32 / d >= 32
 // of the row on this lane (rows of the accumulator = d), `g` = its address, pos = the row's (y, x) or null
 template <typename T>
@@ -151,17 +293,7 @@ __device__ __forceinline__ void store_row(T* __restrict__ g, f16v acc0, f16v acc
 #pragma unroll
     for (int x = 0; x < 2; ++x) {
         f16v a = x ? acc1 : acc0;
-        if (pos) {
-            const float p = (float)pos[x];
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {       // u: registers 0..7 (d < 16 of the half), v: registers 8..15 (d + 16)
-                float sn, cs;
-                rope_sincos(p * f.inv[(r & 3) + 8 * (r >> 2) + 4 * kl], sn, cs);
-                const float u = a[r], v = a[r + 8];
-                a[r] = fmaf(u, cs, v * sn);
-                a[r + 8] = fmaf(v, cs, -(u * sn));
-            }
-        }
+        if (pos) unrotate_half(a, (float)pos[x], f, kl);
 #pragma unroll
         for (int gq = 0; gq < 4; ++gq)
             store4<T>(g + 32 * x + 8 * gq + 4 * kl, a[4 * gq] * mult, a[4 * gq + 1] * mult, a[4 * gq + 2] * mult,
@@ -170,8 +302,9 @@ __device__ __forceinline__ void store_row(T* __restrict__ g, f16v acc0, f16v acc
 }
 
 // ---- forward -------------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(kBlock) void spf_attn_fwd_kernel(AttnArgs a, T* __restrict__ out, float* __restrict__ lse) {
+template <typename T, bool MASK = false, bool NORM = false>
+__global__ __launch_bounds__(kBlock) void spf_attn_fwd_kernel(typename ArgsOf<MASK || NORM>::type a, T* __restrict__ out,
+                                                              float* __restrict__ lse) {
     __shared__ float s_k[kAttnT * kAttnLd];
     __shared__ float s_v[kAttnT * kAttnLd];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, il = lane & 31, kl = lane >> 5;
@@ -183,8 +316,16 @@ __global__ __launch_bounds__(kBlock) void spf_attn_fwd_kernel(AttnArgs a, T* __r
     const int64_t* __restrict__ kp = a.kpos ? a.kpos + (int64_t)b * a.Nk * 2 : nullptr;
 
     float qr[32], unused[32];
-    own_rows<T>(qr, qb, a.qs[1], qp, a.scale, unused, nullptr, 0, q0, a.Nq, s_k, s_v, a.f, tid);
+    if constexpr (NORM) {
+        norm_lds_fill(a.x, tid);
+        own_rows<T, true>(qr, qb, a.qs[1], qp, a.scale, unused, nullptr, 0, q0, a.Nq, s_k, s_v, a.f, tid, norm_lds(), a.x.eps);
+    } else {
+        own_rows<T>(qr, qb, a.qs[1], qp, a.scale, unused, nullptr, 0, q0, a.Nq, s_k, s_v, a.f, tid);
+    }
     const bool active = q0 + kAttnT * wave < a.Nq;      // wave-uniform: a wave without queries only helps staging
+    const int qi = q0 + kAttnT * wave + il;
+    int64_t moff = 0;                                   // MASK: this lane's row of the mask
+    if constexpr (MASK) moff = b * a.x.ms[0] + h * a.x.ms[1] + min(qi, a.Nq - 1) * a.x.ms[2];
 
     f16v o0, o1;
 #pragma unroll
@@ -195,7 +336,15 @@ __global__ __launch_bounds__(kBlock) void spf_attn_fwd_kernel(AttnArgs a, T* __r
     stage_load<T>(sv, vb, a.vs[1], nullptr, 0, a.Nk, tid);
 #pragma unroll 1
     for (int k0 = 0; k0 < a.Nk; k0 += kAttnT) {
+        f16v s;                                         // S^T: rows = keys, column = this lane's query
+        if constexpr (MASK) {
+            if (active) mask_tile(s, a.x, moff, k0, a.Nk, kl);
+        }
         __syncthreads();                                // the previous tile's readers are done
+        if constexpr (MASK) {
+            if (active) mask_park(s, tid);
+        }
+        if constexpr (NORM) stage_norm(sk, norm_lds() + 2 * kAttnD, norm_lds() + 3 * kAttnD, a.x.eps, k0 + (tid >> 3) < a.Nk, tid);
         stage_commit(sk, s_k, kp != nullptr, a.f, 1.f, tid);
         stage_commit(sv, s_v, false, a.f, 1.f, tid);
         __syncthreads();
@@ -204,12 +353,12 @@ __global__ __launch_bounds__(kBlock) void spf_attn_fwd_kernel(AttnArgs a, T* __r
             stage_load<T>(sv, vb, a.vs[1], nullptr, k0 + kAttnT, a.Nk, tid);
         }
         if (!active) continue;
-        f16v s;                                         // S^T: rows = keys, column = this lane's query
 #pragma unroll
         for (int e = 0; e < 16; ++e) s[e] = 0.f;
 #pragma unroll
         for (int st = 0; st < 32; ++st)
             s = __builtin_amdgcn_mfma_f32_32x32x2f32(s_k[il * kAttnLd + 2 * st + kl], qr[st], s, 0, 0, 0);
+        if constexpr (MASK) mask_add(s, tid);
         if (k0 + kAttnT > a.Nk) {                       // padded keys: probability 0
 #pragma unroll
             for (int r = 0; r < 16; ++r)
@@ -219,13 +368,15 @@ __global__ __launch_bounds__(kBlock) void spf_attn_fwd_kernel(AttnArgs a, T* __r
 #pragma unroll
         for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, s[r]);
         tmax = fmaxf(tmax, __shfl_xor(tmax, 32, kWave));
-        const float mn = fmaxf(m, tmax);                // finite: every tile holds at least one key
-        const float alpha = expf(m - mn);
+        const float mn = fmaxf(m, tmax);                // finite: every tile holds at least one key -- unless MASK:
+        float mref = mn;                                // while every key so far is masked the maximum is still -inf;
+        if constexpr (MASK) mref = mn == -INFINITY ? 0.f : mn;      // exp(-inf - 0) = 0 then, where -inf - -inf is NaN
+        const float alpha = expf(m - mref);
         m = mn;
         float ps = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            s[r] = expf(s[r] - mn);
+            s[r] = expf(s[r] - mref);
             ps += s[r];
         }
         l = l * alpha + ps;
@@ -240,13 +391,118 @@ __global__ __launch_bounds__(kBlock) void spf_attn_fwd_kernel(AttnArgs a, T* __r
     }
     if (!active) return;
     const float lt = l + __shfl_xor(l, 32, kWave);
-    const int qi = q0 + kAttnT * wave + il;
     if (qi >= a.Nq) return;
-    if (kl == 0) lse[((int64_t)b * a.H + h) * a.Nq + qi] = m + logf(lt);
-    store_row<T>(out + (((int64_t)b * a.Nq + qi) * a.H + h) * kAttnD, o0, o1, 1.f / lt, nullptr, a.f, kl);
+    float row_lse = m + logf(lt), inv = 1.f / lt;
+    if constexpr (MASK) {
+        if (!(lt > 0.f)) { row_lse = -INFINITY; inv = 0.f; }       // every key masked: out = 0, lse = -inf
+    }
+    if (kl == 0) lse[((int64_t)b * a.H + h) * a.Nq + qi] = row_lse;
+    store_row<T>(out + (((int64_t)b * a.Nq + qi) * a.H + h) * kAttnD, o0, o1, inv, nullptr, a.f, kl);
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------
+// NORM epilogue of an owner row.  a0 / a1: the gradient with respect to the normalised row y = x^ gamma + beta, un-rotated
+// (this lane: elements d = 32 x + acc_row(r, kl) of row il; its partner lane ^ 32 holds the rest).  The row's mean and
+// rstd are recomputed from the input row `xrow` (two passes), then
+//   dx = rstd (g^ - mean(g^) - x^ mean(g^ x^)),  g^ = g gamma
+// is stored at `dst`, and the block's 128 rows of (g x^, g) are added per column in a fixed order -- wave by wave
+// through the tile buffers, rows ascending, in double -- into part[2][64] (float32: one rounding per block).  EVERY thread of the block calls this (barriers); a row
+// that does not exist has valid = false and adds zeros.
+template <typename T>
+__device__ __forceinline__ void norm_backward_row(T* __restrict__ dst, const T* __restrict__ xrow, f16v a0, f16v a1,
+                                                  const float* __restrict__ gamma, float eps, bool valid,
+                                                  float* __restrict__ s_a, float* __restrict__ s_b,
+                                                  float* __restrict__ part, int tid) {
+    const int lane = tid & 63, wave = tid >> 6, il = lane & 31, kl = lane >> 5;
+    float xh[32], g[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        g[i] = valid ? (i < 16 ? a0[i & 15] : a1[i & 15]) : 0.f;
+        xh[i] = 0.f;
+    }
+    if (valid) {
+#pragma unroll
+        for (int gq = 0; gq < 8; ++gq) load4<T>(xrow + 32 * (gq >> 2) + 8 * (gq & 3) + 4 * kl, xh + 4 * gq);
+    }
+    // The row statistics and the three-term difference below in double (64 elements per row, once per row: the cost is
+    // nothing): each stored element then carries one rounding of its own instead of the roundings of two float32 means.
+    double sum = 0.0;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) sum += (double)xh[i];
+    sum += __shfl_xor(sum, 32, kWave);
+    const double mean = sum * (1.0 / kAttnD);
+    double d2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        const double d = (double)xh[i] - mean;
+        d2 = fma(d, d, d2);
+    }
+    d2 += __shfl_xor(d2, 32, kWave);
+    const double rstd = 1.0 / sqrt(d2 * (1.0 / kAttnD) + (double)eps);
+    double m1 = 0.0, m2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        xh[i] = (float)(((double)xh[i] - mean) * rstd);
+        const double gh = (double)g[i] * (double)gamma[32 * (i >> 4) + acc_row(i & 15, kl)];
+        m1 += gh;
+        m2 = fma(gh, (double)xh[i], m2);
+    }
+    m1 += __shfl_xor(m1, 32, kWave);
+    m2 += __shfl_xor(m2, 32, kWave);
+    m1 *= 1.0 / kAttnD;
+    m2 *= 1.0 / kAttnD;
+    if (valid) {
+#pragma unroll
+        for (int gq = 0; gq < 8; ++gq) {
+            float dx[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int i = 4 * gq + e;
+                const double gh = (double)g[i] * (double)gamma[32 * (i >> 4) + acc_row(i & 15, kl)];
+                dx[e] = (float)(rstd * (gh - m1 - (double)xh[i] * m2));
+            }
+            store4<T>(dst + 32 * (gq >> 2) + 8 * (gq & 3) + 4 * kl, dx[0], dx[1], dx[2], dx[3]);
+        }
+    }
+    double acc = 0.0;                                   // (128 terms a column: double costs nothing and rounds once)
+#pragma unroll 1
+    for (int w = 0; w < 4; ++w) {
+        __syncthreads();                                // the tile loop's (or the previous wave's) readers are done
+        if (wave == w) {
+#pragma unroll
+            for (int i = 0; i < 32; ++i) {
+                const int d = 32 * (i >> 4) + acc_row(i & 15, kl);
+                s_a[il * kAttnLd + d] = xh[i];
+                s_b[il * kAttnLd + d] = g[i];
+            }
+        }
+        __syncthreads();
+        if (tid < 2 * kAttnD) {
+            const int col = tid & 63;
+#pragma unroll 8
+            for (int row = 0; row < kAttnT; ++row) {
+                const double gv = (double)s_b[row * kAttnLd + col];
+                acc = tid < kAttnD ? fma(gv, (double)s_a[row * kAttnLd + col], acc) : acc + gv;
+            }
+        }
+    }
+    if (tid < 2 * kAttnD) part[tid] = (float)acc;
+}
+
+// dweight, dbias [64] = the partials of all blocks added in block order, in double: one block of 256 lanes, lane =
+// (half of the blocks, which of the two, column); the two halves meet in LDS.  Fixed order: reproducible.
+__global__ __launch_bounds__(kBlock) void spf_attn_norm_reduce_kernel(const float* __restrict__ part, int nblk,
+                                                                      float* __restrict__ dw, float* __restrict__ db) {
+    __shared__ double s_sum[kBlock];
+    const int tid = threadIdx.x, seg = tid >> 7, per = (nblk + 1) / 2;
+    const int end = min(nblk, (seg + 1) * per);
+    double sum = 0.0;
+    for (int i = seg * per; i < end; ++i) sum += (double)part[(int64_t)i * 2 * kAttnD + (tid & 127)];
+    s_sum[tid] = sum;
+    __syncthreads();
+    if (tid < 2 * kAttnD) (tid >> 6 ? db : dw)[tid & 63] = (float)(s_sum[tid] + s_sum[tid + 128]);
+}
+
 // delta[b,h,q] = sum_d dout[b,q,h,d] * out[b,q,h,d], one lane per row: ONE fma chain over d in ascending order, which
 // is bit for bit how the matrix instruction accumulates dP = dout . v in the two passes below -- where a row attends
 // to a single key (out = v exactly) dP - delta is then exactly zero, as it is in exact arithmetic.
@@ -271,8 +527,9 @@ __global__ __launch_bounds__(kBlock) void spf_attn_delta_kernel(const T* __restr
 }
 
 // dk, dv: the block owns 128 keys, walks the queries.
-template <typename T>
-__global__ __launch_bounds__(kBlock, 2) void spf_attn_dkdv_kernel(AttnArgs a, AttnGradArgs g, const T* __restrict__ dout,
+template <typename T, bool MASK = false, bool NORM = false>
+__global__ __launch_bounds__(kBlock, 2) void spf_attn_dkdv_kernel(typename ArgsOf<MASK || NORM>::type a, AttnGradArgs g,
+                                                               const T* __restrict__ dout,
                                                                const float* __restrict__ lse,
                                                                const float* __restrict__ delta) {
     __shared__ float s_q[kAttnT * kAttnLd];
@@ -291,8 +548,16 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dkdv_kernel(AttnArgs a, At
     const float* __restrict__ dl_r = delta + ((int64_t)b * a.H + h) * a.Nq;
 
     float kr[32], vr[32];
-    own_rows<T>(kr, kb, a.ks[1], kp, 1.f, vr, vb, a.vs[1], k0, a.Nk, s_q, s_do, a.f, tid);
+    if constexpr (NORM) {
+        norm_lds_fill(a.x, tid);
+        own_rows<T, true>(kr, kb, a.ks[1], kp, 1.f, vr, vb, a.vs[1], k0, a.Nk, s_q, s_do, a.f, tid, norm_lds() + 2 * kAttnD,
+                          a.x.eps);
+    } else {
+        own_rows<T>(kr, kb, a.ks[1], kp, 1.f, vr, vb, a.vs[1], k0, a.Nk, s_q, s_do, a.f, tid);
+    }
     const bool active = k0 + kAttnT * wave < a.Nk;
+    [[maybe_unused]] int okey = 0;                      // (flagged only: the unflagged pass forms its key at the end)
+    if constexpr (MASK || NORM) okey = k0 + kAttnT * wave + il;
 
     f16v dk0, dk1, dv0, dv1;
 #pragma unroll
@@ -304,7 +569,16 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dkdv_kernel(AttnArgs a, At
     if (tid < kAttnT && tid < a.Nq) { rl = lse_r[tid]; rd = dl_r[tid]; }
 #pragma unroll 1
     for (int q0 = 0; q0 < a.Nq; q0 += kAttnT) {
+        f16v s, dp;                                     // S, dP: rows = queries, column = this lane's key
+        if constexpr (MASK) {
+            if (active)
+                mask_tile_cols(s, a.x, b * a.x.ms[0] + h * a.x.ms[1], min(okey, a.Nk - 1), q0, a.Nq, kl);
+        }
         __syncthreads();
+        if constexpr (MASK) {
+            if (active) mask_park(s, tid);
+        }
+        if constexpr (NORM) stage_norm(sq, norm_lds(), norm_lds() + kAttnD, a.x.eps, q0 + (tid >> 3) < a.Nq, tid);
         stage_commit(sq, s_q, qp != nullptr, a.f, a.scale, tid);
         stage_commit(sd, s_do, false, a.f, 1.f, tid);
         if (tid < kAttnT) { s_lse[tid] = rl; s_dl[tid] = rd; }
@@ -316,7 +590,6 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dkdv_kernel(AttnArgs a, At
             if (tid < kAttnT && q0 + kAttnT + tid < a.Nq) { rl = lse_r[q0 + kAttnT + tid]; rd = dl_r[q0 + kAttnT + tid]; }
         }
         if (!active) continue;
-        f16v s, dp;                                     // S, dP: rows = queries, column = this lane's key
 #pragma unroll
         for (int e = 0; e < 16; ++e) s[e] = dp[e] = 0.f;
 #pragma unroll
@@ -324,10 +597,12 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dkdv_kernel(AttnArgs a, At
             s = __builtin_amdgcn_mfma_f32_32x32x2f32(s_q[il * kAttnLd + 2 * st + kl], kr[st], s, 0, 0, 0);
             dp = __builtin_amdgcn_mfma_f32_32x32x2f32(s_do[il * kAttnLd + 2 * st + kl], vr[st], dp, 0, 0, 0);
         }
+        if constexpr (MASK) mask_add(s, tid);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = acc_row(r, kl);
-            const float p = expf(s[r] - s_lse[row]);
+            float p = expf(s[r] - s_lse[row]);
+            if constexpr (MASK) p = s[r] == -INFINITY ? 0.f : p;    // (a fully masked row has lse = -inf: -inf - -inf)
             s[r] = p;
             dp[r] = p * (dp[r] - s_dl[row]);
         }
@@ -342,12 +617,26 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dkdv_kernel(AttnArgs a, At
             dk1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qrow[32], dp[r], dk1, 0, 0, 0);
         }
     }
-    if (!active) return;
-    const int key = k0 + kAttnT * wave + il;
-    if (key >= a.Nk) return;
-    store_row<T>(static_cast<T*>(g.dv) + b * g.dvs[0] + (int64_t)key * g.dvs[1] + h * g.dvs[2], dv0, dv1, 1.f, nullptr, a.f, kl);
-    store_row<T>(static_cast<T*>(g.dk) + b * g.dks[0] + (int64_t)key * g.dks[1] + h * g.dks[2], dk0, dk1, 1.f,
-                 kp ? kp + (int64_t)key * 2 : nullptr, a.f, kl);
+    if constexpr (NORM) {
+        const int key = okey;
+        const bool valid = active && key < a.Nk;
+        T* __restrict__ dv_row = static_cast<T*>(g.dv) + b * g.dvs[0] + (int64_t)key * g.dvs[1] + h * g.dvs[2];
+        T* __restrict__ dk_row = static_cast<T*>(g.dk) + b * g.dks[0] + (int64_t)key * g.dks[1] + h * g.dks[2];
+        if (valid) store_row<T>(dv_row, dv0, dv1, 1.f, nullptr, a.f, kl);
+        if (valid && kp) {
+            unrotate_half(dk0, (float)kp[(int64_t)key * 2], a.f, kl);
+            unrotate_half(dk1, (float)kp[(int64_t)key * 2 + 1], a.f, kl);
+        }
+        norm_backward_row<T>(dk_row, kb + (int64_t)key * a.ks[1], dk0, dk1, norm_lds() + 2 * kAttnD, a.x.eps, valid, s_q, s_do,
+                             a.x.part + (((int64_t)b * a.H + h) * gridDim.x + blockIdx.x) * 2 * kAttnD, tid);
+    } else {
+        if (!active) return;
+        const int key = k0 + kAttnT * wave + il;
+        if (key >= a.Nk) return;
+        store_row<T>(static_cast<T*>(g.dv) + b * g.dvs[0] + (int64_t)key * g.dvs[1] + h * g.dvs[2], dv0, dv1, 1.f, nullptr, a.f, kl);
+        store_row<T>(static_cast<T*>(g.dk) + b * g.dks[0] + (int64_t)key * g.dks[1] + h * g.dks[2], dk0, dk1, 1.f,
+                     kp ? kp + (int64_t)key * 2 : nullptr, a.f, kl);
+    }
 }
 
 // dq: the block owns 128 queries, walks the keys.  It also settles the row term.  `delta` comes in as sum_d dout * out
@@ -356,8 +645,9 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dkdv_kernel(AttnArgs a, At
 // accumulates c = sum_j p[j] (dP[j] - delta~) (tiny: the residual of delta~) and B = sum_j p[j] k[j] next to
 // A = sum_j p[j] (dP[j] - delta~) k[j], returns dq = scale (A - c B) -- the gradient with delta = sum_j p[j] dP[j], the
 // softmax backward's own row sum -- and writes delta~ + c back for the dk/dv pass, which recomputes the same dP bits.
-template <typename T>
-__global__ __launch_bounds__(kBlock, 2) void spf_attn_dq_kernel(AttnArgs a, AttnGradArgs g, const T* __restrict__ dout,
+template <typename T, bool MASK = false, bool NORM = false>
+__global__ __launch_bounds__(kBlock, 2) void spf_attn_dq_kernel(typename ArgsOf<MASK || NORM>::type a, AttnGradArgs g,
+                                                             const T* __restrict__ dout,
                                                              const float* __restrict__ lse,
                                                              float* __restrict__ delta) {
     __shared__ float s_k[kAttnT * kAttnLd];
@@ -372,9 +662,17 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dq_kernel(AttnArgs a, Attn
     const int64_t* __restrict__ kp = a.kpos ? a.kpos + (int64_t)b * a.Nk * 2 : nullptr;
 
     float qr[32], gr[32];
-    own_rows<T>(qr, qb, a.qs[1], qp, a.scale, gr, gb, (int64_t)a.H * kAttnD, q0, a.Nq, s_k, s_v, a.f, tid);
+    if constexpr (NORM) {
+        norm_lds_fill(a.x, tid);
+        own_rows<T, true>(qr, qb, a.qs[1], qp, a.scale, gr, gb, (int64_t)a.H * kAttnD, q0, a.Nq, s_k, s_v, a.f, tid, norm_lds(),
+                          a.x.eps);
+    } else {
+        own_rows<T>(qr, qb, a.qs[1], qp, a.scale, gr, gb, (int64_t)a.H * kAttnD, q0, a.Nq, s_k, s_v, a.f, tid);
+    }
     const bool active = q0 + kAttnT * wave < a.Nq;
     const int qi = q0 + kAttnT * wave + il;
+    int64_t moff = 0;                                   // MASK: this lane's row of the mask
+    if constexpr (MASK) moff = b * a.x.ms[0] + h * a.x.ms[1] + min(qi, a.Nq - 1) * a.x.ms[2];
     float my_lse = INFINITY, my_dl = 0.f;
     if (qi < a.Nq) {
         my_lse = lse[((int64_t)b * a.H + h) * a.Nq + qi];
@@ -390,7 +688,15 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dq_kernel(AttnArgs a, Attn
     stage_load<T>(sv, vb, a.vs[1], nullptr, 0, a.Nk, tid);
 #pragma unroll 1
     for (int k0 = 0; k0 < a.Nk; k0 += kAttnT) {
+        f16v s, dp;                                     // S^T, dP^T: rows = keys, column = this lane's query
+        if constexpr (MASK) {
+            if (active) mask_tile(s, a.x, moff, k0, a.Nk, kl);
+        }
         __syncthreads();
+        if constexpr (MASK) {
+            if (active) mask_park(s, tid);
+        }
+        if constexpr (NORM) stage_norm(sk, norm_lds() + 2 * kAttnD, norm_lds() + 3 * kAttnD, a.x.eps, k0 + (tid >> 3) < a.Nk, tid);
         stage_commit(sk, s_k, kp != nullptr, a.f, 1.f, tid);
         stage_commit(sv, s_v, false, a.f, 1.f, tid);
         __syncthreads();
@@ -399,7 +705,6 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dq_kernel(AttnArgs a, Attn
             stage_load<T>(sv, vb, a.vs[1], nullptr, k0 + kAttnT, a.Nk, tid);
         }
         if (!active) continue;
-        f16v s, dp;                                     // S^T, dP^T: rows = keys, column = this lane's query
 #pragma unroll
         for (int e = 0; e < 16; ++e) s[e] = dp[e] = 0.f;
 #pragma unroll
@@ -407,10 +712,12 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dq_kernel(AttnArgs a, Attn
             s = __builtin_amdgcn_mfma_f32_32x32x2f32(s_k[il * kAttnLd + 2 * st + kl], qr[st], s, 0, 0, 0);
             dp = __builtin_amdgcn_mfma_f32_32x32x2f32(s_v[il * kAttnLd + 2 * st + kl], gr[st], dp, 0, 0, 0);
         }
+        if constexpr (MASK) mask_add(s, tid);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             float p = expf(s[r] - my_lse);
             if (k0 + acc_row(r, kl) >= a.Nk) p = 0.f;   // padded keys
+            if constexpr (MASK) p = s[r] == -INFINITY ? 0.f : p;    // (a fully masked row has lse = -inf: -inf - -inf)
             s[r] = p;
             dp[r] = p * (dp[r] - my_dl);
             cres += dp[r];
@@ -425,17 +732,36 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dq_kernel(AttnArgs a, Attn
             pk1 = __builtin_amdgcn_mfma_f32_32x32x2f32(k1v, s[r], pk1, 0, 0, 0);
         }
     }
-    if (!active) return;
-    const float c = cres + __shfl_xor(cres, 32, kWave);
-    if (qi >= a.Nq) return;
+    T* __restrict__ dq_row = static_cast<T*>(g.dq) + b * g.dqs[0] + (int64_t)qi * g.dqs[1] + h * g.dqs[2];
+    if constexpr (NORM) {
+        const bool valid = active && qi < a.Nq;
+        const float c = cres + __shfl_xor(cres, 32, kWave);
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        dq0[e] = fmaf(-c, pk0[e], dq0[e]);
-        dq1[e] = fmaf(-c, pk1[e], dq1[e]);
+        for (int e = 0; e < 16; ++e) {
+            dq0[e] = fmaf(-c, pk0[e], dq0[e]);
+            dq1[e] = fmaf(-c, pk1[e], dq1[e]);
+        }
+        if (valid && kl == 0) delta[((int64_t)b * a.H + h) * a.Nq + qi] = my_dl + c;
+        if (valid && qp) {
+            unrotate_half(dq0, (float)qp[(int64_t)qi * 2], a.f, kl);
+            unrotate_half(dq1, (float)qp[(int64_t)qi * 2 + 1], a.f, kl);
+        }
+#pragma unroll
+        for (int e = 0; e < 16; ++e) { dq0[e] *= a.scale; dq1[e] *= a.scale; }
+        norm_backward_row<T>(dq_row, qb + (int64_t)qi * a.qs[1], dq0, dq1, norm_lds(), a.x.eps, valid, s_k, s_v,
+                             a.x.part + (((int64_t)b * a.H + h) * gridDim.x + blockIdx.x) * 2 * kAttnD, tid);
+    } else {
+        if (!active) return;
+        const float c = cres + __shfl_xor(cres, 32, kWave);
+        if (qi >= a.Nq) return;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            dq0[e] = fmaf(-c, pk0[e], dq0[e]);
+            dq1[e] = fmaf(-c, pk1[e], dq1[e]);
+        }
+        if (kl == 0) delta[((int64_t)b * a.H + h) * a.Nq + qi] = my_dl + c;
+        store_row<T>(dq_row, dq0, dq1, a.scale, qp ? qp + (int64_t)qi * 2 : nullptr, a.f, kl);
     }
-    if (kl == 0) delta[((int64_t)b * a.H + h) * a.Nq + qi] = my_dl + c;
-    store_row<T>(static_cast<T*>(g.dq) + b * g.dqs[0] + (int64_t)qi * g.dqs[1] + h * g.dqs[2], dq0, dq1, a.scale,
-                 qp ? qp + (int64_t)qi * 2 : nullptr, a.f, kl);
 }
 
 AttnArgs make_args(const SpfAttn& p) {
@@ -454,6 +780,67 @@ hipError_t attn_forward_t(const SpfAttn& p, void* out, float* lse, hipStream_t s
     const dim3 grid((p.Nq + kAttnOwn - 1) / kAttnOwn, p.H, p.B);
     spf_attn_fwd_kernel<T><<<grid, kBlock, 0, stream>>>(make_args(p), static_cast<T*>(out), lse);
     return hipGetLastError();
+}
+
+AttnArgsX make_args_x(const SpfAttn& p, const SpfAttnExt& e) {
+    AttnArgsX a;
+    static_cast<AttnArgs&>(a) = make_args(p);
+    a.x.mask = e.mask;
+    for (int i = 0; i < 3; ++i) a.x.ms[i] = e.mask_stride[i];
+    a.x.mask_bool = e.mask_dtype != 0;
+    a.x.qw = e.q_weight; a.x.qb = e.q_bias; a.x.kw = e.k_weight; a.x.kb = e.k_bias;
+    a.x.eps = e.eps;
+    a.x.part = nullptr;
+    return a;
+}
+
+template <typename T, bool MASK, bool NORM>
+hipError_t attn_forward_x(const SpfAttn& p, const SpfAttnExt& e, void* out, float* lse, hipStream_t stream) {
+    const dim3 grid((p.Nq + kAttnOwn - 1) / kAttnOwn, p.H, p.B);
+    spf_attn_fwd_kernel<T, MASK, NORM><<<grid, kBlock, 0, stream>>>(make_args_x(p, e), static_cast<T*>(out), lse);
+    return hipGetLastError();
+}
+
+template <typename T, bool MASK, bool NORM>
+hipError_t attn_backward_x(const SpfAttn& p, const SpfAttnGrads& gr, const SpfAttnExt& e, const void* out, const float* lse,
+                           const void* dout, hipStream_t stream) {
+    AttnArgsX a = make_args_x(p, e);
+    AttnGradArgs g;
+    g.dq = gr.dq; g.dk = gr.dk; g.dv = gr.dv;
+    for (int i = 0; i < 3; ++i) { g.dqs[i] = gr.dq_stride[i]; g.dks[i] = gr.dk_stride[i]; g.dvs[i] = gr.dv_stride[i]; }
+    const int64_t rows = (int64_t)p.B * p.Nq * p.H;
+    const int qblk = (p.Nq + kAttnOwn - 1) / kAttnOwn, kblk = (p.Nk + kAttnOwn - 1) / kAttnOwn;
+    float* part_q = e.partials;
+    float* part_k = e.partials ? e.partials + (int64_t)p.B * p.H * qblk * 2 * kAttnD : nullptr;
+    spf_attn_delta_kernel<T><<<(unsigned)((rows + kBlock - 1) / kBlock), kBlock, 0, stream>>>(
+        static_cast<const T*>(out), static_cast<const T*>(dout), gr.delta, p.B, p.H, p.Nq);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return err;
+    a.x.part = part_q;
+    spf_attn_dq_kernel<T, MASK, NORM><<<dim3(qblk, p.H, p.B), kBlock, 0, stream>>>(a, g, static_cast<const T*>(dout), lse,
+                                                                                  gr.delta);
+    err = hipGetLastError();
+    if (err != hipSuccess) return err;
+    a.x.part = part_k;
+    spf_attn_dkdv_kernel<T, MASK, NORM><<<dim3(kblk, p.H, p.B), kBlock, 0, stream>>>(a, g, static_cast<const T*>(dout), lse,
+                                                                                    gr.delta);
+    err = hipGetLastError();
+    if (err != hipSuccess || !NORM) return err;
+    spf_attn_norm_reduce_kernel<<<1, kBlock, 0, stream>>>(part_q, p.B * p.H * qblk, e.dq_weight, e.dq_bias);
+    spf_attn_norm_reduce_kernel<<<1, kBlock, 0, stream>>>(part_k, p.B * p.H * kblk, e.dk_weight, e.dk_bias);
+    return hipGetLastError();
+}
+
+// the flagged instantiation for (element type, mask, norm)
+template <typename T, typename... A>
+hipError_t attn_forward_flags(bool mask, bool norm, A&&... args) {
+    if (mask && norm) return attn_forward_x<T, true, true>(args...);
+    return mask ? attn_forward_x<T, true, false>(args...) : attn_forward_x<T, false, true>(args...);
+}
+template <typename T, typename... A>
+hipError_t attn_backward_flags(bool mask, bool norm, A&&... args) {
+    if (mask && norm) return attn_backward_x<T, true, true>(args...);
+    return mask ? attn_backward_x<T, true, false>(args...) : attn_backward_x<T, false, true>(args...);
 }
 
 template <typename T>
@@ -493,6 +880,31 @@ hipError_t launch_attn_backward(const SpfAttn& p, const SpfAttnGrads& g, const v
         case 0: return attn_backward_t<float>(p, g, out, lse, dout, stream);
         case 1: return attn_backward_t<__half>(p, g, out, lse, dout, stream);
         default: return attn_backward_t<__hip_bfloat16>(p, g, out, lse, dout, stream);
+    }
+}
+
+int64_t attn_ext_scratch_floats(int B, int H, int Nq, int Nk) {
+    const int64_t blocks = (Nq + kAttnOwn - 1) / kAttnOwn + (Nk + kAttnOwn - 1) / kAttnOwn;
+    return (int64_t)B * H * blocks * 2 * kAttnD;
+}
+
+// (the caller has checked that the extras hold a mask, the norm parameters or both)
+hipError_t launch_attn_forward_ext(const SpfAttn& p, const SpfAttnExt& e, void* out, float* lse, hipStream_t stream) {
+    const bool mask = e.mask != nullptr, norm = e.q_weight != nullptr;
+    switch (p.dtype) {
+        case 0: return attn_forward_flags<float>(mask, norm, p, e, out, lse, stream);
+        case 1: return attn_forward_flags<__half>(mask, norm, p, e, out, lse, stream);
+        default: return attn_forward_flags<__hip_bfloat16>(mask, norm, p, e, out, lse, stream);
+    }
+}
+
+hipError_t launch_attn_backward_ext(const SpfAttn& p, const SpfAttnGrads& g, const SpfAttnExt& e, const void* out,
+                                    const float* lse, const void* dout, hipStream_t stream) {
+    const bool mask = e.mask != nullptr, norm = e.q_weight != nullptr;
+    switch (p.dtype) {
+        case 0: return attn_backward_flags<float>(mask, norm, p, g, e, out, lse, dout, stream);
+        case 1: return attn_backward_flags<__half>(mask, norm, p, g, e, out, lse, dout, stream);
+        default: return attn_backward_flags<__hip_bfloat16>(mask, norm, p, g, e, out, lse, dout, stream);
     }
 }
 
