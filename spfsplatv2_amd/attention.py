@@ -180,19 +180,17 @@ def attention_forward(q, k, v, qpos, kpos, base, F0, scale, *, mask=None, q_norm
     B, H, Nq, D = q.shape
     out = torch.empty(B, Nq, H * D, dtype=q.dtype, device=q.device)
     lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
+    if mask is not None:
+        mask = _mask_view(mask, (B, H, Nq, k.shape[2]))
+    if q_norm is not None:
+        q_norm, k_norm = _norm_tensors(q_norm), _norm_tensors(k_norm)
     lib = _lib.load()
     with torch.cuda.device(q.device):
         stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
         a = _args(q, k, v, qpos, kpos, base, F0, scale)
-        if mask is None and q_norm is None:
-            _lib.check(lib.spf_attn_forward(C.byref(a), C.c_void_p(out.data_ptr()), C.c_void_p(lse.data_ptr()), stream),
-                       "spf_attn_forward")
-        else:
-            mask = _mask_view(mask, (B, H, Nq, k.shape[2]))
-            q_norm, k_norm = _norm_tensors(q_norm), _norm_tensors(k_norm)
-            e = _ext(mask, q_norm, k_norm)
-            _lib.check(lib.spf_attn_forward_ext(C.byref(a), C.byref(e), C.c_void_p(out.data_ptr()),
-                                                C.c_void_p(lse.data_ptr()), stream), "spf_attn_forward_ext")
+        e = _ext(mask, q_norm, k_norm)                  # (empty: the library runs the plain kernels)
+        _lib.check(lib.spf_attn_forward_ext(C.byref(a), C.byref(e), C.c_void_p(out.data_ptr()),
+                                            C.c_void_p(lse.data_ptr()), stream), "spf_attn_forward_ext")
     return out, lse
 
 
@@ -208,76 +206,28 @@ def attention_backward(q, k, v, qpos, kpos, base, F0, scale, out, lse, dout, dq,
         raise RuntimeError(f"rope_attention: gradient dtype {dout.dtype} differs from the inputs' {q.dtype}")
     B, H, Nq, D = q.shape
     delta = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
+    if mask is not None:
+        mask = _mask_view(mask, (B, H, Nq, k.shape[2]))
     lib = _lib.load()
+    dnorm = partials = None
+    if q_norm is not None:
+        q_norm, k_norm = _norm_tensors(q_norm), _norm_tensors(k_norm)
+        n = lib.spf_attn_ext_scratch_floats(B, H, Nq, k.shape[2])           # (the library's grid arithmetic, not ours)
+        if n < 0:
+            raise _lib.SpfError("spf_attn_ext_scratch_floats rejected the sizes")
+        dnorm = torch.empty(4, HEAD_DIM, dtype=torch.float32, device=q.device)
+        partials = torch.empty(n, dtype=torch.float32, device=q.device)
     with torch.cuda.device(q.device):
         stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
         a = _args(q, k, v, qpos, kpos, base, F0, scale)
         g = _lib.SpfAttnGrads()
         g.dq, g.dk, g.dv, g.delta = dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr()
         g.dq_stride, g.dk_stride, g.dv_stride = _strides(dq), _strides(dk), _strides(dv)
-        if mask is None and q_norm is None:
-            _lib.check(lib.spf_attn_backward(C.byref(a), C.byref(g), C.c_void_p(out.data_ptr()),
-                                             C.c_void_p(lse.data_ptr()), C.c_void_p(dout.data_ptr()), stream),
-                       "spf_attn_backward")
-            return None
-        mask = _mask_view(mask, (B, H, Nq, k.shape[2]))
-        q_norm, k_norm = _norm_tensors(q_norm), _norm_tensors(k_norm)
-        dnorm = partials = None
-        if q_norm is not None:
-            n = lib.spf_attn_ext_scratch_floats(B, H, Nq, k.shape[2])       # (the library's grid arithmetic, not ours)
-            if n < 0:
-                raise _lib.SpfError("spf_attn_ext_scratch_floats rejected the sizes")
-            dnorm = torch.empty(4, HEAD_DIM, dtype=torch.float32, device=q.device)
-            partials = torch.empty(n, dtype=torch.float32, device=q.device)
         e = _ext(mask, q_norm, k_norm, dnorm, partials)
         _lib.check(lib.spf_attn_backward_ext(C.byref(a), C.byref(g), C.byref(e), C.c_void_p(out.data_ptr()),
                                              C.c_void_p(lse.data_ptr()), C.c_void_p(dout.data_ptr()), stream),
                    "spf_attn_backward_ext")
-        return dnorm
-
-
-class _RopeAttention(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, k, v, qpos, kpos, base, F0, scale):
-        out, lse = attention_forward(q, k, v, qpos, kpos, base, F0, scale)
-        ctx.save_for_backward(q, k, v, qpos, kpos, out, lse)
-        ctx.cfg = (base, F0, scale)
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dout):
-        q, k, v, qpos, kpos, out, lse = ctx.saved_tensors
-        B, H, Nq, D = q.shape
-        Nk = k.shape[2]
-        # token-major buffers: the [B,H,N,D] views of them are what a following reshape(B, N, C) wants
-        dq = torch.empty(B, Nq, H, D, dtype=q.dtype, device=q.device).transpose(1, 2)
-        dk = torch.empty(B, Nk, H, D, dtype=q.dtype, device=q.device).transpose(1, 2)
-        dv = torch.empty(B, Nk, H, D, dtype=q.dtype, device=q.device).transpose(1, 2)
-        attention_backward(q, k, v, qpos, kpos, *ctx.cfg, out, lse, dout, dq, dk, dv)
-        need = ctx.needs_input_grad
-        return (dq if need[0] else None, dk if need[1] else None, dv if need[2] else None,
-                None, None, None, None, None)
-
-
-class _RopeAttentionPacked(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, qkv, pos, base, F0, scale):
-        q, k, v = _views(qkv)
-        out, lse = attention_forward(q, k, v, pos, pos, base, F0, scale)
-        ctx.save_for_backward(qkv, pos, out, lse)
-        ctx.cfg = (base, F0, scale)
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dout):
-        qkv, pos, out, lse = ctx.saved_tensors
-        q, k, v = _views(qkv)
-        dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
-        dq, dk, dv = _views(dqkv)
-        attention_backward(q, k, v, pos, pos, *ctx.cfg, out, lse, dout, dq, dk, dv)
-        return dqkv, None, None, None, None
+    return dnorm
 
 
 def _norm_args(q_norm, k_norm):
@@ -287,6 +237,11 @@ def _norm_args(q_norm, k_norm):
     return q_norm[0], q_norm[1], k_norm[0], k_norm[1], float(q_norm[2])
 
 
+def _norm_pair(qw, qb, kw, kb, eps):
+    """(q_norm, k_norm) back from the flat arguments."""
+    return ((qw, qb, eps), (kw, kb, eps)) if qw is not None else (None, None)
+
+
 def _norm_grads(ctx, first, dnorm):
     """Gradients of the four norm parameters at needs_input_grad[first:first + 4]."""
     if dnorm is None:
@@ -294,13 +249,20 @@ def _norm_grads(ctx, first, dnorm):
     return tuple(dnorm[i] if ctx.needs_input_grad[first + i] else None for i in range(4))
 
 
-class _RopeAttentionExt(torch.autograd.Function):
-    """_RopeAttention with a mask, the q / k LayerNorm or both (the flagged kernels)."""
+def _token_major(like, N):
+    """An empty [B,H,N,D] gradient for ``like`` [B,H,*,D] on a token-major buffer: such a view is what a following
+    reshape(B, N, C) wants."""
+    B, H, _, D = like.shape
+    return torch.empty(B, N, H, D, dtype=like.dtype, device=like.device).transpose(1, 2)
+
+
+class _RopeAttention(torch.autograd.Function):
+    """mask, qw .. kb: None on a plain call."""
 
     @staticmethod
     def forward(ctx, q, k, v, qpos, kpos, mask, qw, qb, kw, kb, eps, base, F0, scale):
-        norms = ((qw, qb, eps), (kw, kb, eps)) if qw is not None else (None, None)
-        out, lse = attention_forward(q, k, v, qpos, kpos, base, F0, scale, mask=mask, q_norm=norms[0], k_norm=norms[1])
+        q_norm, k_norm = _norm_pair(qw, qb, kw, kb, eps)
+        out, lse = attention_forward(q, k, v, qpos, kpos, base, F0, scale, mask=mask, q_norm=q_norm, k_norm=k_norm)
         ctx.save_for_backward(q, k, v, qpos, kpos, mask, qw, qb, kw, kb, out, lse)
         ctx.cfg = (base, F0, scale)
         ctx.eps = eps
@@ -310,27 +272,22 @@ class _RopeAttentionExt(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, dout):
         q, k, v, qpos, kpos, mask, qw, qb, kw, kb, out, lse = ctx.saved_tensors
-        norms = ((qw, qb, ctx.eps), (kw, kb, ctx.eps)) if qw is not None else (None, None)
-        B, H, Nq, D = q.shape
-        Nk = k.shape[2]
-        dq = torch.empty(B, Nq, H, D, dtype=q.dtype, device=q.device).transpose(1, 2)
-        dk = torch.empty(B, Nk, H, D, dtype=q.dtype, device=q.device).transpose(1, 2)
-        dv = torch.empty(B, Nk, H, D, dtype=q.dtype, device=q.device).transpose(1, 2)
-        dnorm = attention_backward(q, k, v, qpos, kpos, *ctx.cfg, out, lse, dout, dq, dk, dv, mask=mask, q_norm=norms[0],
-                                   k_norm=norms[1])
+        q_norm, k_norm = _norm_pair(qw, qb, kw, kb, ctx.eps)
+        dq, dk, dv = _token_major(q, q.shape[2]), _token_major(q, k.shape[2]), _token_major(q, k.shape[2])
+        dnorm = attention_backward(q, k, v, qpos, kpos, *ctx.cfg, out, lse, dout, dq, dk, dv, mask=mask, q_norm=q_norm,
+                                   k_norm=k_norm)
         need = ctx.needs_input_grad
         return (dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None, None,
                 *_norm_grads(ctx, 6, dnorm), None, None, None, None)
 
 
-class _RopeAttentionPackedExt(torch.autograd.Function):
-    """_RopeAttentionPacked with a mask, the q / k LayerNorm or both."""
+class _RopeAttentionPacked(torch.autograd.Function):
+    """mask, qw .. kb: None on a plain call."""
 
     @staticmethod
     def forward(ctx, qkv, pos, mask, qw, qb, kw, kb, eps, base, F0, scale):
-        q, k, v = _views(qkv)
-        norms = ((qw, qb, eps), (kw, kb, eps)) if qw is not None else (None, None)
-        out, lse = attention_forward(q, k, v, pos, pos, base, F0, scale, mask=mask, q_norm=norms[0], k_norm=norms[1])
+        q_norm, k_norm = _norm_pair(qw, qb, kw, kb, eps)
+        out, lse = attention_forward(*_views(qkv), pos, pos, base, F0, scale, mask=mask, q_norm=q_norm, k_norm=k_norm)
         ctx.save_for_backward(qkv, pos, mask, qw, qb, kw, kb, out, lse)
         ctx.cfg = (base, F0, scale)
         ctx.eps = eps
@@ -340,12 +297,10 @@ class _RopeAttentionPackedExt(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, dout):
         qkv, pos, mask, qw, qb, kw, kb, out, lse = ctx.saved_tensors
-        norms = ((qw, qb, ctx.eps), (kw, kb, ctx.eps)) if qw is not None else (None, None)
-        q, k, v = _views(qkv)
+        q_norm, k_norm = _norm_pair(qw, qb, kw, kb, ctx.eps)
         dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
-        dq, dk, dv = _views(dqkv)
-        dnorm = attention_backward(q, k, v, pos, pos, *ctx.cfg, out, lse, dout, dq, dk, dv, mask=mask, q_norm=norms[0],
-                                   k_norm=norms[1])
+        dnorm = attention_backward(*_views(qkv), pos, pos, *ctx.cfg, out, lse, dout, *_views(dqkv), mask=mask,
+                                   q_norm=q_norm, k_norm=k_norm)
         return (dqkv, None, None, *_norm_grads(ctx, 3, dnorm), None, None, None, None)
 
 
@@ -369,10 +324,8 @@ def rope_attention(q, k, v, qpos=None, kpos=None, *, base: float = 100.0, F0: fl
     _check(q, k, v, qpos, kpos, mask, q_norm, k_norm)
     if scale is None:
         scale = q.shape[3] ** -0.5
-    if mask is None and q_norm is None:
-        return _RopeAttention.apply(q, k, v, qpos, kpos, float(base), float(F0), float(scale))
-    return _RopeAttentionExt.apply(q, k, v, qpos, kpos, mask, *_norm_args(q_norm, k_norm), float(base), float(F0),
-                                   float(scale))
+    return _RopeAttention.apply(q, k, v, qpos, kpos, mask, *_norm_args(q_norm, k_norm), float(base), float(F0),
+                                float(scale))
 
 
 def rope_attention_packed(qkv, pos=None, *, base: float = 100.0, F0: float = 1.0, scale=None, mask=None, q_norm=None,
@@ -387,18 +340,16 @@ def rope_attention_packed(qkv, pos=None, *, base: float = 100.0, F0: float = 1.0
         qkv = qkv.contiguous()
     if scale is None:
         scale = qkv.shape[4] ** -0.5
-    if mask is None and q_norm is None:
-        return _RopeAttentionPacked.apply(qkv, pos, float(base), float(F0), float(scale))
-    return _RopeAttentionPackedExt.apply(qkv, pos, mask, *_norm_args(q_norm, k_norm), float(base), float(F0),
-                                         float(scale))
+    return _RopeAttentionPacked.apply(qkv, pos, mask, *_norm_args(q_norm, k_norm), float(base), float(F0), float(scale))
 
 
-def _rope_cfg(rope):
+def _rope_cfg(rope) -> dict:
+    """The rotation's keyword arguments of a rope_attention call; empty (false) without a rope."""
     if rope is None:
-        return None
+        return {}
     if not (hasattr(rope, "base") and hasattr(rope, "F0")):
         raise TypeError(f"rope must be a cuRoPE2D (base, F0) or None, got {type(rope).__name__}")
-    return float(rope.base), float(rope.F0)
+    return {"base": float(rope.base), "F0": float(rope.F0)}
 
 
 def _check_module(mod, mask=None) -> None:
@@ -432,10 +383,7 @@ class Attention(nn.Module):
         if not x.is_cuda:
             raise RuntimeError("Attention: x is on the CPU; this build only runs on a HIP device (no CPU fallback)")
         qkv = self.qkv(x).reshape(B, N, 3, self.num_heads, C // self.num_heads)
-        if cfg is None:
-            x = rope_attention_packed(qkv, None, scale=self.scale)
-        else:
-            x = rope_attention_packed(qkv, xpos, base=cfg[0], F0=cfg[1], scale=self.scale)
+        x = rope_attention_packed(qkv, xpos if cfg else None, scale=self.scale, **cfg)
         x = self.proj(x)
         x = self.proj_drop(x)
         return x
@@ -472,10 +420,7 @@ class CrossAttention(nn.Module):
         q = self.projq(query).reshape(B, Nq, H, D).permute(0, 2, 1, 3)
         k = self.projk(key).reshape(B, Nk, H, D).permute(0, 2, 1, 3)
         v = self.projv(value).reshape(B, Nv, H, D).permute(0, 2, 1, 3)
-        if cfg is None:
-            x = rope_attention(q, k, v, scale=self.scale)
-        else:
-            x = rope_attention(q, k, v, qpos, kpos, base=cfg[0], F0=cfg[1], scale=self.scale)
+        x = rope_attention(q, k, v, qpos if cfg else None, kpos if cfg else None, scale=self.scale, **cfg)
         x = self.proj(x)
         x = self.proj_drop(x)
         return x

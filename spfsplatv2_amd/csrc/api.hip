@@ -70,12 +70,10 @@ hipError_t launch_camera_fwd(const SpfCamera&, hipStream_t);
 hipError_t launch_camera_bwd(const SpfCamera&, const float*, float*, hipStream_t);
 hipError_t launch_camera_fwd_zero(const SpfCamera&, void*, uint64_t, hipStream_t);
 hipError_t launch_camera_bwd_reduce(const SpfCamera&, const float*, int, float*, hipStream_t);
-hipError_t launch_attn_forward(const SpfAttn&, void*, float*, hipStream_t);
-hipError_t launch_attn_backward(const SpfAttn&, const SpfAttnGrads&, const void*, const float*, const void*, hipStream_t);
+hipError_t launch_attn_forward(const SpfAttn&, const SpfAttnExt*, void*, float*, hipStream_t);
+hipError_t launch_attn_backward(const SpfAttn&, const SpfAttnGrads&, const SpfAttnExt*, const void*, const float*,
+                                const void*, hipStream_t);
 int64_t attn_ext_scratch_floats(int, int, int, int);
-hipError_t launch_attn_forward_ext(const SpfAttn&, const SpfAttnExt&, void*, float*, hipStream_t);
-hipError_t launch_attn_backward_ext(const SpfAttn&, const SpfAttnGrads&, const SpfAttnExt&, const void*, const float*,
-                                    const void*, hipStream_t);
 hipError_t launch_rope2d(void*, void*, const int64_t*, int, int, int, int, int64_t, int64_t, int64_t, int, int, float,
                          float, hipStream_t);
 }  // namespace spf
@@ -1055,28 +1053,29 @@ static const char* attn_args_error(const SpfAttn* a) {
     return nullptr;
 }
 
-int spf_attn_forward(const SpfAttn* args, void* out, float* lse, void* stream_) {
-    if (const char* e = attn_args_error(args)) return fail(SPF_E_INVALID, "%s", e);
-    if (!out || !lse) return fail(SPF_E_INVALID, "attention: out / lse is null");
-    if (reinterpret_cast<uintptr_t>(out) % 16 != 0) return fail(SPF_E_INVALID, "attention: rows of out must be 16-byte aligned");
-    SPF_HIP(spf::launch_attn_forward(*args, out, lse, static_cast<hipStream_t>(stream_)));
-    return SPF_OK;
+// a forward call: args, out, lse and alignment
+static const char* attn_forward_error(const SpfAttn* a, const void* out, const float* lse) {
+    if (const char* e = attn_args_error(a)) return e;
+    if (!out || !lse) return "attention: out / lse is null";
+    if (reinterpret_cast<uintptr_t>(out) % 16 != 0) return "attention: rows of out must be 16-byte aligned";
+    return nullptr;
 }
-
-int spf_attn_backward(const SpfAttn* args, const SpfAttnGrads* g, const void* out, const float* lse, const void* dout,
-                      void* stream_) {
-    if (const char* e = attn_args_error(args)) return fail(SPF_E_INVALID, "%s", e);
-    if (!g) return fail(SPF_E_INVALID, "attention: grads is null");
-    if (!out || !lse || !dout) return fail(SPF_E_INVALID, "attention: out / lse / dout is null");
-    if (!g->dq || !g->dk || !g->dv || !g->delta) return fail(SPF_E_INVALID, "attention: dq / dk / dv / delta is null");
-    const int es = args->dtype == 0 ? 4 : 2;
+// a backward call; ext: the extras with a mask or norm parameters, or null (its outputs are checked in their place)
+static const char* attn_backward_error(const SpfAttn* a, const SpfAttnGrads* g, const SpfAttnExt* ext, const void* out,
+                                       const float* lse, const void* dout) {
+    if (const char* e = attn_args_error(a)) return e;
+    if (!g) return "attention: grads is null";
+    if (!out || !lse || !dout) return "attention: out / lse / dout is null";
+    if (!g->dq || !g->dk || !g->dv || !g->delta) return "attention: dq / dk / dv / delta is null";
+    if (ext && ext->q_weight && (!ext->dq_weight || !ext->dq_bias || !ext->dk_weight || !ext->dk_bias || !ext->partials))
+        return "attention: dq_weight / dq_bias / dk_weight / dk_bias / partials is null";
+    const int es = a->dtype == 0 ? 4 : 2;
     if (reinterpret_cast<uintptr_t>(out) % 16 != 0 || reinterpret_cast<uintptr_t>(dout) % 16 != 0)
-        return fail(SPF_E_INVALID, "attention: rows of out and dout must be 16-byte aligned");
+        return "attention: rows of out and dout must be 16-byte aligned";
     if (!attn_rows_aligned(g->dq, g->dq_stride, es) || !attn_rows_aligned(g->dk, g->dk_stride, es) ||
         !attn_rows_aligned(g->dv, g->dv_stride, es))
-        return fail(SPF_E_INVALID, "attention: rows of dq, dk and dv must be 16-byte aligned");
-    SPF_HIP(spf::launch_attn_backward(*args, *g, out, lse, dout, static_cast<hipStream_t>(stream_)));
-    return SPF_OK;
+        return "attention: rows of dq, dk and dv must be 16-byte aligned";
+    return nullptr;
 }
 
 // the extras of an attention call: 0, or the message of the first one that is wrong
@@ -1094,6 +1093,21 @@ static const char* attn_ext_error(const SpfAttnExt* e) {
     if (given == 4 && !(e->eps >= 0.f)) return "attention: eps must not be negative";
     return nullptr;
 }
+// what the launch takes: null when the extras hold neither a mask nor norm parameters (the unflagged kernels)
+static const SpfAttnExt* attn_ext_or_null(const SpfAttnExt* e) { return e->mask || e->q_weight ? e : nullptr; }
+
+int spf_attn_forward(const SpfAttn* args, void* out, float* lse, void* stream_) {
+    if (const char* e = attn_forward_error(args, out, lse)) return fail(SPF_E_INVALID, "%s", e);
+    SPF_HIP(spf::launch_attn_forward(*args, nullptr, out, lse, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_attn_backward(const SpfAttn* args, const SpfAttnGrads* g, const void* out, const float* lse, const void* dout,
+                      void* stream_) {
+    if (const char* e = attn_backward_error(args, g, nullptr, out, lse, dout)) return fail(SPF_E_INVALID, "%s", e);
+    SPF_HIP(spf::launch_attn_backward(*args, *g, nullptr, out, lse, dout, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
 
 int64_t spf_attn_ext_scratch_floats(int32_t B, int32_t H, int32_t Nq, int32_t Nk) {
     if (B < 1 || H < 1 || Nq < 1 || Nk < 1 || B > 65535 || H > 65535) return -1;
@@ -1102,31 +1116,16 @@ int64_t spf_attn_ext_scratch_floats(int32_t B, int32_t H, int32_t Nq, int32_t Nk
 
 int spf_attn_forward_ext(const SpfAttn* args, const SpfAttnExt* ext, void* out, float* lse, void* stream_) {
     if (const char* e = attn_ext_error(ext)) return fail(SPF_E_INVALID, "%s", e);
-    if (!ext->mask && !ext->q_weight) return spf_attn_forward(args, out, lse, stream_);
-    if (const char* e = attn_args_error(args)) return fail(SPF_E_INVALID, "%s", e);
-    if (!out || !lse) return fail(SPF_E_INVALID, "attention: out / lse is null");
-    if (reinterpret_cast<uintptr_t>(out) % 16 != 0) return fail(SPF_E_INVALID, "attention: rows of out must be 16-byte aligned");
-    SPF_HIP(spf::launch_attn_forward_ext(*args, *ext, out, lse, static_cast<hipStream_t>(stream_)));
+    if (const char* e = attn_forward_error(args, out, lse)) return fail(SPF_E_INVALID, "%s", e);
+    SPF_HIP(spf::launch_attn_forward(*args, attn_ext_or_null(ext), out, lse, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
 
 int spf_attn_backward_ext(const SpfAttn* args, const SpfAttnGrads* g, const SpfAttnExt* ext, const void* out, const float* lse,
                           const void* dout, void* stream_) {
     if (const char* e = attn_ext_error(ext)) return fail(SPF_E_INVALID, "%s", e);
-    if (!ext->mask && !ext->q_weight) return spf_attn_backward(args, g, out, lse, dout, stream_);
-    if (const char* e = attn_args_error(args)) return fail(SPF_E_INVALID, "%s", e);
-    if (!g) return fail(SPF_E_INVALID, "attention: grads is null");
-    if (!out || !lse || !dout) return fail(SPF_E_INVALID, "attention: out / lse / dout is null");
-    if (!g->dq || !g->dk || !g->dv || !g->delta) return fail(SPF_E_INVALID, "attention: dq / dk / dv / delta is null");
-    if (ext->q_weight && (!ext->dq_weight || !ext->dq_bias || !ext->dk_weight || !ext->dk_bias || !ext->partials))
-        return fail(SPF_E_INVALID, "attention: dq_weight / dq_bias / dk_weight / dk_bias / partials is null");
-    const int es = args->dtype == 0 ? 4 : 2;
-    if (reinterpret_cast<uintptr_t>(out) % 16 != 0 || reinterpret_cast<uintptr_t>(dout) % 16 != 0)
-        return fail(SPF_E_INVALID, "attention: rows of out and dout must be 16-byte aligned");
-    if (!attn_rows_aligned(g->dq, g->dq_stride, es) || !attn_rows_aligned(g->dk, g->dk_stride, es) ||
-        !attn_rows_aligned(g->dv, g->dv_stride, es))
-        return fail(SPF_E_INVALID, "attention: rows of dq, dk and dv must be 16-byte aligned");
-    SPF_HIP(spf::launch_attn_backward_ext(*args, *g, *ext, out, lse, dout, static_cast<hipStream_t>(stream_)));
+    if (const char* e = attn_backward_error(args, g, ext, out, lse, dout)) return fail(SPF_E_INVALID, "%s", e);
+    SPF_HIP(spf::launch_attn_backward(*args, *g, attn_ext_or_null(ext), out, lse, dout, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
 

@@ -29,6 +29,8 @@
 // the online softmax and in both recomputations -- a row without any key gives out = 0, lse = -inf and zero gradients;
 // NORM applies LayerNorm(64) with weight and bias to every q and k row while it is staged, before the rotation, and its
 // backward in the epilogues of the two backward passes, with the parameter gradients summed from per-block partials.
+// The host part at the end is one path for every call: the extras are a nullable SpfAttnExt, and one dispatch picks the
+// instantiation from (element type, mask present, norm present) for both directions.
 #include "rope_math.h"
 
 namespace spf {
@@ -764,148 +766,116 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dq_kernel(typename ArgsOf<
     }
 }
 
-AttnArgs make_args(const SpfAttn& p) {
-    AttnArgs a;
+// The kernels' argument of a call: AttnArgs, and for a flagged instantiation (X) the extras behind it.
+template <bool X>
+typename ArgsOf<X>::type make_args(const SpfAttn& p, [[maybe_unused]] const SpfAttnExt* e) {
+    typename ArgsOf<X>::type a;
     a.q = p.q; a.k = p.k; a.v = p.v;
     a.qpos = p.qpos; a.kpos = p.kpos;
     for (int i = 0; i < 3; ++i) { a.qs[i] = p.q_stride[i]; a.ks[i] = p.k_stride[i]; a.vs[i] = p.v_stride[i]; }
     a.B = p.B; a.H = p.H; a.Nq = p.Nq; a.Nk = p.Nk;
     a.scale = p.scale;
     a.f = rope_freq(kAttnD, p.base, p.F0);
+    if constexpr (X) {
+        a.x.mask = e->mask;
+        for (int i = 0; i < 3; ++i) a.x.ms[i] = e->mask_stride[i];
+        a.x.mask_bool = e->mask_dtype != 0;
+        a.x.qw = e->q_weight; a.x.qb = e->q_bias; a.x.kw = e->k_weight; a.x.kb = e->k_bias;
+        a.x.eps = e->eps;
+        a.x.part = nullptr;
+    }
     return a;
 }
 
-template <typename T>
-hipError_t attn_forward_t(const SpfAttn& p, void* out, float* lse, hipStream_t stream) {
-    const dim3 grid((p.Nq + kAttnOwn - 1) / kAttnOwn, p.H, p.B);
-    spf_attn_fwd_kernel<T><<<grid, kBlock, 0, stream>>>(make_args(p), static_cast<T*>(out), lse);
-    return hipGetLastError();
-}
-
-AttnArgsX make_args_x(const SpfAttn& p, const SpfAttnExt& e) {
-    AttnArgsX a;
-    static_cast<AttnArgs&>(a) = make_args(p);
-    a.x.mask = e.mask;
-    for (int i = 0; i < 3; ++i) a.x.ms[i] = e.mask_stride[i];
-    a.x.mask_bool = e.mask_dtype != 0;
-    a.x.qw = e.q_weight; a.x.qb = e.q_bias; a.x.kw = e.k_weight; a.x.kb = e.k_bias;
-    a.x.eps = e.eps;
-    a.x.part = nullptr;
-    return a;
-}
-
-template <typename T, bool MASK, bool NORM>
-hipError_t attn_forward_x(const SpfAttn& p, const SpfAttnExt& e, void* out, float* lse, hipStream_t stream) {
-    const dim3 grid((p.Nq + kAttnOwn - 1) / kAttnOwn, p.H, p.B);
-    spf_attn_fwd_kernel<T, MASK, NORM><<<grid, kBlock, 0, stream>>>(make_args_x(p, e), static_cast<T*>(out), lse);
-    return hipGetLastError();
-}
-
-template <typename T, bool MASK, bool NORM>
-hipError_t attn_backward_x(const SpfAttn& p, const SpfAttnGrads& gr, const SpfAttnExt& e, const void* out, const float* lse,
-                           const void* dout, hipStream_t stream) {
-    AttnArgsX a = make_args_x(p, e);
+AttnGradArgs make_grad_args(const SpfAttnGrads& gr) {
     AttnGradArgs g;
     g.dq = gr.dq; g.dk = gr.dk; g.dv = gr.dv;
     for (int i = 0; i < 3; ++i) { g.dqs[i] = gr.dq_stride[i]; g.dks[i] = gr.dk_stride[i]; g.dvs[i] = gr.dv_stride[i]; }
+    return g;
+}
+
+inline int attn_blocks(int n) { return (n + kAttnOwn - 1) / kAttnOwn; }
+
+template <typename T, bool MASK, bool NORM>
+hipError_t attn_forward(const SpfAttn& p, const SpfAttnExt* e, void* out, float* lse, hipStream_t stream) {
+    spf_attn_fwd_kernel<T, MASK, NORM><<<dim3(attn_blocks(p.Nq), p.H, p.B), kBlock, 0, stream>>>(
+        make_args<MASK || NORM>(p, e), static_cast<T*>(out), lse);
+    return hipGetLastError();
+}
+
+template <typename T, bool MASK, bool NORM>
+hipError_t attn_backward(const SpfAttn& p, const SpfAttnGrads& gr, const SpfAttnExt* e, const void* out, const float* lse,
+                         const void* dout, hipStream_t stream) {
+    auto a = make_args<MASK || NORM>(p, e);
+    const AttnGradArgs g = make_grad_args(gr);
+    const T* go = static_cast<const T*>(dout);
     const int64_t rows = (int64_t)p.B * p.Nq * p.H;
-    const int qblk = (p.Nq + kAttnOwn - 1) / kAttnOwn, kblk = (p.Nk + kAttnOwn - 1) / kAttnOwn;
-    float* part_q = e.partials;
-    float* part_k = e.partials ? e.partials + (int64_t)p.B * p.H * qblk * 2 * kAttnD : nullptr;
+    const int qblk = attn_blocks(p.Nq), kblk = attn_blocks(p.Nk);
+    [[maybe_unused]] float *part_q = nullptr, *part_k = nullptr;    // NORM: the two passes' partials, q blocks first
+    if constexpr (NORM) {
+        part_q = e->partials;
+        part_k = e->partials + (int64_t)p.B * p.H * qblk * 2 * kAttnD;
+    }
     spf_attn_delta_kernel<T><<<(unsigned)((rows + kBlock - 1) / kBlock), kBlock, 0, stream>>>(
-        static_cast<const T*>(out), static_cast<const T*>(dout), gr.delta, p.B, p.H, p.Nq);
+        static_cast<const T*>(out), go, gr.delta, p.B, p.H, p.Nq);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
-    a.x.part = part_q;
-    spf_attn_dq_kernel<T, MASK, NORM><<<dim3(qblk, p.H, p.B), kBlock, 0, stream>>>(a, g, static_cast<const T*>(dout), lse,
-                                                                                  gr.delta);
-    err = hipGetLastError();
+    if constexpr (NORM) a.x.part = part_q;
+    spf_attn_dq_kernel<T, MASK, NORM><<<dim3(qblk, p.H, p.B), kBlock, 0, stream>>>(a, g, go, lse, gr.delta);
+    err = hipGetLastError();                                        // (dq settles delta: before the dk/dv pass)
     if (err != hipSuccess) return err;
-    a.x.part = part_k;
-    spf_attn_dkdv_kernel<T, MASK, NORM><<<dim3(kblk, p.H, p.B), kBlock, 0, stream>>>(a, g, static_cast<const T*>(dout), lse,
-                                                                                    gr.delta);
+    if constexpr (NORM) a.x.part = part_k;
+    spf_attn_dkdv_kernel<T, MASK, NORM><<<dim3(kblk, p.H, p.B), kBlock, 0, stream>>>(a, g, go, lse, gr.delta);
     err = hipGetLastError();
-    if (err != hipSuccess || !NORM) return err;
-    spf_attn_norm_reduce_kernel<<<1, kBlock, 0, stream>>>(part_q, p.B * p.H * qblk, e.dq_weight, e.dq_bias);
-    spf_attn_norm_reduce_kernel<<<1, kBlock, 0, stream>>>(part_k, p.B * p.H * kblk, e.dk_weight, e.dk_bias);
-    return hipGetLastError();
+    if constexpr (NORM) {
+        if (err != hipSuccess) return err;
+        spf_attn_norm_reduce_kernel<<<1, kBlock, 0, stream>>>(part_q, p.B * p.H * qblk, e->dq_weight, e->dq_bias);
+        spf_attn_norm_reduce_kernel<<<1, kBlock, 0, stream>>>(part_k, p.B * p.H * kblk, e->dk_weight, e->dk_bias);
+        err = hipGetLastError();
+    }
+    return err;
 }
 
-// the flagged instantiation for (element type, mask, norm)
-template <typename T, typename... A>
-hipError_t attn_forward_flags(bool mask, bool norm, A&&... args) {
-    if (mask && norm) return attn_forward_x<T, true, true>(args...);
-    return mask ? attn_forward_x<T, true, false>(args...) : attn_forward_x<T, false, true>(args...);
-}
-template <typename T, typename... A>
-hipError_t attn_backward_flags(bool mask, bool norm, A&&... args) {
-    if (mask && norm) return attn_backward_x<T, true, true>(args...);
-    return mask ? attn_backward_x<T, true, false>(args...) : attn_backward_x<T, false, true>(args...);
-}
-
-template <typename T>
-hipError_t attn_backward_t(const SpfAttn& p, const SpfAttnGrads& gr, const void* out, const float* lse, const void* dout,
-                           hipStream_t stream) {
-    const AttnArgs a = make_args(p);
-    AttnGradArgs g;
-    g.dq = gr.dq; g.dk = gr.dk; g.dv = gr.dv;
-    for (int i = 0; i < 3; ++i) { g.dqs[i] = gr.dq_stride[i]; g.dks[i] = gr.dk_stride[i]; g.dvs[i] = gr.dv_stride[i]; }
-    const int64_t rows = (int64_t)p.B * p.Nq * p.H;
-    spf_attn_delta_kernel<T><<<(unsigned)((rows + kBlock - 1) / kBlock), kBlock, 0, stream>>>(
-        static_cast<const T*>(out), static_cast<const T*>(dout), gr.delta, p.B, p.H, p.Nq);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    spf_attn_dq_kernel<T><<<dim3((p.Nq + kAttnOwn - 1) / kAttnOwn, p.H, p.B), kBlock, 0, stream>>>(
-        a, g, static_cast<const T*>(dout), lse, gr.delta);                  // (settles delta: before the dk/dv pass)
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    spf_attn_dkdv_kernel<T><<<dim3((p.Nk + kAttnOwn - 1) / kAttnOwn, p.H, p.B), kBlock, 0, stream>>>(
-        a, g, static_cast<const T*>(dout), lse, gr.delta);
-    return hipGetLastError();
+// The instantiation of a call: f(AttnKind<element type, mask present, norm present>()); e null: a plain call.
+template <typename T, bool MASK, bool NORM> struct AttnKind {
+    typedef T type;
+    static constexpr bool mask = MASK, norm = NORM;
+};
+template <typename F>
+hipError_t attn_dispatch(int dtype, const SpfAttnExt* e, F f) {
+    const bool mask = e && e->mask, norm = e && e->q_weight;
+    auto flags = [&](auto t) {
+        typedef decltype(t) T;
+        if (mask) return norm ? f(AttnKind<T, true, true>()) : f(AttnKind<T, true, false>());
+        return norm ? f(AttnKind<T, false, true>()) : f(AttnKind<T, false, false>());
+    };
+    switch (dtype) {
+        case 0: return flags(float());
+        case 1: return flags(__half());
+        default: return flags(__hip_bfloat16());
+    }
 }
 
 }  // namespace
 
-hipError_t launch_attn_forward(const SpfAttn& p, void* out, float* lse, hipStream_t stream) {
-    switch (p.dtype) {
-        case 0: return attn_forward_t<float>(p, out, lse, stream);
-        case 1: return attn_forward_t<__half>(p, out, lse, stream);
-        default: return attn_forward_t<__hip_bfloat16>(p, out, lse, stream);
-    }
+// e: the extras of the call, or null for a plain one (the caller has checked both).
+hipError_t launch_attn_forward(const SpfAttn& p, const SpfAttnExt* e, void* out, float* lse, hipStream_t stream) {
+    return attn_dispatch(p.dtype, e, [&](auto k) {
+        typedef decltype(k) K;
+        return attn_forward<typename K::type, K::mask, K::norm>(p, e, out, lse, stream);
+    });
 }
 
-hipError_t launch_attn_backward(const SpfAttn& p, const SpfAttnGrads& g, const void* out, const float* lse,
-                                const void* dout, hipStream_t stream) {
-    switch (p.dtype) {
-        case 0: return attn_backward_t<float>(p, g, out, lse, dout, stream);
-        case 1: return attn_backward_t<__half>(p, g, out, lse, dout, stream);
-        default: return attn_backward_t<__hip_bfloat16>(p, g, out, lse, dout, stream);
-    }
+hipError_t launch_attn_backward(const SpfAttn& p, const SpfAttnGrads& g, const SpfAttnExt* e, const void* out,
+                                const float* lse, const void* dout, hipStream_t stream) {
+    return attn_dispatch(p.dtype, e, [&](auto k) {
+        typedef decltype(k) K;
+        return attn_backward<typename K::type, K::mask, K::norm>(p, g, e, out, lse, dout, stream);
+    });
 }
 
 int64_t attn_ext_scratch_floats(int B, int H, int Nq, int Nk) {
-    const int64_t blocks = (Nq + kAttnOwn - 1) / kAttnOwn + (Nk + kAttnOwn - 1) / kAttnOwn;
-    return (int64_t)B * H * blocks * 2 * kAttnD;
-}
-
-// (the caller has checked that the extras hold a mask, the norm parameters or both)
-hipError_t launch_attn_forward_ext(const SpfAttn& p, const SpfAttnExt& e, void* out, float* lse, hipStream_t stream) {
-    const bool mask = e.mask != nullptr, norm = e.q_weight != nullptr;
-    switch (p.dtype) {
-        case 0: return attn_forward_flags<float>(mask, norm, p, e, out, lse, stream);
-        case 1: return attn_forward_flags<__half>(mask, norm, p, e, out, lse, stream);
-        default: return attn_forward_flags<__hip_bfloat16>(mask, norm, p, e, out, lse, stream);
-    }
-}
-
-hipError_t launch_attn_backward_ext(const SpfAttn& p, const SpfAttnGrads& g, const SpfAttnExt& e, const void* out,
-                                    const float* lse, const void* dout, hipStream_t stream) {
-    const bool mask = e.mask != nullptr, norm = e.q_weight != nullptr;
-    switch (p.dtype) {
-        case 0: return attn_backward_flags<float>(mask, norm, p, g, e, out, lse, dout, stream);
-        case 1: return attn_backward_flags<__half>(mask, norm, p, g, e, out, lse, dout, stream);
-        default: return attn_backward_flags<__hip_bfloat16>(mask, norm, p, g, e, out, lse, dout, stream);
-    }
+    return (int64_t)B * H * (attn_blocks(Nq) + attn_blocks(Nk)) * 2 * kAttnD;
 }
 
 }  // namespace spf

@@ -67,11 +67,9 @@ class VGGTAttention(nn.Module):
         if not x.is_cuda:
             raise RuntimeError("VGGTAttention: x is on the CPU; this build only runs on a HIP device (no CPU fallback)")
         qkv = self.qkv(x).reshape(B, N, 3, self.num_heads, self.head_dim)
-        if self.rope is None:
-            x = rope_attention_packed(qkv, None, scale=self.scale, mask=mask, q_norm=q_norm, k_norm=k_norm)
-        else:
-            x = rope_attention_packed(qkv, pos, base=float(self.rope.base_frequency), scale=self.scale, mask=mask,
-                                      q_norm=q_norm, k_norm=k_norm)
+        cfg = {"base": float(self.rope.base_frequency)} if self.rope is not None else {}
+        x = rope_attention_packed(qkv, pos if cfg else None, scale=self.scale, mask=mask, q_norm=q_norm, k_norm=k_norm,
+                                  **cfg)
         x = self.proj(x)
         x = self.proj_drop(x)
         return x

@@ -326,3 +326,59 @@ def test_module_against_the_reference_goldens(gold, name):
         figures.append((n, e_got, e_gold))
     for n, e_got, e_gold in figures:
         assert e_got <= 2 * e_gold + EPS, (name, n, e_got, e_gold)
+
+
+def test_selective_gradients_are_the_all_grad_run_bitwise():
+    """Only some inputs require grad: each gradient that is asked for is bitwise what the run with everything requiring
+    grad returns, in its own slot, and nothing else gets one.  N = 33: one owner block, partly empty, and two key tiles,
+    the second with one key; unpacked 33 queries on 40 keys."""
+    import spfsplatv2_amd as spf
+    B, H, N, Nk = 1, 2, 33, 40
+    gen = torch.Generator().manual_seed(3340)
+    qkv0 = torch.randn(B, N, 3, H, 64, generator=gen)
+    q0, k0, v0 = (torch.randn(B, n, H, 64, generator=gen).permute(0, 2, 1, 3) for n in (N, Nk, Nk))
+    qpos, kpos = (torch.randint(0, 8, (B, n, 2), generator=gen).to(DEV) for n in (N, Nk))
+    dout = torch.randn(B, N, H * 64, generator=gen).to(DEV)
+    params0 = [1.0 + 0.3 * torch.randn(64, generator=gen), 0.1 * torch.randn(64, generator=gen),
+               1.0 + 0.3 * torch.randn(64, generator=gen), 0.1 * torch.randn(64, generator=gen)]
+
+    def band(nk):                                       # keys 3 .. 8 past the row's own index are excluded
+        d = torch.arange(nk)[None, :] - torch.arange(N)[:, None]
+        m = torch.where((d >= 3) & (d < 9), NEG, 0.0)
+        assert every_row_has_a_key(m, (N, nk)) and int((m == NEG).sum()) >= 4 * N
+        return m.to(DEV)
+
+    def leaves(tensors, need):
+        return [t.to(DEV).requires_grad_(r) for t, r in zip(tensors, need)]
+
+    def norms(p):
+        return {"q_norm": (p[0], p[1], NORM_EPS), "k_norm": (p[2], p[3], NORM_EPS)}
+
+    def packed(need_params):
+        (qkv,), p = leaves([qkv0], [True]), leaves(params0, need_params)
+        spf.rope_attention_packed(qkv, qpos, mask=band(N), **norms(p)).backward(dout)
+        return qkv.grad, [t.grad for t in p]
+
+    base, base_p = packed([True] * 4)
+    assert all(g is not None for g in base_p)
+    some, some_p = packed([False, False, False, True])
+    assert torch.equal(some, base) and torch.equal(some_p[3], base_p[3])
+    assert some_p[0] is None and some_p[1] is None and some_p[2] is None
+
+    def unpacked(need, need_params):
+        t, p = leaves([q0, k0, v0], need), leaves(params0, need_params)
+        spf.rope_attention(*t, qpos, kpos, mask=band(Nk), **norms(p)).backward(dout)
+        return [x.grad for x in t]
+
+    base = unpacked([True] * 3, [True] * 4)
+    some = unpacked([False, True, False], [False] * 4)
+    assert torch.equal(some[1], base[1]) and some[0] is None and some[2] is None
+
+    def plain(need):
+        t = leaves([q0, k0, v0], need)
+        spf.rope_attention(*t, qpos, kpos).backward(dout)
+        return [x.grad for x in t]
+
+    base = plain([True] * 3)
+    some = plain([False, False, True])
+    assert torch.equal(some[2], base[2]) and some[0] is None and some[1] is None

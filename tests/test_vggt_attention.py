@@ -261,3 +261,60 @@ def test_scratch_size_comes_from_the_library(hip_lib):
     assert f(2, 3, 128, 129) == 2 * 3 * (1 + 2) * 128
     assert f(1, 16, 786, 786) == 16 * 14 * 128
     assert f(0, 1, 1, 1) == -1 and f(1, 1, 0, 1) == -1 and f(1, 70000, 1, 1) == -1
+
+
+def test_plain_and_empty_ext_calls_reject_alike(hip_lib):
+    """One checker behind both entry points: every invalid plain call gets the same code and the same message from
+    spf_attn_forward / spf_attn_backward and from the _ext twin with empty extras.  Nothing here reaches a launch."""
+    from spfsplatv2_amd import _lib
+    ok, off = C.c_void_p(4096), C.c_void_p(4100)
+    empty = _lib.SpfAttnExt()
+    odd = (C.c_int64 * 3)(1024, 130, 64)
+
+    def same(plain, ext, args, want):
+        ref = C.byref(args) if args is not None else None
+        rc = plain(ref)
+        msg = hip_lib.spf_last_error()
+        rc_ext = ext(ref)
+        msg_ext = hip_lib.spf_last_error()
+        assert rc == rc_ext == -1 and msg == msg_ext and want in msg, (want, rc, rc_ext, msg, msg_ext)
+
+    forward = [  # (args, out, lse, a piece of the message)
+        (None, ok, ok, b"args is null"),
+        (_attn(q=None), ok, ok, b"q / k / v is null"),
+        (_attn(qpos=4096), ok, ok, b"qpos and kpos must both"),
+        (_attn(kpos=4096), ok, ok, b"qpos and kpos must both"),
+        (_attn(D=32), ok, ok, b"head dim must be 64"),
+        (_attn(D=128), ok, ok, b"head dim must be 64"),
+        (_attn(B=0), ok, ok, b"must be positive"),
+        (_attn(H=65536), ok, ok, b"must not exceed 65535"),
+        (_attn(dtype=3), ok, ok, b"dtype must be"),
+        (_attn(q=4100), ok, ok, b"rows of q, k and v must be 16-byte aligned"),
+        (_attn(k_stride=odd), ok, ok, b"rows of q, k and v must be 16-byte aligned"),
+        (_attn(), None, ok, b"out / lse is null"),
+        (_attn(), ok, None, b"out / lse is null"),
+        (_attn(), off, ok, b"rows of out must be 16-byte aligned"),
+    ]
+    for args, out, lse, want in forward:
+        same(lambda a: hip_lib.spf_attn_forward(a, out, lse, None),
+             lambda a: hip_lib.spf_attn_forward_ext(a, C.byref(empty), out, lse, None), args, want)
+
+    def grads(**kw):
+        g = _lib.SpfAttnGrads()
+        g.dq = g.dk = g.dv = g.delta = 4096
+        g.dq_stride = g.dk_stride = g.dv_stride = (C.c_int64 * 3)(1024, 128, 64)
+        for k, v in kw.items():
+            setattr(g, k, v)
+        return g
+
+    backward = [  # (grads, dout, a piece of the message)
+        (None, ok, b"grads is null"),
+        (grads(), None, b"out / lse / dout is null"),
+        (grads(delta=None), ok, b"dq / dk / dv / delta is null"),
+        (grads(), off, b"rows of out and dout must be 16-byte aligned"),
+        (grads(dk_stride=odd), ok, b"rows of dq, dk and dv must be 16-byte aligned"),
+    ]
+    for g, dout, want in backward:
+        gref = C.byref(g) if g is not None else None
+        same(lambda a: hip_lib.spf_attn_backward(a, gref, ok, ok, dout, None),
+             lambda a: hip_lib.spf_attn_backward_ext(a, gref, C.byref(empty), ok, ok, dout, None), _attn(), want)
