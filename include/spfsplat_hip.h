@@ -61,7 +61,8 @@ extern "C" {
                               spf_focal_*): eight entry points added, nothing moved; spf_raster_state_layout likewise; and for the
                               fused attention (SpfAttn, SpfAttnGrads, spf_attn_forward, spf_attn_backward) and its
                               mask / q-k-LayerNorm extras (SpfAttnExt, spf_attn_forward_ext, spf_attn_backward_ext,
-                              spf_attn_ext_scratch_floats) */
+                              spf_attn_ext_scratch_floats) and its multi-view family (SpfAttnViews,
+                              spf_attn_views_forward, spf_attn_views_backward) */
 
 #define SPF_OK 0
 #define SPF_E_INVALID (-1)   /* bad argument (null pointer, size, unsupported degree ...) */
@@ -738,6 +739,34 @@ int64_t spf_attn_ext_scratch_floats(int32_t B, int32_t H, int32_t Nq, int32_t Nk
 int spf_attn_forward_ext(const SpfAttn* args, const SpfAttnExt* ext, void* out, float* lse, void* stream);
 int spf_attn_backward_ext(const SpfAttn* args, const SpfAttnGrads* grads, const SpfAttnExt* ext, const void* out,
                           const float* lse, const void* dout, void* stream);
+
+/* The same attention for a multi-view decoder's cross-attention (an additive family: nothing above moves; plain only,
+ * no mask and no q/k norm).  A scene has Vq query views and ONE set of Vk key views that all its query views share:
+ *   out[b,i] = softmax_j(scale * R(qpos[b,i]) q[b,i] * (R(kpos[b,s]) k[b,s,j])^T) v[b,s,j],
+ *   j over all tokens of all key views s with bit s of allow[i] set, views ascending
+ * -- the reference's expression on keys gathered per query view (backbone_croco_multiview.py generate_ctx_views), without
+ * the gather.  SpfAttn describes one (scene, view): B = scenes, q [B,Vq,H,Nq,64], k and v [B,Vk,H,Nk,64] with
+ * q_stride[0] / k_stride[0] / v_stride[0] the element stride between SCENES and the strides below between VIEWS, so a
+ * slice x[:, 1:] of a [b, v, l, c] projection is read in place.  qpos [B,Vq,Nq,2], kpos [B,Vk,Nk,2] int64 with contiguous
+ * (token, 2) rows, read through (scene, view) strides in int64 elements; both null: no rotation.  allow: a host-known
+ * table, the same for every scene, passed by value (Vq, Vk <= 32); every query view must read at least one key view.
+ * The gradients' scene strides are SpfAttnGrads' batch strides, their view strides are below; a key view that no query
+ * view reads gets zeros.  All view strides must keep rows 16-byte aligned, and the rows of one view must lie within
+ * 2^31 elements of its first (N * token stride; scenes and views are reached through 64-bit strides). */
+typedef struct SpfAttnViews {
+    int32_t Vq, Vk;
+    uint32_t allow[32];
+    int64_t q_view_stride, k_view_stride, v_view_stride;
+    int64_t qpos_stride[2], kpos_stride[2];
+    int64_t dq_view_stride, dk_view_stride, dv_view_stride;     /* backward only */
+} SpfAttnViews;
+/* out [B,Vq,Nq,H*64] contiguous (dtype), lse [B,Vq,H,Nq] float32.  Argument errors return SPF_E_INVALID before anything
+ * is launched; nothing is allocated or synchronised. */
+int spf_attn_views_forward(const SpfAttn* args, const SpfAttnViews* views, void* out, float* lse, void* stream);
+/* out, lse: what the forward wrote; dout [B,Vq,Nq,H*64] contiguous; grads->delta: B*Vq*H*Nq floats of scratch.  No
+ * atomics: every dq, dk, dv row is written once, in a fixed order of sums -- bitwise reproducible. */
+int spf_attn_views_backward(const SpfAttn* args, const SpfAttnViews* views, const SpfAttnGrads* grads, const void* out,
+                            const float* lse, const void* dout, void* stream);
 
 /* Per-stage device timing with HIP events recorded on the launch stream around every kernel
  * stage.  spf_stage_timing_enable(mask) clears the log and starts recording the stages whose bit

@@ -101,6 +101,13 @@ class SpfAttnExt(C.Structure):
                 ("dk_bias", C.c_void_p), ("partials", C.c_void_p)]
 
 
+class SpfAttnViews(C.Structure):
+    _fields_ = [("Vq", C.c_int32), ("Vk", C.c_int32), ("allow", C.c_uint32 * 32), ("q_view_stride", C.c_int64),
+                ("k_view_stride", C.c_int64), ("v_view_stride", C.c_int64), ("qpos_stride", C.c_int64 * 2),
+                ("kpos_stride", C.c_int64 * 2), ("dq_view_stride", C.c_int64), ("dk_view_stride", C.c_int64),
+                ("dv_view_stride", C.c_int64)]
+
+
 # Every symbol include/spfsplat_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "spf_abi_version": (C.c_int, []),
@@ -195,6 +202,9 @@ SYMBOLS = {
     "spf_attn_forward_ext": (C.c_int, [C.POINTER(SpfAttn), C.POINTER(SpfAttnExt), C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_attn_backward_ext": (C.c_int, [C.POINTER(SpfAttn), C.POINTER(SpfAttnGrads), C.POINTER(SpfAttnExt),
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_attn_views_forward": (C.c_int, [C.POINTER(SpfAttn), C.POINTER(SpfAttnViews), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_attn_views_backward": (C.c_int, [C.POINTER(SpfAttn), C.POINTER(SpfAttnViews), C.POINTER(SpfAttnGrads),
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_stage_timing_enable": (C.c_int, [C.c_int32]),
     "spf_stage_timing_sample_every": (C.c_int, [C.c_int32]),
     "spf_stage_times_ms": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_int32)]),

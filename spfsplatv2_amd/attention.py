@@ -10,6 +10,11 @@ here                       reference (src/model/encoder/backbone/croco/blocks.py
 ``CrossAttention``         ``CrossAttention`` (133-179)
 =========================  ============================================================================
 
+Multi-view decoders (backbone_croco_multiview.py:178-200, backbone_masked_croco.py:216-302) hand ``CrossAttention`` keys
+gathered per query view: every view's tokens copied into the key set of every other view.  ``rope_attention_views`` and
+``CrossAttention.forward_views`` compute the same result from ONE key set per scene, read in place, with a host-known
+table ``allow[query view][key view]``; ``decoder_view_sets`` builds the tables the two backbones' decoder blocks use.
+
 One kernel per direction of the data flow (csrc/attention.hip): the score matrix never exists in memory, q and k are
 rotated while they are staged, strided views are read in place.  Head dim 64 only; no dropout on the probabilities, no
 CPU path -- each of these raises before anything is launched.
@@ -343,6 +348,240 @@ def rope_attention_packed(qkv, pos=None, *, base: float = 100.0, F0: float = 1.0
     return _RopeAttentionPacked.apply(qkv, pos, mask, *_norm_args(q_norm, k_norm), float(base), float(F0), float(scale))
 
 
+# ---- multi-view: one key set per scene, whole views left out per query view ------------------------------------------
+MAX_VIEWS = 32
+
+
+def allow_words(allow):
+    """``allow`` ([Vq, Vk] bool CPU tensor or nested sequence: query view i may read key view s) as
+    ``(words, Vq, Vk)``: one 32-bit word per query view, bit s of word i set iff ``allow[i][s]``.  Host only."""
+    if isinstance(allow, torch.Tensor):
+        if allow.is_cuda:
+            raise RuntimeError("rope_attention_views: allow must be a CPU tensor (it is packed on the host and never "
+                               "touches the device)")
+        if allow.dtype != torch.bool:
+            raise RuntimeError(f"rope_attention_views: allow must be bool, got {allow.dtype}")
+        if allow.dim() != 2:
+            raise RuntimeError(f"rope_attention_views: allow must be [Vq, Vk], got {tuple(allow.shape)}")
+        rows = allow.tolist()
+    else:
+        try:
+            rows = [list(r) for r in allow]
+        except TypeError as e:
+            raise TypeError("rope_attention_views: allow must be a [Vq, Vk] bool tensor or a nested sequence") from e
+    Vq = len(rows)
+    Vk = len(rows[0]) if rows else 0
+    if any(len(r) != Vk for r in rows):
+        raise RuntimeError("rope_attention_views: the rows of allow differ in length")
+    if not (1 <= Vq <= MAX_VIEWS and 1 <= Vk <= MAX_VIEWS):
+        raise ValueError(f"rope_attention_views: Vq and Vk must be 1 .. {MAX_VIEWS}, got {Vq} and {Vk}")
+    words = [sum(1 << s for s, on in enumerate(r) if on) for r in rows]
+    for i, w in enumerate(words):
+        if w == 0:
+            raise ValueError(f"rope_attention_views: query view {i} is allowed no key view")
+    return words, Vq, Vk
+
+
+def _check_view_positions(name, tokens, positions) -> None:
+    if positions.dim() != 4 or tuple(positions.shape) != (tokens.shape[0], tokens.shape[1], tokens.shape[3], 2):
+        raise RuntimeError(f"rope_attention_views: {name} must be [b, V, N, 2] = "
+                           f"{[tokens.shape[0], tokens.shape[1], tokens.shape[3], 2]}, got {list(positions.shape)}")
+    if positions.dtype != torch.int64:
+        raise RuntimeError("positions must be int64")
+    if positions.device != tokens.device:
+        raise RuntimeError("tokens and positions are not on the same device")
+
+
+def _check_views(q, k, v, qpos, kpos, words, Vq, Vk) -> None:
+    for t in (q, k, v):
+        if t.dim() != 5:
+            raise RuntimeError("rope_attention_views: q, k and v must have 5 dimensions [b, V, H, N, 64]")
+        if t.shape[4] != HEAD_DIM:
+            raise ValueError(f"rope_attention: head dim must be {HEAD_DIM}, got {t.shape[4]}")
+        if t.dtype not in _DTYPES:
+            raise RuntimeError(f"rope_attention: unsupported dtype {t.dtype}")
+    if not (q.dtype == k.dtype == v.dtype):
+        raise RuntimeError(f"rope_attention: q, k and v differ in dtype ({q.dtype}, {k.dtype}, {v.dtype})")
+    if not (q.device == k.device == v.device):
+        raise RuntimeError("rope_attention: q, k and v are not on the same device")
+    if k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
+        raise RuntimeError(f"rope_attention_views: shapes differ: q {tuple(q.shape)}, k {tuple(k.shape)}, "
+                           f"v {tuple(v.shape)}")
+    if (q.shape[1], k.shape[1]) != (Vq, Vk):
+        raise RuntimeError(f"rope_attention_views: allow is [{Vq}, {Vk}] but q has {q.shape[1]} views and k has "
+                           f"{k.shape[1]}")
+    if (qpos is None) != (kpos is None):
+        raise RuntimeError("rope_attention: qpos and kpos must both be given or both be None")
+    if qpos is not None:
+        _check_view_positions("qpos", q, qpos)
+        _check_view_positions("kpos", k, kpos)
+    if not q.is_cuda:
+        raise RuntimeError("rope_attention: q, k and v are on the CPU; this build only runs on a HIP device "
+                           "(no CPU fallback)")
+
+
+def _rows5(t: torch.Tensor) -> torch.Tensor:
+    """``_rows`` for [b, V, H, N, D]."""
+    es = t.element_size()
+    if t.stride(4) == 1 and t.data_ptr() % 16 == 0 and all((t.stride(i) * es) % 16 == 0 for i in range(4)):
+        return t
+    return t.contiguous()
+
+
+def _pos_rows(p):
+    """Positions [b, V, N, 2] whose (token, 2) rows are contiguous: read in place through (scene, view) strides."""
+    if p is None or (p.stride(3) == 1 and p.stride(2) == 2) or p.shape[2] == 1 and p.stride(3) == 1:
+        return p
+    return p.contiguous()
+
+
+def _strides5(t: torch.Tensor):
+    """(scene, token, head) element strides of a [b, V, H, N, D] tensor."""
+    return (C.c_int64 * 3)(t.stride(0), t.stride(3), t.stride(2))
+
+
+def _view_args(q, k, v, qpos, kpos, words, base, F0, scale):
+    b, Vq, H, Nq, D = q.shape
+    a = _lib.SpfAttn()
+    a.q, a.k, a.v = q.data_ptr(), k.data_ptr(), v.data_ptr()
+    a.qpos = qpos.data_ptr() if qpos is not None else None
+    a.kpos = kpos.data_ptr() if kpos is not None else None
+    a.q_stride, a.k_stride, a.v_stride = _strides5(q), _strides5(k), _strides5(v)
+    a.B, a.H, a.Nq, a.Nk, a.D, a.dtype = b, H, Nq, k.shape[3], D, _DTYPES[q.dtype]
+    a.base, a.F0, a.scale = float(base), float(F0), float(scale)
+    w = _lib.SpfAttnViews()
+    w.Vq, w.Vk = Vq, k.shape[1]
+    w.allow = (C.c_uint32 * 32)(*words)
+    w.q_view_stride, w.k_view_stride, w.v_view_stride = q.stride(1), k.stride(1), v.stride(1)
+    if qpos is not None:
+        w.qpos_stride = (C.c_int64 * 2)(qpos.stride(0), qpos.stride(1))
+        w.kpos_stride = (C.c_int64 * 2)(kpos.stride(0), kpos.stride(1))
+    return a, w
+
+
+def attention_views_forward(q, k, v, qpos, kpos, words, base, F0, scale):
+    """The forward launch: (out [b,Vq,Nq,H*D], lse [b,Vq,H,Nq] float32).  q [b,Vq,H,Nq,64], k and v [b,Vk,H,Nk,64]: views,
+    read in place; ``words``: what ``allow_words`` returned."""
+    _check_views(q, k, v, qpos, kpos, words, len(words), k.shape[1] if k.dim() == 5 else 0)
+    q, k, v, qpos, kpos = _rows5(q), _rows5(k), _rows5(v), _pos_rows(qpos), _pos_rows(kpos)
+    b, Vq, H, Nq, D = q.shape
+    out = torch.empty(b, Vq, Nq, H * D, dtype=q.dtype, device=q.device)
+    lse = torch.empty(b, Vq, H, Nq, dtype=torch.float32, device=q.device)
+    lib = _lib.load()
+    with torch.cuda.device(q.device):
+        stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        a, w = _view_args(q, k, v, qpos, kpos, words, base, F0, scale)
+        _lib.check(lib.spf_attn_views_forward(C.byref(a), C.byref(w), C.c_void_p(out.data_ptr()),
+                                              C.c_void_p(lse.data_ptr()), stream), "spf_attn_views_forward")
+    return out, lse
+
+
+def attention_views_backward(q, k, v, qpos, kpos, words, base, F0, scale, out, lse, dout, dq, dk, dv):
+    """The backward launches: writes dq [b,Vq,H,Nq,64], dk, dv [b,Vk,H,Nk,64] (any views with 16-byte aligned rows, e.g.
+    slices of larger tensors), every row once; a key view nobody reads gets zeros."""
+    _check_views(q, k, v, qpos, kpos, words, len(words), k.shape[1] if k.dim() == 5 else 0)
+    if dq.shape != q.shape or dk.shape != k.shape or dv.shape != v.shape:
+        raise RuntimeError("rope_attention_views: dq, dk and dv must have the shapes of q, k and v")
+    if any(t.stride(4) != 1 or t.dtype != q.dtype for t in (dq, dk, dv)):
+        raise RuntimeError("rope_attention_views: dq, dk and dv must have unit stride along D and the inputs' dtype")
+    q, k, v, qpos, kpos = _rows5(q), _rows5(k), _rows5(v), _pos_rows(qpos), _pos_rows(kpos)
+    out, dout = out.contiguous(), dout.contiguous()
+    if dout.dtype != q.dtype or out.dtype != q.dtype:
+        raise RuntimeError(f"rope_attention: gradient dtype {dout.dtype} differs from the inputs' {q.dtype}")
+    b, Vq, H, Nq, D = q.shape
+    delta = torch.empty(b, Vq, H, Nq, dtype=torch.float32, device=q.device)
+    lib = _lib.load()
+    with torch.cuda.device(q.device):
+        stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        a, w = _view_args(q, k, v, qpos, kpos, words, base, F0, scale)
+        w.dq_view_stride, w.dk_view_stride, w.dv_view_stride = dq.stride(1), dk.stride(1), dv.stride(1)
+        g = _lib.SpfAttnGrads()
+        g.dq, g.dk, g.dv, g.delta = dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr()
+        g.dq_stride, g.dk_stride, g.dv_stride = _strides5(dq), _strides5(dk), _strides5(dv)
+        _lib.check(lib.spf_attn_views_backward(C.byref(a), C.byref(w), C.byref(g), C.c_void_p(out.data_ptr()),
+                                               C.c_void_p(lse.data_ptr()), C.c_void_p(dout.data_ptr()), stream),
+                   "spf_attn_views_backward")
+
+
+def _token_major5(like, V, N):
+    """An empty [b,V,H,N,D] gradient on a token-major buffer (what a following reshape(b, V, N, C) wants)."""
+    b, _, H, _, D = like.shape
+    return torch.empty(b, V, N, H, D, dtype=like.dtype, device=like.device).transpose(2, 3)
+
+
+class _RopeAttentionViews(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, qpos, kpos, words, base, F0, scale):
+        out, lse = attention_views_forward(q, k, v, qpos, kpos, words, base, F0, scale)
+        ctx.save_for_backward(q, k, v, qpos, kpos, out, lse)
+        ctx.cfg = (words, base, F0, scale)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        q, k, v, qpos, kpos, out, lse = ctx.saved_tensors
+        dq = _token_major5(q, q.shape[1], q.shape[3])
+        dk, dv = _token_major5(q, k.shape[1], k.shape[3]), _token_major5(q, k.shape[1], k.shape[3])
+        attention_views_backward(q, k, v, qpos, kpos, *ctx.cfg, out, lse, dout, dq, dk, dv)
+        need = ctx.needs_input_grad
+        return (dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None, None, None, None,
+                None)
+
+
+def rope_attention_views(q, k, v, qpos=None, kpos=None, *, allow, base: float = 100.0, F0: float = 1.0, scale=None):
+    """Cross-attention of a scene's query views over ONE shared set of key views, whole views left out per query view:
+
+        out[b,i] = softmax_j(scale * rope(q[b,i], qpos[b,i]) @ rope(k[b,s,j], kpos[b,s])^T) @ v[b,s,j],
+                   j over all tokens of all key views s with allow[i][s], views ascending
+
+    -- what ``rope_attention`` returns for query batch item (b, i) on the keys of the allowed views gathered in
+    ascending order, without the gather.  q [b,Vq,H,Nq,64], k and v [b,Vk,H,Nk,64]: views with unit stride along D and
+    16-byte aligned rows are read in place (``x[:, 1:]`` of a projection included).  qpos [b,Vq,Nq,2], kpos [b,Vk,Nk,2]:
+    int64 (y, x); both None: no rotation.  allow: [Vq, Vk] bool CPU tensor or nested sequence, Vq, Vk <= 32, at least one
+    key view per query view; it is packed into one word per query view on the host and never touches the device.
+    Returns [b,Vq,Nq,H*64].  The gradient of a key view is written once (no atomics, bitwise reproducible) and is exact
+    zeros for a key view nobody reads."""
+    words, Vq, Vk = allow_words(allow)
+    _check_views(q, k, v, qpos, kpos, words, Vq, Vk)
+    if scale is None:
+        scale = q.shape[4] ** -0.5
+    return _RopeAttentionViews.apply(q, k, v, qpos, kpos, tuple(words), float(base), float(F0), float(scale))
+
+
+class ViewSet(tuple):
+    """(query view slice, key view slice, allow [Vq, Vk] bool CPU tensor) of one decoder block."""
+    __slots__ = ()
+
+    def __new__(cls, query, key, allow):
+        return super().__new__(cls, (query, key, allow))
+
+    query = property(lambda self: self[0])
+    key = property(lambda self: self[1])
+    allow = property(lambda self: self[2])
+
+
+def decoder_view_sets(v: int, num_target: int = 0):
+    """The view sets of the two decoder blocks of the multi-view backbones, as ``(blk1, blk2)`` of
+    ``ViewSet(query view slice, key view slice, allow)``; ``v`` views of which the last ``num_target`` are targets,
+    ``vc = v - num_target`` context views.
+
+    blk1 (backbone_croco_multiview.py:191, backbone_masked_croco.py's first branch): query view 0 over key views
+    1 .. vc-1, all allowed.  blk2: query views 1 .. v-1 over key views 0 .. v-1 with ``allow[i][s]`` iff ``s != i`` and
+    (``i >= vc`` or ``s < vc``): a context view sees the other context views, a target view sees every other view --
+    ONE call where the masked backbone makes one for the context and one for the target queries.  Host code only."""
+    v, num_target = int(v), int(num_target)
+    vc = v - num_target
+    if num_target < 0 or vc < 2:
+        raise ValueError(f"decoder_view_sets: {v} views with {num_target} targets leave {vc} context views; blk1 needs "
+                         "at least 2 (view 0 would have no keys)")
+    if v > MAX_VIEWS:
+        raise ValueError(f"decoder_view_sets: at most {MAX_VIEWS} views, got {v}")
+    allow1 = torch.ones(1, vc - 1, dtype=torch.bool)
+    allow2 = torch.tensor([[s != i and (i >= vc or s < vc) for s in range(v)] for i in range(1, v)], dtype=torch.bool)
+    return ViewSet(slice(0, 1), slice(1, vc), allow1), ViewSet(slice(1, v), slice(0, v), allow2)
+
+
 def _rope_cfg(rope) -> dict:
     """The rotation's keyword arguments of a rope_attention call; empty (false) without a rope."""
     if rope is None:
@@ -421,6 +660,36 @@ class CrossAttention(nn.Module):
         k = self.projk(key).reshape(B, Nk, H, D).permute(0, 2, 1, 3)
         v = self.projv(value).reshape(B, Nv, H, D).permute(0, 2, 1, 3)
         x = rope_attention(q, k, v, qpos if cfg else None, kpos if cfg else None, scale=self.scale, **cfg)
+        x = self.proj(x)
+        x = self.proj_drop(x)
+        return x
+
+    def forward_views(self, query, key, qpos, kpos, allow):
+        """The layer on a scene's views without gathered keys: query [b,Vq,Nq,C], key [b,Vk,Nk,C] (key and value, as at
+        every call site of the reference), qpos [b,Vq,Nq,2], kpos [b,Vk,Nk,2], allow [Vq,Vk] (``rope_attention_views``).
+        ``projk`` and ``projv`` run ONCE over the b*Vk*Nk key tokens; returns [b,Vq,Nq,C].  Same parameters as
+        ``forward``."""
+        _check_module(self)
+        if query.dim() != 4 or key.dim() != 4:
+            raise RuntimeError("CrossAttention.forward_views: query and key must be [b, V, N, C]")
+        b, Vq, Nq, C_ = query.shape
+        _, Vk, Nk, _ = key.shape
+        H, D = self.num_heads, C_ // self.num_heads
+        if D != HEAD_DIM:
+            raise ValueError(f"rope_attention: head dim must be {HEAD_DIM}, got {D}")
+        words, aq, ak = allow_words(allow)
+        if (aq, ak) != (Vq, Vk) or key.shape[0] != b:
+            raise RuntimeError(f"CrossAttention.forward_views: allow is [{aq}, {ak}], query {tuple(query.shape)}, key "
+                               f"{tuple(key.shape)}")
+        cfg = _rope_cfg(self.rope)
+        if not query.is_cuda:
+            raise RuntimeError("CrossAttention: query is on the CPU; this build only runs on a HIP device "
+                               "(no CPU fallback)")
+        q = self.projq(query).reshape(b, Vq, Nq, H, D).transpose(2, 3)
+        k = self.projk(key).reshape(b, Vk, Nk, H, D).transpose(2, 3)
+        v = self.projv(key).reshape(b, Vk, Nk, H, D).transpose(2, 3)
+        x = rope_attention_views(q, k, v, qpos if cfg else None, kpos if cfg else None, allow=allow, scale=self.scale,
+                                 **cfg)
         x = self.proj(x)
         x = self.proj_drop(x)
         return x

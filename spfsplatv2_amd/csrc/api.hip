@@ -74,6 +74,9 @@ hipError_t launch_attn_forward(const SpfAttn&, const SpfAttnExt*, void*, float*,
 hipError_t launch_attn_backward(const SpfAttn&, const SpfAttnGrads&, const SpfAttnExt*, const void*, const float*,
                                 const void*, hipStream_t);
 int64_t attn_ext_scratch_floats(int, int, int, int);
+hipError_t launch_attn_views_forward(const SpfAttn&, const SpfAttnViews&, void*, float*, hipStream_t);
+hipError_t launch_attn_views_backward(const SpfAttn&, const SpfAttnViews&, const SpfAttnGrads&, const void*, const float*,
+                                      const void*, hipStream_t);
 hipError_t launch_rope2d(void*, void*, const int64_t*, int, int, int, int, int64_t, int64_t, int64_t, int, int, float,
                          float, hipStream_t);
 }  // namespace spf
@@ -1126,6 +1129,46 @@ int spf_attn_backward_ext(const SpfAttn* args, const SpfAttnGrads* g, const SpfA
     if (const char* e = attn_ext_error(ext)) return fail(SPF_E_INVALID, "%s", e);
     if (const char* e = attn_backward_error(args, g, ext, out, lse, dout)) return fail(SPF_E_INVALID, "%s", e);
     SPF_HIP(spf::launch_attn_backward(*args, *g, attn_ext_or_null(ext), out, lse, dout, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+// the views of a multi-view attention call (args has passed attn_args_error): 0, or the message of the first thing wrong
+static const char* attn_views_error(const SpfAttn* a, const SpfAttnViews* w) {
+    if (!w) return "attention: views is null";
+    if (w->Vq < 1 || w->Vq > 32 || w->Vk < 1 || w->Vk > 32) return "attention: Vq and Vk must be 1 .. 32";
+    const uint32_t known = w->Vk == 32 ? 0xffffffffu : (1u << w->Vk) - 1u;
+    for (int i = 0; i < w->Vq; ++i) {
+        if (w->allow[i] == 0) return "attention: a query view is allowed no key view";
+        if (w->allow[i] & ~known) return "attention: allow names a key view at or above Vk";
+    }
+    if ((int64_t)a->B * w->Vq > 65535 || (int64_t)a->B * w->Vk > 65535) return "attention: B * Vq and B * Vk must not exceed 65535";
+    const int es = a->dtype == 0 ? 4 : 2;
+    if ((w->q_view_stride * es) % 16 != 0 || (w->k_view_stride * es) % 16 != 0 || (w->v_view_stride * es) % 16 != 0)
+        return "attention: rows of q, k and v must be 16-byte aligned";
+    // the kernels form a lane's offset INTO a view in 32 bits (the views themselves are reached through 64-bit strides)
+    const int64_t lim = (int64_t)1 << 31;
+    if (a->q_stride[1] < 0 || a->k_stride[1] < 0 || a->v_stride[1] < 0 || (int64_t)a->Nq * a->q_stride[1] + 64 >= lim ||
+        (int64_t)a->Nk * a->k_stride[1] + 64 >= lim || (int64_t)a->Nk * a->v_stride[1] + 64 >= lim ||
+        (int64_t)a->Nq * a->H * 64 >= lim)
+        return "attention: the rows of one view must lie within 2^31 elements";
+    return nullptr;
+}
+
+int spf_attn_views_forward(const SpfAttn* args, const SpfAttnViews* views, void* out, float* lse, void* stream_) {
+    if (const char* e = attn_forward_error(args, out, lse)) return fail(SPF_E_INVALID, "%s", e);
+    if (const char* e = attn_views_error(args, views)) return fail(SPF_E_INVALID, "%s", e);
+    SPF_HIP(spf::launch_attn_views_forward(*args, *views, out, lse, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_attn_views_backward(const SpfAttn* args, const SpfAttnViews* views, const SpfAttnGrads* g, const void* out,
+                            const float* lse, const void* dout, void* stream_) {
+    if (const char* e = attn_backward_error(args, g, nullptr, out, lse, dout)) return fail(SPF_E_INVALID, "%s", e);
+    if (const char* e = attn_views_error(args, views)) return fail(SPF_E_INVALID, "%s", e);
+    const int es = args->dtype == 0 ? 4 : 2;
+    if ((views->dq_view_stride * es) % 16 != 0 || (views->dk_view_stride * es) % 16 != 0 || (views->dv_view_stride * es) % 16 != 0)
+        return fail(SPF_E_INVALID, "attention: rows of dq, dk and dv must be 16-byte aligned");
+    SPF_HIP(spf::launch_attn_views_backward(*args, *views, *g, out, lse, dout, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
 

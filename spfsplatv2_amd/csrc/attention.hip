@@ -31,6 +31,12 @@
 // backward in the epilogues of the two backward passes, with the parameter gradients summed from per-block partials.
 // The host part at the end is one path for every call: the extras are a nullable SpfAttnExt, and one dispatch picks the
 // instantiation from (element type, mask present, norm present) for both directions.
+//
+// A third feature, VIEWS (plain only: neither MASK nor NORM), serves the multi-view decoder's cross-attention: a batch
+// item of the owner side is a (scene, view) pair, the keys of a scene are ONE [Vk] set of views shared by all of that
+// scene's query views, and query view i reads key view s iff bit s of a host-known word allow[i] is set.  The walk over
+// the other side becomes a walk over the allowed views in ascending order and, inside, over each view's tiles; an
+// excluded view is never loaded.  Everything about views is a function of blockIdx and kernel arguments: scalar registers.
 #include "rope_math.h"
 
 namespace spf {
@@ -71,8 +77,30 @@ struct AttnExt {
 struct AttnArgsX : AttnArgs {
     AttnExt x;
 };
-template <bool X> struct ArgsOf { typedef AttnArgs type; };
-template <> struct ArgsOf<true> { typedef AttnArgsX type; };
+// What the VIEWS instantiations read on top of AttnArgs (B = scenes; qs[0] / ks[0] / vs[0] = the stride between scenes).
+// words: forward and dq pass, [query view] = the key views it reads; dk/dv pass, [key view] = the query views that read it
+// (the transpose, formed on the host).  Strides in elements; positions [scene][view][token][2] through two strides.
+struct AttnViews {
+    int Vq, Vk;
+    uint32_t words[32];
+    int64_t qv, kv, vv;             // between views
+    int64_t qpb, qpv, kpb, kpv;     // positions: between scenes, between views
+    int64_t dqv, dkv, dvv;          // gradients: between views (between scenes: AttnGradArgs' batch stride)
+};
+struct AttnArgsV : AttnArgs {
+    AttnViews w;
+};
+template <bool X, bool V = false> struct ArgsOf { typedef AttnArgs type; };
+template <> struct ArgsOf<true, false> { typedef AttnArgsX type; };
+template <> struct ArgsOf<false, true> { typedef AttnArgsV type; };
+// A word of views is walked by DISTANCE, so that a kernel keeps the pointers of the view it is loading and nothing else:
+// `rest` holds the views above the current one, bit 0 = the next; this returns how many views ahead the next set one is
+// (>= 1) and shifts it out.  Before the first view `rest` is the whole word, and the result minus 1 is that view.
+__device__ __forceinline__ int view_step(uint32_t& rest) {
+    const int d = __builtin_ctz(rest);
+    rest = rest >> d >> 1;                              // (two shifts: d + 1 may be 32)
+    return d + 1;
+}
 
 template <typename T> __device__ __forceinline__ void load4(const T* p, float* f);
 template <> __device__ __forceinline__ void load4<float>(const float* p, float* f) {
@@ -105,16 +133,21 @@ template <> __device__ __forceinline__ void store4<__hip_bfloat16>(__hip_bfloat1
 struct Stage {
     float u[4], v[4], p;
 };
-template <typename T>
+// NARROW (the VIEWS kernels, whose `base` moves from view to view): the lane's offset into the view is formed in 32
+// bits -- a uniform base plus a 32-bit lane offset is one address register per lane instead of two, which is what keeps
+// the VIEWS dk/dv pass inside its plain sibling's registers; the host refuses a view whose rows reach past 2^31 elements.
+template <typename T, bool NARROW = false>
 __device__ __forceinline__ void stage_load(Stage& r, const T* __restrict__ base, int64_t stride_n,
                                            const int64_t* __restrict__ pos, int row0, int N, int tid) {
     const int row = row0 + (tid >> 3), part = tid & 7, x = part >> 2, q0 = (part & 3) * 4;
     r.p = 0.f;
     if (row < N) {
-        const T* __restrict__ s = base + (int64_t)row * stride_n + 32 * x + q0;
+        const T* __restrict__ s;
+        if constexpr (NARROW) s = base + (uint32_t)(row * (int)stride_n + 32 * x + q0);
+        else s = base + (int64_t)row * stride_n + 32 * x + q0;
         load4<T>(s, r.u);
         load4<T>(s + 16, r.v);
-        if (pos) r.p = (float)pos[(int64_t)row * 2 + x];
+        if (pos) r.p = NARROW ? (float)pos[(uint32_t)(row * 2 + x)] : (float)pos[(int64_t)row * 2 + x];
     } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) r.u[k] = r.v[k] = 0.f;
@@ -304,18 +337,36 @@ __device__ __forceinline__ void store_row(T* __restrict__ g, f16v acc0, f16v acc
 }
 
 // ---- forward -------------------------------------------------------------------------------------------------------
-template <typename T, bool MASK = false, bool NORM = false>
-__global__ __launch_bounds__(kBlock) void spf_attn_fwd_kernel(typename ArgsOf<MASK || NORM>::type a, T* __restrict__ out,
+// VIEWS: b = (scene, query view) is the batch item of out and lse; the keys walked are the views of word a.w.words[view]
+// of the scene, in ascending order.  kb, vb, kp then point at the view being LOADED (the prefetch runs one tile ahead and
+// hops to the next allowed view when the current one is used up), which nothing after a tile's commit depends on.
+template <typename T, bool MASK = false, bool NORM = false, bool VIEWS = false>
+__global__ __launch_bounds__(kBlock) void spf_attn_fwd_kernel(typename ArgsOf<MASK || NORM, VIEWS>::type a, T* __restrict__ out,
                                                               float* __restrict__ lse) {
+    static_assert(!(VIEWS && (MASK || NORM)), "VIEWS is plain only");
     __shared__ float s_k[kAttnT * kAttnLd];
     __shared__ float s_v[kAttnT * kAttnLd];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, il = lane & 31, kl = lane >> 5;
     const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * kAttnOwn;
-    const T* __restrict__ qb = static_cast<const T*>(a.q) + b * a.qs[0] + h * a.qs[2];
-    const T* __restrict__ kb = static_cast<const T*>(a.k) + b * a.ks[0] + h * a.ks[2];
-    const T* __restrict__ vb = static_cast<const T*>(a.v) + b * a.vs[0] + h * a.vs[2];
+    int sb = b;                                         // the batch item of q, k, v: the scene when VIEWS
+    if constexpr (VIEWS) sb = b / a.w.Vq;
+    const T* __restrict__ qb = static_cast<const T*>(a.q) + sb * a.qs[0] + h * a.qs[2];
+    const T* __restrict__ kb = static_cast<const T*>(a.k) + sb * a.ks[0] + h * a.ks[2];
+    const T* __restrict__ vb = static_cast<const T*>(a.v) + sb * a.vs[0] + h * a.vs[2];
     const int64_t* __restrict__ qp = a.qpos ? a.qpos + (int64_t)b * a.Nq * 2 : nullptr;
     const int64_t* __restrict__ kp = a.kpos ? a.kpos + (int64_t)b * a.Nk * 2 : nullptr;
+    [[maybe_unused]] uint32_t rest = 0;                 // VIEWS: the allowed views not yet loaded
+    [[maybe_unused]] bool more = false;                 // VIEWS: a next view's first tile is in flight
+    if constexpr (VIEWS) {
+        const int vi = b - sb * a.w.Vq;
+        qb += vi * a.w.qv;
+        qp = a.qpos ? a.qpos + sb * a.w.qpb + vi * a.w.qpv : nullptr;
+        rest = a.w.words[vi];                           // (never 0: the host refuses a query view without keys)
+        const int s = view_step(rest) - 1;
+        kb += s * a.w.kv;
+        vb += s * a.w.vv;
+        kp = a.kpos ? a.kpos + sb * a.w.kpb + s * a.w.kpv : nullptr;
+    }
 
     float qr[32], unused[32];
     if constexpr (NORM) {
@@ -337,6 +388,8 @@ __global__ __launch_bounds__(kBlock) void spf_attn_fwd_kernel(typename ArgsOf<MA
     stage_load<T>(sk, kb, a.ks[1], kp, 0, a.Nk, tid);
     stage_load<T>(sv, vb, a.vs[1], nullptr, 0, a.Nk, tid);
 #pragma unroll 1
+    do {                                                // VIEWS: one round per allowed view; else one round
+#pragma unroll 1
     for (int k0 = 0; k0 < a.Nk; k0 += kAttnT) {
         f16v s;                                         // S^T: rows = keys, column = this lane's query
         if constexpr (MASK) {
@@ -350,7 +403,23 @@ __global__ __launch_bounds__(kBlock) void spf_attn_fwd_kernel(typename ArgsOf<MA
         stage_commit(sk, s_k, kp != nullptr, a.f, 1.f, tid);
         stage_commit(sv, s_v, false, a.f, 1.f, tid);
         __syncthreads();
-        if (k0 + kAttnT < a.Nk) {                       // in flight under the matrix instructions below
+        if constexpr (VIEWS) {                          // the next tile: of this view, or the first of the next allowed one
+            int n0 = k0 + kAttnT;
+            if (n0 >= a.Nk) {                           // the view is used up: hop (scalar work only)
+                more = rest != 0;
+                if (more) {
+                    const int d = view_step(rest);
+                    kb += d * a.w.kv;
+                    vb += d * a.w.vv;
+                    if (kp) kp += d * a.w.kpv;
+                    n0 = 0;
+                }
+            }
+            if (n0 < a.Nk) {                            // ONE load site: in flight under the matrix instructions below
+                stage_load<T, true>(sk, kb, a.ks[1], kp, n0, a.Nk, tid);
+                stage_load<T, true>(sv, vb, a.vs[1], nullptr, n0, a.Nk, tid);
+            }
+        } else if (k0 + kAttnT < a.Nk) {                // in flight under the matrix instructions below
             stage_load<T>(sk, kb, a.ks[1], kp, k0 + kAttnT, a.Nk, tid);
             stage_load<T>(sv, vb, a.vs[1], nullptr, k0 + kAttnT, a.Nk, tid);
         }
@@ -391,6 +460,7 @@ __global__ __launch_bounds__(kBlock) void spf_attn_fwd_kernel(typename ArgsOf<MA
             o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[32], s[r], o1, 0, 0, 0);
         }
     }
+    } while (VIEWS && more);
     if (!active) return;
     const float lt = l + __shfl_xor(l, 32, kWave);
     if (qi >= a.Nq) return;
@@ -529,8 +599,11 @@ __global__ __launch_bounds__(kBlock) void spf_attn_delta_kernel(const T* __restr
 }
 
 // dk, dv: the block owns 128 keys, walks the queries.
-template <typename T, bool MASK = false, bool NORM = false>
-__global__ __launch_bounds__(kBlock, 2) void spf_attn_dkdv_kernel(typename ArgsOf<MASK || NORM>::type a, AttnGradArgs g,
+// VIEWS: b = (scene, key view); the queries walked are those of the views in a.w.words[key view], ascending, then each
+// view's tiles ascending -- one fixed order, each dk / dv row written once.  A key view nobody reads walks nothing and
+// stores the zeros the accumulators start from.
+template <typename T, bool MASK = false, bool NORM = false, bool VIEWS = false>
+__global__ __launch_bounds__(kBlock, 2) void spf_attn_dkdv_kernel(typename ArgsOf<MASK || NORM, VIEWS>::type a, AttnGradArgs g,
                                                                const T* __restrict__ dout,
                                                                const float* __restrict__ lse,
                                                                const float* __restrict__ delta) {
@@ -538,16 +611,46 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dkdv_kernel(typename ArgsO
     __shared__ float s_do[kAttnT * kAttnLd];
     __shared__ float s_lse[kAttnT], s_dl[kAttnT];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, il = lane & 31, kl = lane >> 5;
+    static_assert(!(VIEWS && (MASK || NORM)), "VIEWS is plain only");
     const int b = blockIdx.z, h = blockIdx.y, k0 = blockIdx.x * kAttnOwn;
-    const T* __restrict__ qb = static_cast<const T*>(a.q) + b * a.qs[0] + h * a.qs[2];
-    const T* __restrict__ kb = static_cast<const T*>(a.k) + b * a.ks[0] + h * a.ks[2];
-    const T* __restrict__ vb = static_cast<const T*>(a.v) + b * a.vs[0] + h * a.vs[2];
+    int sb = b;                                         // the batch item of q, k, v: the scene when VIEWS
+    if constexpr (VIEWS) sb = b / a.w.Vk;
+    const T* __restrict__ qb = static_cast<const T*>(a.q) + sb * a.qs[0] + h * a.qs[2];
+    const T* __restrict__ kb = static_cast<const T*>(a.k) + sb * a.ks[0] + h * a.ks[2];
+    const T* __restrict__ vb = static_cast<const T*>(a.v) + sb * a.vs[0] + h * a.vs[2];
     const T* __restrict__ gb = dout + ((int64_t)b * a.Nq * a.H + h) * kAttnD;
     const int64_t g_sn = (int64_t)a.H * kAttnD;
     const int64_t* __restrict__ qp = a.qpos ? a.qpos + (int64_t)b * a.Nq * 2 : nullptr;
     const int64_t* __restrict__ kp = a.kpos ? a.kpos + (int64_t)b * a.Nk * 2 : nullptr;
     const float* __restrict__ lse_r = lse + ((int64_t)b * a.H + h) * a.Nq;
     const float* __restrict__ dl_r = delta + ((int64_t)b * a.H + h) * a.Nq;
+    [[maybe_unused]] uint32_t rest = 0;                 // VIEWS: the reading query views not yet loaded
+    [[maybe_unused]] bool more = false;                 // VIEWS: a next view's first tile is in flight
+    // VIEWS: move the query side (q, its positions, dout, lse, delta) d query views ahead
+    [[maybe_unused]] auto hop = [&](int d) {
+        if constexpr (VIEWS) {
+            const int64_t rows = (int64_t)d * a.H * a.Nq;       // (dout, lse and delta are contiguous)
+            qb += d * a.w.qv;
+            if (qp) qp += d * a.w.qpv;
+            gb += rows * kAttnD;
+            lse_r += rows;
+            dl_r += rows;
+        }
+    };
+    if constexpr (VIEWS) {
+        const int kview = b - sb * a.w.Vk;
+        const int64_t bq = (int64_t)sb * a.w.Vq;        // query view 0 of the scene
+        kb += kview * a.w.kv;
+        vb += kview * a.w.vv;
+        kp = a.kpos ? a.kpos + sb * a.w.kpb + kview * a.w.kpv : nullptr;
+        qp = a.qpos ? a.qpos + sb * a.w.qpb : nullptr;
+        gb = dout + (bq * a.Nq * a.H + h) * kAttnD;
+        lse_r = lse + (bq * a.H + h) * a.Nq;
+        dl_r = delta + (bq * a.H + h) * a.Nq;
+        rest = a.w.words[kview];
+        more = rest != 0;                               // (0: nobody reads this view)
+        if (more) hop(view_step(rest) - 1);
+    }
 
     float kr[32], vr[32];
     if constexpr (NORM) {
@@ -566,9 +669,12 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dkdv_kernel(typename ArgsO
     for (int e = 0; e < 16; ++e) dk0[e] = dk1[e] = dv0[e] = dv1[e] = 0.f;
     Stage sq, sd;
     float rl = INFINITY, rd = 0.f;                      // a padded query: probability 0
+    if (!VIEWS || more) {
     stage_load<T>(sq, qb, a.qs[1], qp, 0, a.Nq, tid);
     stage_load<T>(sd, gb, g_sn, nullptr, 0, a.Nq, tid);
     if (tid < kAttnT && tid < a.Nq) { rl = lse_r[tid]; rd = dl_r[tid]; }
+#pragma unroll 1
+    do {                                                // VIEWS: one round per reading query view; else one round
 #pragma unroll 1
     for (int q0 = 0; q0 < a.Nq; q0 += kAttnT) {
         f16v s, dp;                                     // S, dP: rows = queries, column = this lane's key
@@ -585,7 +691,22 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dkdv_kernel(typename ArgsO
         stage_commit(sd, s_do, false, a.f, 1.f, tid);
         if (tid < kAttnT) { s_lse[tid] = rl; s_dl[tid] = rd; }
         __syncthreads();
-        if (q0 + kAttnT < a.Nq) {
+        if constexpr (VIEWS) {                          // the next tile: of this view, or the first of the next reading one
+            int n0 = q0 + kAttnT;
+            if (n0 >= a.Nq) {                           // the view is used up: hop (scalar work only)
+                more = rest != 0;
+                if (more) {
+                    hop(view_step(rest));
+                    n0 = 0;
+                }
+            }
+            if (n0 < a.Nq) {                            // ONE load site
+                stage_load<T, true>(sq, qb, a.qs[1], qp, n0, a.Nq, tid);
+                stage_load<T, true>(sd, gb, g_sn, nullptr, n0, a.Nq, tid);
+                rl = INFINITY; rd = 0.f;
+                if (tid < kAttnT && n0 + tid < a.Nq) { rl = lse_r[n0 + tid]; rd = dl_r[n0 + tid]; }
+            }
+        } else if (q0 + kAttnT < a.Nq) {
             stage_load<T>(sq, qb, a.qs[1], qp, q0 + kAttnT, a.Nq, tid);
             stage_load<T>(sd, gb, g_sn, nullptr, q0 + kAttnT, a.Nq, tid);
             rl = INFINITY; rd = 0.f;
@@ -619,6 +740,8 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dkdv_kernel(typename ArgsO
             dk1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qrow[32], dp[r], dk1, 0, 0, 0);
         }
     }
+    } while (VIEWS && more);
+    }
     if constexpr (NORM) {
         const int key = okey;
         const bool valid = active && key < a.Nk;
@@ -635,8 +758,10 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dkdv_kernel(typename ArgsO
         if (!active) return;
         const int key = k0 + kAttnT * wave + il;
         if (key >= a.Nk) return;
-        store_row<T>(static_cast<T*>(g.dv) + b * g.dvs[0] + (int64_t)key * g.dvs[1] + h * g.dvs[2], dv0, dv1, 1.f, nullptr, a.f, kl);
-        store_row<T>(static_cast<T*>(g.dk) + b * g.dks[0] + (int64_t)key * g.dks[1] + h * g.dks[2], dk0, dk1, 1.f,
+        int64_t dv_view = 0, dk_view = 0;
+        if constexpr (VIEWS) { dv_view = (b - sb * a.w.Vk) * a.w.dvv; dk_view = (b - sb * a.w.Vk) * a.w.dkv; }
+        store_row<T>(static_cast<T*>(g.dv) + sb * g.dvs[0] + dv_view + (int64_t)key * g.dvs[1] + h * g.dvs[2], dv0, dv1, 1.f, nullptr, a.f, kl);
+        store_row<T>(static_cast<T*>(g.dk) + sb * g.dks[0] + dk_view + (int64_t)key * g.dks[1] + h * g.dks[2], dk0, dk1, 1.f,
                      kp ? kp + (int64_t)key * 2 : nullptr, a.f, kl);
     }
 }
@@ -647,21 +772,37 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dkdv_kernel(typename ArgsO
 // accumulates c = sum_j p[j] (dP[j] - delta~) (tiny: the residual of delta~) and B = sum_j p[j] k[j] next to
 // A = sum_j p[j] (dP[j] - delta~) k[j], returns dq = scale (A - c B) -- the gradient with delta = sum_j p[j] dP[j], the
 // softmax backward's own row sum -- and writes delta~ + c back for the dk/dv pass, which recomputes the same dP bits.
-template <typename T, bool MASK = false, bool NORM = false>
-__global__ __launch_bounds__(kBlock, 2) void spf_attn_dq_kernel(typename ArgsOf<MASK || NORM>::type a, AttnGradArgs g,
+// VIEWS: as in the forward -- b = (scene, query view), the keys are the allowed views' in ascending order.
+template <typename T, bool MASK = false, bool NORM = false, bool VIEWS = false>
+__global__ __launch_bounds__(kBlock, 2) void spf_attn_dq_kernel(typename ArgsOf<MASK || NORM, VIEWS>::type a, AttnGradArgs g,
                                                              const T* __restrict__ dout,
                                                              const float* __restrict__ lse,
                                                              float* __restrict__ delta) {
     __shared__ float s_k[kAttnT * kAttnLd];
     __shared__ float s_v[kAttnT * kAttnLd];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, il = lane & 31, kl = lane >> 5;
+    static_assert(!(VIEWS && (MASK || NORM)), "VIEWS is plain only");
     const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * kAttnOwn;
-    const T* __restrict__ qb = static_cast<const T*>(a.q) + b * a.qs[0] + h * a.qs[2];
-    const T* __restrict__ kb = static_cast<const T*>(a.k) + b * a.ks[0] + h * a.ks[2];
-    const T* __restrict__ vb = static_cast<const T*>(a.v) + b * a.vs[0] + h * a.vs[2];
+    int sb = b;                                         // the batch item of q, k, v: the scene when VIEWS
+    if constexpr (VIEWS) sb = b / a.w.Vq;
+    const T* __restrict__ qb = static_cast<const T*>(a.q) + sb * a.qs[0] + h * a.qs[2];
+    const T* __restrict__ kb = static_cast<const T*>(a.k) + sb * a.ks[0] + h * a.ks[2];
+    const T* __restrict__ vb = static_cast<const T*>(a.v) + sb * a.vs[0] + h * a.vs[2];
     const T* __restrict__ gb = dout + ((int64_t)b * a.Nq * a.H + h) * kAttnD;
     const int64_t* __restrict__ qp = a.qpos ? a.qpos + (int64_t)b * a.Nq * 2 : nullptr;
     const int64_t* __restrict__ kp = a.kpos ? a.kpos + (int64_t)b * a.Nk * 2 : nullptr;
+    [[maybe_unused]] uint32_t rest = 0;                 // VIEWS: the allowed views not yet loaded
+    [[maybe_unused]] bool more = false;                 // VIEWS: a next view's first tile is in flight
+    if constexpr (VIEWS) {
+        const int vi = b - sb * a.w.Vq;
+        qb += vi * a.w.qv;
+        qp = a.qpos ? a.qpos + sb * a.w.qpb + vi * a.w.qpv : nullptr;
+        rest = a.w.words[vi];                           // (never 0: the host refuses a query view without keys)
+        const int s = view_step(rest) - 1;
+        kb += s * a.w.kv;
+        vb += s * a.w.vv;
+        kp = a.kpos ? a.kpos + sb * a.w.kpb + s * a.w.kpv : nullptr;
+    }
 
     float qr[32], gr[32];
     if constexpr (NORM) {
@@ -689,6 +830,8 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dq_kernel(typename ArgsOf<
     stage_load<T>(sk, kb, a.ks[1], kp, 0, a.Nk, tid);
     stage_load<T>(sv, vb, a.vs[1], nullptr, 0, a.Nk, tid);
 #pragma unroll 1
+    do {                                                // VIEWS: one round per allowed view; else one round
+#pragma unroll 1
     for (int k0 = 0; k0 < a.Nk; k0 += kAttnT) {
         f16v s, dp;                                     // S^T, dP^T: rows = keys, column = this lane's query
         if constexpr (MASK) {
@@ -702,7 +845,23 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dq_kernel(typename ArgsOf<
         stage_commit(sk, s_k, kp != nullptr, a.f, 1.f, tid);
         stage_commit(sv, s_v, false, a.f, 1.f, tid);
         __syncthreads();
-        if (k0 + kAttnT < a.Nk) {
+        if constexpr (VIEWS) {                          // the next tile, as in the forward
+            int n0 = k0 + kAttnT;
+            if (n0 >= a.Nk) {
+                more = rest != 0;
+                if (more) {
+                    const int d = view_step(rest);
+                    kb += d * a.w.kv;
+                    vb += d * a.w.vv;
+                    if (kp) kp += d * a.w.kpv;
+                    n0 = 0;
+                }
+            }
+            if (n0 < a.Nk) {
+                stage_load<T, true>(sk, kb, a.ks[1], kp, n0, a.Nk, tid);
+                stage_load<T, true>(sv, vb, a.vs[1], nullptr, n0, a.Nk, tid);
+            }
+        } else if (k0 + kAttnT < a.Nk) {
             stage_load<T>(sk, kb, a.ks[1], kp, k0 + kAttnT, a.Nk, tid);
             stage_load<T>(sv, vb, a.vs[1], nullptr, k0 + kAttnT, a.Nk, tid);
         }
@@ -734,7 +893,9 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dq_kernel(typename ArgsOf<
             pk1 = __builtin_amdgcn_mfma_f32_32x32x2f32(k1v, s[r], pk1, 0, 0, 0);
         }
     }
-    T* __restrict__ dq_row = static_cast<T*>(g.dq) + b * g.dqs[0] + (int64_t)qi * g.dqs[1] + h * g.dqs[2];
+    } while (VIEWS && more);
+    T* __restrict__ dq_row = static_cast<T*>(g.dq) + sb * g.dqs[0] + (int64_t)qi * g.dqs[1] + h * g.dqs[2];
+    if constexpr (VIEWS) dq_row += (b - sb * a.w.Vq) * a.w.dqv;
     if constexpr (NORM) {
         const bool valid = active && qi < a.Nq;
         const float c = cres + __shfl_xor(cres, 32, kWave);
@@ -856,7 +1017,70 @@ hipError_t attn_dispatch(int dtype, const SpfAttnExt* e, F f) {
     }
 }
 
+// ---- VIEWS: the host part ---------------------------------------------------------------------------------------------
+// words: SpfAttnViews.allow itself (forward, dq pass) or its transpose (dk/dv pass)
+AttnArgsV make_view_args(const SpfAttn& p, const SpfAttnViews& w, bool transpose) {
+    AttnArgsV a;
+    static_cast<AttnArgs&>(a) = make_args<false>(p, nullptr);
+    a.w.Vq = w.Vq; a.w.Vk = w.Vk;
+    for (int i = 0; i < 32; ++i) a.w.words[i] = 0;
+    for (int i = 0; i < w.Vq; ++i)
+        for (int s = 0; s < w.Vk; ++s)
+            if (w.allow[i] >> s & 1u) {
+                if (transpose) a.w.words[s] |= 1u << i;
+                else a.w.words[i] |= 1u << s;
+            }
+    a.w.qv = w.q_view_stride; a.w.kv = w.k_view_stride; a.w.vv = w.v_view_stride;
+    a.w.qpb = w.qpos_stride[0]; a.w.qpv = w.qpos_stride[1];
+    a.w.kpb = w.kpos_stride[0]; a.w.kpv = w.kpos_stride[1];
+    a.w.dqv = w.dq_view_stride; a.w.dkv = w.dk_view_stride; a.w.dvv = w.dv_view_stride;
+    return a;
+}
+
+template <typename T>
+hipError_t attn_views_forward(const SpfAttn& p, const SpfAttnViews& w, void* out, float* lse, hipStream_t stream) {
+    spf_attn_fwd_kernel<T, false, false, true><<<dim3(attn_blocks(p.Nq), p.H, p.B * w.Vq), kBlock, 0, stream>>>(
+        make_view_args(p, w, false), static_cast<T*>(out), lse);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t attn_views_backward(const SpfAttn& p, const SpfAttnViews& w, const SpfAttnGrads& gr, const void* out,
+                               const float* lse, const void* dout, hipStream_t stream) {
+    const AttnGradArgs g = make_grad_args(gr);
+    const T* go = static_cast<const T*>(dout);
+    const int64_t rows = (int64_t)p.B * w.Vq * p.Nq * p.H;
+    spf_attn_delta_kernel<T><<<(unsigned)((rows + kBlock - 1) / kBlock), kBlock, 0, stream>>>(
+        static_cast<const T*>(out), go, gr.delta, p.B * w.Vq, p.H, p.Nq);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return err;
+    spf_attn_dq_kernel<T, false, false, true><<<dim3(attn_blocks(p.Nq), p.H, p.B * w.Vq), kBlock, 0, stream>>>(
+        make_view_args(p, w, false), g, go, lse, gr.delta);
+    err = hipGetLastError();                                        // (dq settles delta: before the dk/dv pass)
+    if (err != hipSuccess) return err;
+    spf_attn_dkdv_kernel<T, false, false, true><<<dim3(attn_blocks(p.Nk), p.H, p.B * w.Vk), kBlock, 0, stream>>>(
+        make_view_args(p, w, true), g, go, lse, gr.delta);
+    return hipGetLastError();
+}
+
 }  // namespace
+
+hipError_t launch_attn_views_forward(const SpfAttn& p, const SpfAttnViews& w, void* out, float* lse, hipStream_t stream) {
+    switch (p.dtype) {
+        case 0: return attn_views_forward<float>(p, w, out, lse, stream);
+        case 1: return attn_views_forward<__half>(p, w, out, lse, stream);
+        default: return attn_views_forward<__hip_bfloat16>(p, w, out, lse, stream);
+    }
+}
+
+hipError_t launch_attn_views_backward(const SpfAttn& p, const SpfAttnViews& w, const SpfAttnGrads& g, const void* out,
+                                      const float* lse, const void* dout, hipStream_t stream) {
+    switch (p.dtype) {
+        case 0: return attn_views_backward<float>(p, w, g, out, lse, dout, stream);
+        case 1: return attn_views_backward<__half>(p, w, g, out, lse, dout, stream);
+        default: return attn_views_backward<__hip_bfloat16>(p, w, g, out, lse, dout, stream);
+    }
+}
 
 // e: the extras of the call, or null for a plain one (the caller has checked both).
 hipError_t launch_attn_forward(const SpfAttn& p, const SpfAttnExt* e, void* out, float* lse, hipStream_t stream) {
