@@ -62,7 +62,8 @@ extern "C" {
                               fused attention (SpfAttn, SpfAttnGrads, spf_attn_forward, spf_attn_backward) and its
                               mask / q-k-LayerNorm extras (SpfAttnExt, spf_attn_forward_ext, spf_attn_backward_ext,
                               spf_attn_ext_scratch_floats) and its multi-view family (SpfAttnViews,
-                              spf_attn_views_forward, spf_attn_views_backward) */
+                              spf_attn_views_forward, spf_attn_views_backward) and the opt-in 16-bit matrix path of
+                              the plain call (spf_attn16_forward, spf_attn16_backward) */
 
 #define SPF_OK 0
 #define SPF_E_INVALID (-1)   /* bad argument (null pointer, size, unsupported degree ...) */
@@ -702,6 +703,16 @@ int spf_attn_forward(const SpfAttn* args, void* out, float* lse, void* stream);
 /* out, lse: what the forward wrote; dout [B,Nq,H*64] contiguous.  No atomics: bitwise reproducible. */
 int spf_attn_backward(const SpfAttn* args, const SpfAttnGrads* grads, const void* out, const float* lse,
                       const void* dout, void* stream);
+
+/* The same two calls on the 16-bit matrix units (an additive, opt-in family: nothing above moves): dtype must be 1
+ * (float16) or 2 (bfloat16); every product runs on the 32x32x16 f16 / bf16 matrix instructions with float32 accumulators.
+ * q and k are rotated in float32 and rounded once to the element type; the score, the softmax statistics, lse, delta, the
+ * scale factor and the gradients' rotate-back stay float32; the probabilities (and dS in the backward) are rounded once
+ * to the element type as operands; out, dq, dk and dv are rounded at the store.  Same arguments, same checks and messages
+ * as spf_attn_forward / spf_attn_backward; nothing is allocated or synchronised; no atomics: bitwise reproducible. */
+int spf_attn16_forward(const SpfAttn* args, void* out, float* lse, void* stream);
+int spf_attn16_backward(const SpfAttn* args, const SpfAttnGrads* grads, const void* out, const float* lse,
+                        const void* dout, void* stream);
 
 /* The same attention with the two things vggt/layers/attention.py adds (an additive family: SpfAttn, SpfAttnGrads and
  * the two entry points above do not move):

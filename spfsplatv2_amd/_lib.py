@@ -198,6 +198,9 @@ SYMBOLS = {
     "spf_attn_forward": (C.c_int, [C.POINTER(SpfAttn), C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_attn_backward": (C.c_int, [C.POINTER(SpfAttn), C.POINTER(SpfAttnGrads),
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_attn16_forward": (C.c_int, [C.POINTER(SpfAttn), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_attn16_backward": (C.c_int, [C.POINTER(SpfAttn), C.POINTER(SpfAttnGrads),
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_attn_ext_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "spf_attn_forward_ext": (C.c_int, [C.POINTER(SpfAttn), C.POINTER(SpfAttnExt), C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_attn_backward_ext": (C.c_int, [C.POINTER(SpfAttn), C.POINTER(SpfAttnGrads), C.POINTER(SpfAttnExt),

@@ -23,6 +23,12 @@ CPU path -- each of these raises before anything is launched.
 (vggt_attention.py) and CroCo's two classes here do not use: ``mask`` (additive float32 or bool, broadcast to
 [B,H,Nq,Nk], read in place) and ``q_norm`` / ``k_norm`` (``(weight, bias, eps)`` of a LayerNorm over the 64 elements of
 every q / k row, applied before the rotation).  With all three None the launch is the one it always was.
+
+``matrix16=True`` (keyword-only, on the two functions and on the two modules) moves a float16 / bfloat16 call to the
+16-bit matrix units (csrc/attention16.hip): q and k are rotated in float32 and rounded once, the probabilities are
+rounded once as operands, everything else stays float32.  It is opt-in: an unflagged 16-bit call runs the float32
+compute path as before.  Plain calls only -- with ``mask``, ``q_norm`` or ``k_norm`` it raises NotImplementedError, with
+float32 tokens ValueError; ``rope_attention_views`` does not take it.
 """
 from __future__ import annotations
 
@@ -122,6 +128,15 @@ def _check(q, k, v, qpos, kpos, mask=None, q_norm=None, k_norm=None) -> None:
         raise RuntimeError("rope_attention: the mask and the norm parameters must be on the tokens' device")
 
 
+def _check_matrix16(dtype, mask=None, q_norm=None, k_norm=None) -> None:
+    """What ``matrix16=True`` refuses, before anything else is looked at."""
+    if mask is not None or q_norm is not None or k_norm is not None:
+        raise NotImplementedError("rope_attention: matrix16=True is the plain call only; mask, q_norm and k_norm are not "
+                                  "supported on the 16-bit matrix path yet")
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"rope_attention: matrix16=True needs float16 or bfloat16 tokens, got {dtype}")
+
+
 def _rows(t: torch.Tensor) -> torch.Tensor:
     """``t`` itself when the kernels can read it in place (unit stride along D, 16-byte aligned rows), else a copy."""
     es = t.element_size()
@@ -178,8 +193,11 @@ def _norm_tensors(n):
     return None if n is None else (n[0].detach().contiguous(), n[1].detach().contiguous(), float(n[2]))
 
 
-def attention_forward(q, k, v, qpos, kpos, base, F0, scale, *, mask=None, q_norm=None, k_norm=None):
-    """The forward launch: (out [B,Nq,H*D], lse [B,H,Nq] float32).  q, k, v: [B,H,N,64] views, read in place."""
+def attention_forward(q, k, v, qpos, kpos, base, F0, scale, *, mask=None, q_norm=None, k_norm=None, matrix16=False):
+    """The forward launch: (out [B,Nq,H*D], lse [B,H,Nq] float32).  q, k, v: [B,H,N,64] views, read in place.
+    matrix16: the 16-bit matrix path (float16 / bfloat16, plain calls only)."""
+    if matrix16:
+        _check_matrix16(q.dtype, mask, q_norm, k_norm)
     _check(q, k, v, qpos, kpos, mask, q_norm, k_norm)
     q, k, v = _rows(q), _rows(k), _rows(v)
     B, H, Nq, D = q.shape
@@ -193,6 +211,10 @@ def attention_forward(q, k, v, qpos, kpos, base, F0, scale, *, mask=None, q_norm
     with torch.cuda.device(q.device):
         stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
         a = _args(q, k, v, qpos, kpos, base, F0, scale)
+        if matrix16:
+            _lib.check(lib.spf_attn16_forward(C.byref(a), C.c_void_p(out.data_ptr()), C.c_void_p(lse.data_ptr()), stream),
+                       "spf_attn16_forward")
+            return out, lse
         e = _ext(mask, q_norm, k_norm)                  # (empty: the library runs the plain kernels)
         _lib.check(lib.spf_attn_forward_ext(C.byref(a), C.byref(e), C.c_void_p(out.data_ptr()),
                                             C.c_void_p(lse.data_ptr()), stream), "spf_attn_forward_ext")
@@ -200,10 +222,13 @@ def attention_forward(q, k, v, qpos, kpos, base, F0, scale, *, mask=None, q_norm
 
 
 def attention_backward(q, k, v, qpos, kpos, base, F0, scale, out, lse, dout, dq, dk, dv, *, mask=None, q_norm=None,
-                       k_norm=None):
+                       k_norm=None, matrix16=False):
     """The backward launches: writes dq [B,H,Nq,64], dk, dv [B,H,Nk,64] (any views with 16-byte aligned rows, e.g. the
     three slices of one packed gradient) from what the forward saved.  With q_norm / k_norm it returns the gradients of
-    the four norm parameters as one [4,64] float32 tensor (q weight, q bias, k weight, k bias), else None."""
+    the four norm parameters as one [4,64] float32 tensor (q weight, q bias, k weight, k bias), else None.
+    matrix16: the 16-bit matrix path, on what a ``matrix16`` forward saved."""
+    if matrix16:
+        _check_matrix16(q.dtype, mask, q_norm, k_norm)
     _check(q, k, v, qpos, kpos, mask, q_norm, k_norm)
     q, k, v = _rows(q), _rows(k), _rows(v)
     out, dout = out.contiguous(), dout.contiguous()
@@ -228,6 +253,11 @@ def attention_backward(q, k, v, qpos, kpos, base, F0, scale, out, lse, dout, dq,
         g = _lib.SpfAttnGrads()
         g.dq, g.dk, g.dv, g.delta = dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr()
         g.dq_stride, g.dk_stride, g.dv_stride = _strides(dq), _strides(dk), _strides(dv)
+        if matrix16:
+            _lib.check(lib.spf_attn16_backward(C.byref(a), C.byref(g), C.c_void_p(out.data_ptr()),
+                                               C.c_void_p(lse.data_ptr()), C.c_void_p(dout.data_ptr()), stream),
+                       "spf_attn16_backward")
+            return None
         e = _ext(mask, q_norm, k_norm, dnorm, partials)
         _lib.check(lib.spf_attn_backward_ext(C.byref(a), C.byref(g), C.byref(e), C.c_void_p(out.data_ptr()),
                                              C.c_void_p(lse.data_ptr()), C.c_void_p(dout.data_ptr()), stream),
@@ -265,12 +295,14 @@ class _RopeAttention(torch.autograd.Function):
     """mask, qw .. kb: None on a plain call."""
 
     @staticmethod
-    def forward(ctx, q, k, v, qpos, kpos, mask, qw, qb, kw, kb, eps, base, F0, scale):
+    def forward(ctx, q, k, v, qpos, kpos, mask, qw, qb, kw, kb, eps, base, F0, scale, matrix16=False):
         q_norm, k_norm = _norm_pair(qw, qb, kw, kb, eps)
-        out, lse = attention_forward(q, k, v, qpos, kpos, base, F0, scale, mask=mask, q_norm=q_norm, k_norm=k_norm)
+        out, lse = attention_forward(q, k, v, qpos, kpos, base, F0, scale, mask=mask, q_norm=q_norm, k_norm=k_norm,
+                                     matrix16=matrix16)
         ctx.save_for_backward(q, k, v, qpos, kpos, mask, qw, qb, kw, kb, out, lse)
         ctx.cfg = (base, F0, scale)
         ctx.eps = eps
+        ctx.matrix16 = matrix16
         return out
 
     @staticmethod
@@ -280,22 +312,24 @@ class _RopeAttention(torch.autograd.Function):
         q_norm, k_norm = _norm_pair(qw, qb, kw, kb, ctx.eps)
         dq, dk, dv = _token_major(q, q.shape[2]), _token_major(q, k.shape[2]), _token_major(q, k.shape[2])
         dnorm = attention_backward(q, k, v, qpos, kpos, *ctx.cfg, out, lse, dout, dq, dk, dv, mask=mask, q_norm=q_norm,
-                                   k_norm=k_norm)
+                                   k_norm=k_norm, matrix16=ctx.matrix16)
         need = ctx.needs_input_grad
         return (dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None, None,
-                *_norm_grads(ctx, 6, dnorm), None, None, None, None)
+                *_norm_grads(ctx, 6, dnorm), None, None, None, None, None)
 
 
 class _RopeAttentionPacked(torch.autograd.Function):
     """mask, qw .. kb: None on a plain call."""
 
     @staticmethod
-    def forward(ctx, qkv, pos, mask, qw, qb, kw, kb, eps, base, F0, scale):
+    def forward(ctx, qkv, pos, mask, qw, qb, kw, kb, eps, base, F0, scale, matrix16=False):
         q_norm, k_norm = _norm_pair(qw, qb, kw, kb, eps)
-        out, lse = attention_forward(*_views(qkv), pos, pos, base, F0, scale, mask=mask, q_norm=q_norm, k_norm=k_norm)
+        out, lse = attention_forward(*_views(qkv), pos, pos, base, F0, scale, mask=mask, q_norm=q_norm, k_norm=k_norm,
+                                     matrix16=matrix16)
         ctx.save_for_backward(qkv, pos, mask, qw, qb, kw, kb, out, lse)
         ctx.cfg = (base, F0, scale)
         ctx.eps = eps
+        ctx.matrix16 = matrix16
         return out
 
     @staticmethod
@@ -305,8 +339,8 @@ class _RopeAttentionPacked(torch.autograd.Function):
         q_norm, k_norm = _norm_pair(qw, qb, kw, kb, ctx.eps)
         dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
         dnorm = attention_backward(*_views(qkv), pos, pos, *ctx.cfg, out, lse, dout, *_views(dqkv), mask=mask,
-                                   q_norm=q_norm, k_norm=k_norm)
-        return (dqkv, None, None, *_norm_grads(ctx, 3, dnorm), None, None, None, None)
+                                   q_norm=q_norm, k_norm=k_norm, matrix16=ctx.matrix16)
+        return (dqkv, None, None, *_norm_grads(ctx, 3, dnorm), None, None, None, None, None)
 
 
 def _views(qkv: torch.Tensor):
@@ -316,7 +350,7 @@ def _views(qkv: torch.Tensor):
 
 
 def rope_attention(q, k, v, qpos=None, kpos=None, *, base: float = 100.0, F0: float = 1.0, scale=None, mask=None,
-                   q_norm=None, k_norm=None):
+                   q_norm=None, k_norm=None, matrix16: bool = False):
     """softmax(scale * rope(norm(q), qpos) @ rope(norm(k), kpos)^T + mask) @ v, returned as [B,Nq,H*D].
 
     q [B,H,Nq,64], k and v [B,H,Nk,64]: any views with unit stride along D and 16-byte aligned rows are read in place
@@ -325,19 +359,26 @@ def rope_attention(q, k, v, qpos=None, kpos=None, *, base: float = 100.0, F0: fl
     dimensions broadcast to [B,H,Nq,Nk] and read in place (broadcast axes cost nothing); no gradient.  A row with
     every key excluded returns zeros and has zero gradients.  q_norm, k_norm: ``(weight, bias, eps)`` of a LayerNorm
     over the 64 elements of every row, float32 [64] each, both or neither; their gradients come out of the backward.
+    matrix16: run a float16 / bfloat16 call on the 16-bit matrix units (q, k and the probabilities rounded once to the
+    dtype as operands, float32 accumulation and softmax); refuses float32 tokens (ValueError) and mask / q_norm / k_norm
+    (NotImplementedError).  Off: 16-bit tokens run the float32 compute path.
     """
+    if matrix16:
+        _check_matrix16(q.dtype if isinstance(q, torch.Tensor) else None, mask, q_norm, k_norm)
     _check(q, k, v, qpos, kpos, mask, q_norm, k_norm)
     if scale is None:
         scale = q.shape[3] ** -0.5
     return _RopeAttention.apply(q, k, v, qpos, kpos, mask, *_norm_args(q_norm, k_norm), float(base), float(F0),
-                                float(scale))
+                                float(scale), bool(matrix16))
 
 
 def rope_attention_packed(qkv, pos=None, *, base: float = 100.0, F0: float = 1.0, scale=None, mask=None, q_norm=None,
-                          k_norm=None):
+                          k_norm=None, matrix16: bool = False):
     """Self-attention on a packed projection qkv [B,N,3,H,64] (what ``self.qkv(x).reshape(B, N, 3, H, D)`` yields):
     the same result as ``rope_attention`` on its three views, and ONE gradient of the packed shape out of the backward
-    instead of three that autograd would have to add up.  mask, q_norm, k_norm: as in ``rope_attention``."""
+    instead of three that autograd would have to add up.  mask, q_norm, k_norm, matrix16: as in ``rope_attention``."""
+    if matrix16:
+        _check_matrix16(qkv.dtype if isinstance(qkv, torch.Tensor) else None, mask, q_norm, k_norm)
     if qkv.dim() != 5 or qkv.shape[2] != 3:
         raise RuntimeError(f"rope_attention_packed: qkv must be [B,N,3,H,D], got {tuple(qkv.shape)}")
     _check(*_views(qkv), pos, pos, mask, q_norm, k_norm)
@@ -345,7 +386,8 @@ def rope_attention_packed(qkv, pos=None, *, base: float = 100.0, F0: float = 1.0
         qkv = qkv.contiguous()
     if scale is None:
         scale = qkv.shape[4] ** -0.5
-    return _RopeAttentionPacked.apply(qkv, pos, mask, *_norm_args(q_norm, k_norm), float(base), float(F0), float(scale))
+    return _RopeAttentionPacked.apply(qkv, pos, mask, *_norm_args(q_norm, k_norm), float(base), float(F0), float(scale),
+                                      bool(matrix16))
 
 
 # ---- multi-view: one key set per scene, whole views left out per query view ------------------------------------------
@@ -599,11 +641,19 @@ def _check_module(mod, mask=None) -> None:
         raise NotImplementedError("attn_drop > 0 in training mode is not supported by the fused kernel")
 
 
-class Attention(nn.Module):
-    """blocks.py:81-113 with the fused core; same parameters, same state dict."""
+def _use_matrix16(mod, t: torch.Tensor) -> bool:
+    """A flagged module takes the 16-bit matrix path for 16-bit projections and the float32 path, bit for bit, for
+    float32 ones: one flag serves a model inside and outside autocast."""
+    return bool(getattr(mod, "matrix16", False)) and t.dtype in (torch.float16, torch.bfloat16)
 
-    def __init__(self, dim, rope=None, num_heads=8, qkv_bias=False, attn_drop=0., proj_drop=0.):
+
+class Attention(nn.Module):
+    """blocks.py:81-113 with the fused core; same parameters, same state dict.  matrix16 (keyword-only, also an
+    attribute): 16-bit projections (autocast, a half model) run on the 16-bit matrix units; float32 ones are unaffected."""
+
+    def __init__(self, dim, rope=None, num_heads=8, qkv_bias=False, attn_drop=0., proj_drop=0., *, matrix16=False):
         super().__init__()
+        self.matrix16 = bool(matrix16)
         self.num_heads = num_heads
         head_dim = dim // num_heads
         self.scale = head_dim ** -0.5
@@ -622,17 +672,20 @@ class Attention(nn.Module):
         if not x.is_cuda:
             raise RuntimeError("Attention: x is on the CPU; this build only runs on a HIP device (no CPU fallback)")
         qkv = self.qkv(x).reshape(B, N, 3, self.num_heads, C // self.num_heads)
-        x = rope_attention_packed(qkv, xpos if cfg else None, scale=self.scale, **cfg)
+        x = rope_attention_packed(qkv, xpos if cfg else None, scale=self.scale, matrix16=_use_matrix16(self, qkv),
+                                  **cfg)
         x = self.proj(x)
         x = self.proj_drop(x)
         return x
 
 
 class CrossAttention(nn.Module):
-    """blocks.py:133-179 with the fused core; same parameters, same state dict."""
+    """blocks.py:133-179 with the fused core; same parameters, same state dict.  matrix16 (keyword-only, also an
+    attribute): as in ``Attention``; ``forward_views`` ignores it (the multi-view kernels have no 16-bit matrix form yet)."""
 
-    def __init__(self, dim, rope=None, num_heads=8, qkv_bias=False, attn_drop=0., proj_drop=0.):
+    def __init__(self, dim, rope=None, num_heads=8, qkv_bias=False, attn_drop=0., proj_drop=0., *, matrix16=False):
         super().__init__()
+        self.matrix16 = bool(matrix16)
         self.num_heads = num_heads
         head_dim = dim // num_heads
         self.scale = head_dim ** -0.5
@@ -659,7 +712,8 @@ class CrossAttention(nn.Module):
         q = self.projq(query).reshape(B, Nq, H, D).permute(0, 2, 1, 3)
         k = self.projk(key).reshape(B, Nk, H, D).permute(0, 2, 1, 3)
         v = self.projv(value).reshape(B, Nv, H, D).permute(0, 2, 1, 3)
-        x = rope_attention(q, k, v, qpos if cfg else None, kpos if cfg else None, scale=self.scale, **cfg)
+        x = rope_attention(q, k, v, qpos if cfg else None, kpos if cfg else None, scale=self.scale,
+                           matrix16=_use_matrix16(self, q), **cfg)
         x = self.proj(x)
         x = self.proj_drop(x)
         return x
@@ -668,7 +722,7 @@ class CrossAttention(nn.Module):
         """The layer on a scene's views without gathered keys: query [b,Vq,Nq,C], key [b,Vk,Nk,C] (key and value, as at
         every call site of the reference), qpos [b,Vq,Nq,2], kpos [b,Vk,Nk,2], allow [Vq,Vk] (``rope_attention_views``).
         ``projk`` and ``projv`` run ONCE over the b*Vk*Nk key tokens; returns [b,Vq,Nq,C].  Same parameters as
-        ``forward``."""
+        ``forward``.  The module's ``matrix16`` flag is ignored here: this call always runs the float32 compute path."""
         _check_module(self)
         if query.dim() != 4 or key.dim() != 4:
             raise RuntimeError("CrossAttention.forward_views: query and key must be [b, V, N, C]")

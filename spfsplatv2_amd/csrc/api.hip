@@ -74,6 +74,8 @@ hipError_t launch_attn_forward(const SpfAttn&, const SpfAttnExt*, void*, float*,
 hipError_t launch_attn_backward(const SpfAttn&, const SpfAttnGrads&, const SpfAttnExt*, const void*, const float*,
                                 const void*, hipStream_t);
 int64_t attn_ext_scratch_floats(int, int, int, int);
+hipError_t launch_attn16_forward(const SpfAttn&, void*, float*, hipStream_t);
+hipError_t launch_attn16_backward(const SpfAttn&, const SpfAttnGrads&, const void*, const float*, const void*, hipStream_t);
 hipError_t launch_attn_views_forward(const SpfAttn&, const SpfAttnViews&, void*, float*, hipStream_t);
 hipError_t launch_attn_views_backward(const SpfAttn&, const SpfAttnViews&, const SpfAttnGrads&, const void*, const float*,
                                       const void*, hipStream_t);
@@ -1109,6 +1111,26 @@ int spf_attn_backward(const SpfAttn* args, const SpfAttnGrads* g, const void* ou
                       void* stream_) {
     if (const char* e = attn_backward_error(args, g, nullptr, out, lse, dout)) return fail(SPF_E_INVALID, "%s", e);
     SPF_HIP(spf::launch_attn_backward(*args, *g, nullptr, out, lse, dout, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+// the 16-bit matrix path (attention16.hip): the checks of the plain call, and the element type must be a 16-bit one
+static const char* attn16_dtype_error(const SpfAttn* a) {
+    return a->dtype == 1 || a->dtype == 2 ? nullptr : "attention16: dtype must be 1 (f16) or 2 (bf16)";
+}
+
+int spf_attn16_forward(const SpfAttn* args, void* out, float* lse, void* stream_) {
+    if (const char* e = attn_forward_error(args, out, lse)) return fail(SPF_E_INVALID, "%s", e);
+    if (const char* e = attn16_dtype_error(args)) return fail(SPF_E_INVALID, "%s", e);
+    SPF_HIP(spf::launch_attn16_forward(*args, out, lse, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_attn16_backward(const SpfAttn* args, const SpfAttnGrads* g, const void* out, const float* lse, const void* dout,
+                        void* stream_) {
+    if (const char* e = attn_backward_error(args, g, nullptr, out, lse, dout)) return fail(SPF_E_INVALID, "%s", e);
+    if (const char* e = attn16_dtype_error(args)) return fail(SPF_E_INVALID, "%s", e);
+    SPF_HIP(spf::launch_attn16_backward(*args, *g, out, lse, dout, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
 

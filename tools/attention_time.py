@@ -1,13 +1,17 @@
 """Time forward + backward of the fused RoPE attention core against the eager expression, on one GPU.
 
     python tools/attention_time.py [--warmup 20] [--iters 100] [--shapes all|name,name] [--out profiles/attention_time.json]
+    python tools/attention_time.py --matrix16 [--shapes ...]      (16-bit shapes, writes profiles/attention16_time.json)
 
 Variants, alternated shape by shape in one run:
   eager  the reference's lines (croco/blocks.py:97-110 / 155-176) with the rotation done by this library's own
          rope_2d_pair / cuRoPE2D -- the fastest unfused path a user has today: rope, q @ k^T * scale, softmax, @ v,
          .transpose(1, 2).reshape(B, N, C), and autograd's backward of it
   fused  rope_attention_packed (self) / rope_attention (cross), and their backward
-Both start from the projection's output (a packed [B,N,3,H,D] buffer, or three [B,N,H*D] buffers: non-leaf tensors made
+  matrix16      (--matrix16 only) the same calls with matrix16=True: the 16-bit matrix path
+  fused_repeat  (--matrix16 only) `fused` a second time in the same rotation: the spread of two runs of one variant, which
+                a difference between `fused` and `matrix16` has to exceed to mean anything
+All start from the projection's output (a packed [B,N,3,H,D] buffer, or three [B,N,H*D] buffers: non-leaf tensors made
 outside the timed region, so the eager path rotates q and k in place with no copy, as the reference does) and a given
 upstream gradient, and end with the gradient of those buffers.
 
@@ -37,6 +41,16 @@ SHAPES = {
     "cross_32x12x258_258_f32": ("cross", 32, 12, 258, 258, "float32"),
     "cross_32x12x258_2322_f32": ("cross", 32, 12, 258, 2322, "float32"),       # the 10-view shape
 }
+# --matrix16: eager in the 16-bit type, the float32 compute path on the same operands (twice) and the 16-bit matrix path
+SHAPES16 = {
+    "self_32x12x258_f16": ("self", 32, 12, 258, 258, "float16"),
+    "self_32x12x258_bf16": ("self", 32, 12, 258, 258, "bfloat16"),
+    "self_48x16x256_bf16": ("self", 48, 16, 256, 256, "bfloat16"),
+    "cross_32x12x258_258_bf16": ("cross", 32, 12, 258, 258, "bfloat16"),
+    "cross_32x12x258_2322_bf16": ("cross", 32, 12, 258, 2322, "bfloat16"),
+}
+VARIANTS = ("eager", "fused")
+VARIANTS16 = ("eager", "fused", "matrix16", "fused_repeat")
 CACHE_BYTES = 256 << 20
 
 
@@ -77,8 +91,8 @@ def step(variant, kind, H, s, leaves, bufs):
     import spfsplatv2_amd as spf
     if kind == "self":
         (qkv,) = bufs
-        if variant == "fused":
-            out = spf.rope_attention_packed(qkv, s["qpos"])
+        if variant != "eager":
+            out = spf.rope_attention_packed(qkv, s["qpos"], matrix16=variant == "matrix16")
         else:
             B, N = qkv.shape[:2]
             t = _rope_packed_(qkv, s["qpos"]).transpose(1, 3)
@@ -88,8 +102,8 @@ def step(variant, kind, H, s, leaves, bufs):
     else:
         B, Nq = bufs[0].shape[:2]
         q, k, v = (x.reshape(B, x.shape[1], H, 64).permute(0, 2, 1, 3) for x in bufs)
-        if variant == "fused":
-            out = spf.rope_attention(q, k, v, s["qpos"], s["kpos"])
+        if variant != "eager":
+            out = spf.rope_attention(q, k, v, s["qpos"], s["kpos"], matrix16=variant == "matrix16")
         else:
             rope = spf.cuRoPE2D(100.0, 1.0)                      # in place on the non-leaf views, as blocks.py:161-163
             q, k = rope(q, s["qpos"]), rope(k, s["kpos"])
@@ -149,9 +163,9 @@ def errors(kind, H, s, results, rows=2):
     return res
 
 
-def run(name, warmup, iters):
+def run(name, warmup, iters, shapes=SHAPES, variants=VARIANTS):
     import torch
-    kind, B, H, Nq, Nk, dt = SHAPES[name]
+    kind, B, H, Nq, Nk, dt = shapes[name]
     dtype = getattr(torch, dt)
     dev = torch.device("cuda")
     gen = torch.Generator().manual_seed(0)
@@ -162,14 +176,14 @@ def run(name, warmup, iters):
     res = {"shape": name, "kind": kind, "B": B, "H": H, "Nq": Nq, "Nk": Nk, "dtype": dt, "input_sets": nsets,
            "input_set_bytes": set_bytes, "variants": {}}
     results = {}
-    times = {"eager": [], "fused": []}
-    for var in ("eager", "fused"):
+    times = {var: [] for var in variants}
+    for var in variants:
         for i in range(warmup):
             step(var, kind, H, sets[i % nsets], *prepare(kind, sets[i % nsets]))
     torch.cuda.synchronize()
-    for i in range(iters):                              # the two variants alternate, on rotating buffers
-        for var in ("eager", "fused"):
-            s = sets[(2 * i + (var == "fused")) % nsets]
+    for i in range(iters):                              # the variants alternate, on rotating buffers
+        for vi, var in enumerate(variants):
+            s = sets[(len(variants) * i + vi) % nsets]
             prepared = prepare(kind, s)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -178,7 +192,7 @@ def run(name, warmup, iters):
             e1.record()
             e1.synchronize()
             times[var].append(e0.elapsed_time(e1))
-    for var in ("eager", "fused"):
+    for var in variants:
         prepared = prepare(kind, sets[0])
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
@@ -190,7 +204,13 @@ def run(name, warmup, iters):
                                 "bytes_allocated_peak": torch.cuda.max_memory_allocated() - before,
                                 "iters": iters, "warmup": warmup}
     res["err_vs_float64"] = errors(kind, H, sets[0], results)
-    res["speedup_fused_over_eager"] = res["variants"]["eager"]["ms_median"] / res["variants"]["fused"]["ms_median"]
+    ms = {var: res["variants"][var]["ms_median"] for var in variants}
+    res["speedup_fused_over_eager"] = ms["eager"] / ms["fused"]
+    if "matrix16" in ms:
+        res["fused_spread_ms"] = abs(ms["fused"] - ms["fused_repeat"])
+        res["matrix16_gain_over_fused_ms"] = min(ms["fused"], ms["fused_repeat"]) - ms["matrix16"]
+        res["speedup_matrix16_over_fused"] = min(ms["fused"], ms["fused_repeat"]) / ms["matrix16"]
+        res["speedup_matrix16_over_eager"] = ms["eager"] / ms["matrix16"]
     return res
 
 
@@ -199,17 +219,21 @@ def main():
     ap.add_argument("--shapes", default="all")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--iters", type=int, default=100)
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "attention_time.json"))
+    ap.add_argument("--matrix16", action="store_true", help="the 16-bit shapes with the matrix16 variant")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    shapes, variants = (SHAPES16, VARIANTS16) if args.matrix16 else (SHAPES, VARIANTS)
+    if args.out is None:
+        args.out = str(ROOT / "profiles" / ("attention16_time.json" if args.matrix16 else "attention_time.json"))
     if args.iters < 100 or args.warmup < 20:
         raise SystemExit("attention_time.py: the median is taken over at least 100 steps after at least 20 warm-ups")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("attention_time.py needs a GPU")
-    names = list(SHAPES) if args.shapes == "all" else args.shapes.split(",")
+    names = list(shapes) if args.shapes == "all" else args.shapes.split(",")
     res = {"tool": "attention_time", "device": torch.cuda.get_device_name(0), "results": []}
     for n in names:
-        res["results"].append(run(n, args.warmup, args.iters))
+        res["results"].append(run(n, args.warmup, args.iters, shapes, variants))
         print(json.dumps(res["results"][-1]), file=sys.stderr, flush=True)
     line = json.dumps(res)
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
