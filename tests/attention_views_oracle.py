@@ -23,7 +23,7 @@ def gather_views(x, idx, dim=1):
     return sel.flatten(dim, dim + 1)
 
 
-def core_views(q, k, v, qpos, kpos, allow, base=100.0, scale=None):
+def core_views(q, k, v, qpos, kpos, allow, base=100.0, scale=None, F0=1.0):
     """q [b,Vq,H,Nq,D], k, v [b,Vk,H,Nk,D], qpos [b,Vq,Nq,2], kpos [b,Vk,Nk,2] -> [b,Vq,Nq,H*D]."""
     outs = []
     for i in range(q.shape[1]):
@@ -32,28 +32,30 @@ def core_views(q, k, v, qpos, kpos, allow, base=100.0, scale=None):
         kg = k.index_select(1, idx.to(k.device)).transpose(1, 2).flatten(2, 3)
         vg = v.index_select(1, idx.to(v.device)).transpose(1, 2).flatten(2, 3)
         kp = gather_views(kpos, idx) if kpos is not None else None
-        outs.append(oracle.attention_core(q[:, i], kg, vg, qpos[:, i] if qpos is not None else None, kp, base, scale))
+        outs.append(oracle.attention_core(q[:, i], kg, vg, qpos[:, i] if qpos is not None else None, kp, base, scale,
+                                          F0))
     return torch.stack(outs, dim=1)
 
 
-def core_views_with_grads(q, k, v, qpos, kpos, allow, dout, base=100.0, scale=None, dtype=torch.float64):
+def core_views_with_grads(q, k, v, qpos, kpos, allow, dout, base=100.0, scale=None, dtype=torch.float64, F0=1.0):
     """(out, dq, dk, dv) of core_views in ``dtype`` on the inputs' device; dk, dv: the sums over the gathered copies."""
     q, k, v = (t.detach().to(dtype).requires_grad_(True) for t in (q, k, v))
-    out = core_views(q, k, v, qpos, kpos, allow, base, scale)
+    out = core_views(q, k, v, qpos, kpos, allow, base, scale, F0)
     dq, dk, dv = torch.autograd.grad(out, (q, k, v), dout.to(dtype), allow_unused=True)
     dk = torch.zeros_like(k) if dk is None else dk
     dv = torch.zeros_like(v) if dv is None else dv
     return out.detach(), dq, dk, dv
 
 
-def module_views(query, key, qpos, kpos, allow, w: dict, num_heads: int, base=100.0):
+def module_views(query, key, qpos, kpos, allow, w: dict, num_heads: int, base=100.0, F0=1.0):
     """``CrossAttention.forward`` per query view on the gathered key views (key = value): query [b,Vq,Nq,C],
     key [b,Vk,Nk,C] -> [b,Vq,Nq,C]."""
     outs = []
     for i in range(query.shape[1]):
         idx = allowed(allow, i)
         mem = gather_views(key, idx)
-        outs.append(oracle.cross_attention(query[:, i], mem, mem, qpos[:, i], gather_views(kpos, idx), w, num_heads, base))
+        outs.append(oracle.cross_attention(query[:, i], mem, mem, qpos[:, i], gather_views(kpos, idx), w, num_heads, base,
+                                            F0))
     return torch.stack(outs, dim=1)
 
 

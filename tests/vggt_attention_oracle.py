@@ -1,6 +1,6 @@
 """Oracle of the VGGT attention (TEST INFRASTRUCTURE ONLY): a restatement of the reference's
 ``vggt/layers/attention.py:Attention.forward`` (lines 50-84) -- ``F.layer_norm`` of q and k (qk_norm), the 2-D rotation
-(oracle/rope_torch_ref.py: VGGT's RotaryPositionEmbedding2D is the same formula as CroCo's fallback), ``scale * q k^T +
+(tests/attention_oracle.py:rope2d: VGGT's RotaryPositionEmbedding2D is the same formula as CroCo's fallback), ``scale * q k^T +
 mask``, softmax, ``@ v`` -- dtype- and device-generic; the tests run it in float64 on the CPU and in float32 on the
 device.  One definition the reference leaves to SDPA: a query row whose keys are ALL excluded (-inf) is zeros, and
 autograd then gives it zero gradients.  Gradients come from autograd.
@@ -13,7 +13,7 @@ from __future__ import annotations
 import torch
 import torch.nn.functional as F
 
-from oracle.rope_torch_ref import rope2d_fallback
+from tests.attention_oracle import rope2d
 
 
 def view_positions(B: int, S: int, hh: int, ww: int, special: int) -> torch.Tensor:
@@ -43,7 +43,7 @@ def _additive(mask, dtype):
 
 
 def attention_core(q, k, v, qpos=None, kpos=None, mask=None, q_norm=None, k_norm=None, base: float = 100.0,
-                   scale: float | None = None, probe: dict | None = None):
+                   scale: float | None = None, probe: dict | None = None, F0: float = 1.0):
     """q [B,H,Nq,D], k, v [B,H,Nk,D] -> [B,Nq,H*D].  q_norm / k_norm: (weight, bias, eps) or None; mask: additive or
     bool, broadcast to [B,H,Nq,Nk].  probe: a dict that receives the normalised k (``k_hat``, gradient retained) for
     ``k_bias_cancel_scale``."""
@@ -57,8 +57,8 @@ def attention_core(q, k, v, qpos=None, kpos=None, mask=None, q_norm=None, k_norm
             k.retain_grad()
             probe["k_hat"] = k
     if qpos is not None:
-        q = rope2d_fallback(q, qpos, base)
-        k = rope2d_fallback(k, kpos, base)
+        q = rope2d(q, qpos, base, F0)
+        k = rope2d(k, kpos, base, F0)
     attn = (q @ k.transpose(-2, -1)) * scale
     m = _additive(mask, attn.dtype)
     if m is not None:
@@ -81,7 +81,7 @@ def k_bias_cancel_scale(probe: dict) -> float:
 
 
 def core_with_grads(q, k, v, qpos, kpos, dout, mask=None, q_norm=None, k_norm=None, base: float = 100.0,
-                    scale: float | None = None, dtype=torch.float64, probe: dict | None = None):
+                    scale: float | None = None, dtype=torch.float64, probe: dict | None = None, F0: float = 1.0):
     """(out, dq, dk, dv, dq_weight, dq_bias, dk_weight, dk_bias) of attention_core evaluated in ``dtype`` on the inputs'
     device; the four parameter gradients are None without the norms."""
     q, k, v = (t.detach().to(dtype).requires_grad_(True) for t in (q, k, v))
@@ -92,7 +92,7 @@ def core_with_grads(q, k, v, qpos, kpos, dout, mask=None, q_norm=None, k_norm=No
         leaves += params
     if mask is not None and mask.dtype != torch.bool:
         mask = mask.to(dtype)
-    out = attention_core(q, k, v, qpos, kpos, mask, norms[0], norms[1], base, scale, probe)
+    out = attention_core(q, k, v, qpos, kpos, mask, norms[0], norms[1], base, scale, probe, F0)
     out.backward(dout.to(dtype))
     grads = [t.grad for t in leaves]
     return (out.detach(),) + tuple(grads) + (None,) * (7 - len(grads))
