@@ -44,13 +44,33 @@ from .rope import _DTYPES
 HEAD_DIM = 64
 
 
-def _check_tokens(t: torch.Tensor) -> None:
-    if t.dim() != 4:
-        raise RuntimeError("tokens must have 4 dimensions")
-    if t.shape[3] != HEAD_DIM:
-        raise ValueError(f"rope_attention: head dim must be {HEAD_DIM}, got {t.shape[3]}")
-    if t.dtype not in _DTYPES:
-        raise RuntimeError(f"rope_attention: unsupported dtype {t.dtype}")
+def _check_tokens(q, k, v, rank: int, rank_error: str) -> None:
+    """What [B,H,N,D] and [b,V,H,N,D] calls ask of q, k and v alike: each one's rank, head dim and dtype, then one dtype
+    and one device."""
+    for t in (q, k, v):
+        if t.dim() != rank:
+            raise RuntimeError(rank_error)
+        if t.shape[-1] != HEAD_DIM:
+            raise ValueError(f"rope_attention: head dim must be {HEAD_DIM}, got {t.shape[-1]}")
+        if t.dtype not in _DTYPES:
+            raise RuntimeError(f"rope_attention: unsupported dtype {t.dtype}")
+    if not (q.dtype == k.dtype == v.dtype):
+        raise RuntimeError(f"rope_attention: q, k and v differ in dtype ({q.dtype}, {k.dtype}, {v.dtype})")
+    if not (q.device == k.device == v.device):
+        raise RuntimeError("rope_attention: q, k and v are not on the same device")
+
+
+def _have_positions(qpos, kpos) -> bool:
+    if (qpos is None) != (kpos is None):
+        raise RuntimeError("rope_attention: qpos and kpos must both be given or both be None")
+    return qpos is not None
+
+
+def _check_on_device(q) -> None:
+    """The last check of every call."""
+    if not q.is_cuda:
+        raise RuntimeError("rope_attention: q, k and v are on the CPU; this build only runs on a HIP device "
+                           "(no CPU fallback)")
 
 
 def _check_positions(tokens: torch.Tensor, positions: torch.Tensor) -> None:
@@ -104,25 +124,16 @@ def _check_norms(q_norm, k_norm) -> None:
 
 
 def _check(q, k, v, qpos, kpos, mask=None, q_norm=None, k_norm=None) -> None:
-    for t in (q, k, v):
-        _check_tokens(t)
-    if not (q.dtype == k.dtype == v.dtype):
-        raise RuntimeError(f"rope_attention: q, k and v differ in dtype ({q.dtype}, {k.dtype}, {v.dtype})")
-    if not (q.device == k.device == v.device):
-        raise RuntimeError("rope_attention: q, k and v are not on the same device")
+    _check_tokens(q, k, v, 4, "tokens must have 4 dimensions")
     if k.shape != v.shape or q.shape[:2] != k.shape[:2]:
         raise RuntimeError(f"rope_attention: shapes differ: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}")
-    if (qpos is None) != (kpos is None):
-        raise RuntimeError("rope_attention: qpos and kpos must both be given or both be None")
-    if qpos is not None:
+    if _have_positions(qpos, kpos):
         _check_positions(q, qpos)
         _check_positions(k, kpos)
     if mask is not None:
         _check_mask(mask, (q.shape[0], q.shape[1], q.shape[2], k.shape[2]))
     _check_norms(q_norm, k_norm)
-    if not q.is_cuda:
-        raise RuntimeError("rope_attention: q, k and v are on the CPU; this build only runs on a HIP device "
-                           "(no CPU fallback)")
+    _check_on_device(q)
     extras = ([mask] if mask is not None else []) + (list(q_norm[:2]) + list(k_norm[:2]) if q_norm is not None else [])
     if any(t.device != q.device for t in extras):
         raise RuntimeError("rope_attention: the mask and the norm parameters must be on the tokens' device")
@@ -138,28 +149,58 @@ def _check_matrix16(dtype, mask=None, q_norm=None, k_norm=None) -> None:
 
 
 def _rows(t: torch.Tensor) -> torch.Tensor:
-    """``t`` itself when the kernels can read it in place (unit stride along D, 16-byte aligned rows), else a copy."""
+    """``t`` ([.., H, N, D], any rank) itself when the kernels can read it in place (unit stride along D, every other
+    stride and the base 16-byte aligned), else a copy."""
     es = t.element_size()
-    if t.stride(3) == 1 and t.data_ptr() % 16 == 0 and all((t.stride(i) * es) % 16 == 0 for i in range(3)):
+    if t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and all((s * es) % 16 == 0 for s in t.stride()[:-1]):
         return t
     return t.contiguous()
 
 
+_rows5 = _rows          # the name the views tests know it by
+
+
 def _strides(t: torch.Tensor):
-    """(batch, token, head) element strides of a [B,H,N,D] tensor."""
-    return (C.c_int64 * 3)(t.stride(0), t.stride(2), t.stride(1))
+    """(batch or scene, token, head) element strides of a [B,H,N,D] or [b,V,H,N,D] tensor."""
+    return (C.c_int64 * 3)(t.stride(0), t.stride(-2), t.stride(-3))
 
 
 def _args(q, k, v, qpos, kpos, base, F0, scale) -> _lib.SpfAttn:
-    B, H, Nq, D = q.shape
+    """SpfAttn of a call on [B,H,N,D] or [b,V,H,N,D] tokens (B: the scenes then; the views travel in SpfAttnViews)."""
     a = _lib.SpfAttn()
     a.q, a.k, a.v = q.data_ptr(), k.data_ptr(), v.data_ptr()
     a.qpos = qpos.data_ptr() if qpos is not None else None
     a.kpos = kpos.data_ptr() if kpos is not None else None
     a.q_stride, a.k_stride, a.v_stride = _strides(q), _strides(k), _strides(v)
-    a.B, a.H, a.Nq, a.Nk, a.D, a.dtype = B, H, Nq, k.shape[2], D, _DTYPES[q.dtype]
+    a.B, a.H, a.Nq, a.Nk, a.D = q.shape[0], q.shape[-3], q.shape[-2], k.shape[-2], q.shape[-1]
+    a.dtype = _DTYPES[q.dtype]
     a.base, a.F0, a.scale = float(base), float(F0), float(scale)
     return a
+
+
+def _grads(dq, dk, dv, delta) -> _lib.SpfAttnGrads:
+    g = _lib.SpfAttnGrads()
+    g.dq, g.dk, g.dv, g.delta = dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr()
+    g.dq_stride, g.dk_stride, g.dv_stride = _strides(dq), _strides(dk), _strides(dv)
+    return g
+
+
+def _saved(out, dout, dtype):
+    """What the forward saved and the incoming gradient, contiguous, for a backward launch."""
+    out, dout = out.contiguous(), dout.contiguous()
+    if dout.dtype != dtype or out.dtype != dtype:
+        raise RuntimeError(f"rope_attention: gradient dtype {dout.dtype} differs from the inputs' {dtype}")
+    return out, dout
+
+
+def _launch(name: str, device, *args) -> None:
+    """Entry point ``name`` of the library on ``device``'s current stream; a tensor goes as its pointer, a structure by
+    reference, in the order given."""
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        cargs = [C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else C.byref(a) for a in args]
+        _lib.check(getattr(lib, name)(*cargs, stream), name)
 
 
 def _mask_view(mask, shape):
@@ -203,21 +244,13 @@ def attention_forward(q, k, v, qpos, kpos, base, F0, scale, *, mask=None, q_norm
     B, H, Nq, D = q.shape
     out = torch.empty(B, Nq, H * D, dtype=q.dtype, device=q.device)
     lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
-    if mask is not None:
-        mask = _mask_view(mask, (B, H, Nq, k.shape[2]))
-    if q_norm is not None:
-        q_norm, k_norm = _norm_tensors(q_norm), _norm_tensors(k_norm)
-    lib = _lib.load()
-    with torch.cuda.device(q.device):
-        stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-        a = _args(q, k, v, qpos, kpos, base, F0, scale)
-        if matrix16:
-            _lib.check(lib.spf_attn16_forward(C.byref(a), C.c_void_p(out.data_ptr()), C.c_void_p(lse.data_ptr()), stream),
-                       "spf_attn16_forward")
-            return out, lse
-        e = _ext(mask, q_norm, k_norm)                  # (empty: the library runs the plain kernels)
-        _lib.check(lib.spf_attn_forward_ext(C.byref(a), C.byref(e), C.c_void_p(out.data_ptr()),
-                                            C.c_void_p(lse.data_ptr()), stream), "spf_attn_forward_ext")
+    mask = _mask_view(mask, (B, H, Nq, k.shape[2]))
+    q_norm, k_norm = _norm_tensors(q_norm), _norm_tensors(k_norm)
+    a = _args(q, k, v, qpos, kpos, base, F0, scale)
+    if matrix16:
+        _launch("spf_attn16_forward", q.device, a, out, lse)
+    else:                                               # (an empty SpfAttnExt: the library runs the plain kernels)
+        _launch("spf_attn_forward_ext", q.device, a, _ext(mask, q_norm, k_norm), out, lse)
     return out, lse
 
 
@@ -231,37 +264,23 @@ def attention_backward(q, k, v, qpos, kpos, base, F0, scale, out, lse, dout, dq,
         _check_matrix16(q.dtype, mask, q_norm, k_norm)
     _check(q, k, v, qpos, kpos, mask, q_norm, k_norm)
     q, k, v = _rows(q), _rows(k), _rows(v)
-    out, dout = out.contiguous(), dout.contiguous()
-    if dout.dtype != q.dtype or out.dtype != q.dtype:
-        raise RuntimeError(f"rope_attention: gradient dtype {dout.dtype} differs from the inputs' {q.dtype}")
+    out, dout = _saved(out, dout, q.dtype)
     B, H, Nq, D = q.shape
     delta = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
-    if mask is not None:
-        mask = _mask_view(mask, (B, H, Nq, k.shape[2]))
-    lib = _lib.load()
+    mask = _mask_view(mask, (B, H, Nq, k.shape[2]))
     dnorm = partials = None
     if q_norm is not None:
         q_norm, k_norm = _norm_tensors(q_norm), _norm_tensors(k_norm)
-        n = lib.spf_attn_ext_scratch_floats(B, H, Nq, k.shape[2])           # (the library's grid arithmetic, not ours)
+        n = _lib.load().spf_attn_ext_scratch_floats(B, H, Nq, k.shape[2])   # (the library's grid arithmetic, not ours)
         if n < 0:
             raise _lib.SpfError("spf_attn_ext_scratch_floats rejected the sizes")
         dnorm = torch.empty(4, HEAD_DIM, dtype=torch.float32, device=q.device)
         partials = torch.empty(n, dtype=torch.float32, device=q.device)
-    with torch.cuda.device(q.device):
-        stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-        a = _args(q, k, v, qpos, kpos, base, F0, scale)
-        g = _lib.SpfAttnGrads()
-        g.dq, g.dk, g.dv, g.delta = dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr()
-        g.dq_stride, g.dk_stride, g.dv_stride = _strides(dq), _strides(dk), _strides(dv)
-        if matrix16:
-            _lib.check(lib.spf_attn16_backward(C.byref(a), C.byref(g), C.c_void_p(out.data_ptr()),
-                                               C.c_void_p(lse.data_ptr()), C.c_void_p(dout.data_ptr()), stream),
-                       "spf_attn16_backward")
-            return None
-        e = _ext(mask, q_norm, k_norm, dnorm, partials)
-        _lib.check(lib.spf_attn_backward_ext(C.byref(a), C.byref(g), C.byref(e), C.c_void_p(out.data_ptr()),
-                                             C.c_void_p(lse.data_ptr()), C.c_void_p(dout.data_ptr()), stream),
-                   "spf_attn_backward_ext")
+    a, g = _args(q, k, v, qpos, kpos, base, F0, scale), _grads(dq, dk, dv, delta)
+    if matrix16:
+        _launch("spf_attn16_backward", q.device, a, g, out, lse, dout)
+    else:
+        _launch("spf_attn_backward_ext", q.device, a, g, _ext(mask, q_norm, k_norm, dnorm, partials), out, lse, dout)
     return dnorm
 
 
@@ -284,11 +303,11 @@ def _norm_grads(ctx, first, dnorm):
     return tuple(dnorm[i] if ctx.needs_input_grad[first + i] else None for i in range(4))
 
 
-def _token_major(like, N):
-    """An empty [B,H,N,D] gradient for ``like`` [B,H,*,D] on a token-major buffer: such a view is what a following
-    reshape(B, N, C) wants."""
-    B, H, _, D = like.shape
-    return torch.empty(B, N, H, D, dtype=like.dtype, device=like.device).transpose(1, 2)
+def _token_major(t):
+    """An empty gradient for ``t`` [.., H, N, D] on a token-major buffer [.., N, H, D]: such a view is what a following
+    reshape(.., N, C) wants."""
+    *lead, H, N, D = t.shape
+    return torch.empty(*lead, N, H, D, dtype=t.dtype, device=t.device).transpose(-3, -2)
 
 
 class _RopeAttention(torch.autograd.Function):
@@ -310,7 +329,7 @@ class _RopeAttention(torch.autograd.Function):
     def backward(ctx, dout):
         q, k, v, qpos, kpos, mask, qw, qb, kw, kb, out, lse = ctx.saved_tensors
         q_norm, k_norm = _norm_pair(qw, qb, kw, kb, ctx.eps)
-        dq, dk, dv = _token_major(q, q.shape[2]), _token_major(q, k.shape[2]), _token_major(q, k.shape[2])
+        dq, dk, dv = _token_major(q), _token_major(k), _token_major(v)
         dnorm = attention_backward(q, k, v, qpos, kpos, *ctx.cfg, out, lse, dout, dq, dk, dv, mask=mask, q_norm=q_norm,
                                    k_norm=k_norm, matrix16=ctx.matrix16)
         need = ctx.needs_input_grad
@@ -435,39 +454,17 @@ def _check_view_positions(name, tokens, positions) -> None:
 
 
 def _check_views(q, k, v, qpos, kpos, words, Vq, Vk) -> None:
-    for t in (q, k, v):
-        if t.dim() != 5:
-            raise RuntimeError("rope_attention_views: q, k and v must have 5 dimensions [b, V, H, N, 64]")
-        if t.shape[4] != HEAD_DIM:
-            raise ValueError(f"rope_attention: head dim must be {HEAD_DIM}, got {t.shape[4]}")
-        if t.dtype not in _DTYPES:
-            raise RuntimeError(f"rope_attention: unsupported dtype {t.dtype}")
-    if not (q.dtype == k.dtype == v.dtype):
-        raise RuntimeError(f"rope_attention: q, k and v differ in dtype ({q.dtype}, {k.dtype}, {v.dtype})")
-    if not (q.device == k.device == v.device):
-        raise RuntimeError("rope_attention: q, k and v are not on the same device")
+    _check_tokens(q, k, v, 5, "rope_attention_views: q, k and v must have 5 dimensions [b, V, H, N, 64]")
     if k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
         raise RuntimeError(f"rope_attention_views: shapes differ: q {tuple(q.shape)}, k {tuple(k.shape)}, "
                            f"v {tuple(v.shape)}")
     if (q.shape[1], k.shape[1]) != (Vq, Vk):
         raise RuntimeError(f"rope_attention_views: allow is [{Vq}, {Vk}] but q has {q.shape[1]} views and k has "
                            f"{k.shape[1]}")
-    if (qpos is None) != (kpos is None):
-        raise RuntimeError("rope_attention: qpos and kpos must both be given or both be None")
-    if qpos is not None:
+    if _have_positions(qpos, kpos):
         _check_view_positions("qpos", q, qpos)
         _check_view_positions("kpos", k, kpos)
-    if not q.is_cuda:
-        raise RuntimeError("rope_attention: q, k and v are on the CPU; this build only runs on a HIP device "
-                           "(no CPU fallback)")
-
-
-def _rows5(t: torch.Tensor) -> torch.Tensor:
-    """``_rows`` for [b, V, H, N, D]."""
-    es = t.element_size()
-    if t.stride(4) == 1 and t.data_ptr() % 16 == 0 and all((t.stride(i) * es) % 16 == 0 for i in range(4)):
-        return t
-    return t.contiguous()
+    _check_on_device(q)
 
 
 def _pos_rows(p):
@@ -477,44 +474,28 @@ def _pos_rows(p):
     return p.contiguous()
 
 
-def _strides5(t: torch.Tensor):
-    """(scene, token, head) element strides of a [b, V, H, N, D] tensor."""
-    return (C.c_int64 * 3)(t.stride(0), t.stride(3), t.stride(2))
-
-
-def _view_args(q, k, v, qpos, kpos, words, base, F0, scale):
-    b, Vq, H, Nq, D = q.shape
-    a = _lib.SpfAttn()
-    a.q, a.k, a.v = q.data_ptr(), k.data_ptr(), v.data_ptr()
-    a.qpos = qpos.data_ptr() if qpos is not None else None
-    a.kpos = kpos.data_ptr() if kpos is not None else None
-    a.q_stride, a.k_stride, a.v_stride = _strides5(q), _strides5(k), _strides5(v)
-    a.B, a.H, a.Nq, a.Nk, a.D, a.dtype = b, H, Nq, k.shape[3], D, _DTYPES[q.dtype]
-    a.base, a.F0, a.scale = float(base), float(F0), float(scale)
+def _view_ext(q, k, v, qpos, kpos, words) -> _lib.SpfAttnViews:
+    """What a [b,V,H,N,D] call hands the library next to ``_args``: the view counts, words and strides."""
     w = _lib.SpfAttnViews()
-    w.Vq, w.Vk = Vq, k.shape[1]
+    w.Vq, w.Vk = q.shape[1], k.shape[1]
     w.allow = (C.c_uint32 * 32)(*words)
     w.q_view_stride, w.k_view_stride, w.v_view_stride = q.stride(1), k.stride(1), v.stride(1)
     if qpos is not None:
         w.qpos_stride = (C.c_int64 * 2)(qpos.stride(0), qpos.stride(1))
         w.kpos_stride = (C.c_int64 * 2)(kpos.stride(0), kpos.stride(1))
-    return a, w
+    return w
 
 
 def attention_views_forward(q, k, v, qpos, kpos, words, base, F0, scale):
     """The forward launch: (out [b,Vq,Nq,H*D], lse [b,Vq,H,Nq] float32).  q [b,Vq,H,Nq,64], k and v [b,Vk,H,Nk,64]: views,
     read in place; ``words``: what ``allow_words`` returned."""
     _check_views(q, k, v, qpos, kpos, words, len(words), k.shape[1] if k.dim() == 5 else 0)
-    q, k, v, qpos, kpos = _rows5(q), _rows5(k), _rows5(v), _pos_rows(qpos), _pos_rows(kpos)
+    q, k, v, qpos, kpos = _rows(q), _rows(k), _rows(v), _pos_rows(qpos), _pos_rows(kpos)
     b, Vq, H, Nq, D = q.shape
     out = torch.empty(b, Vq, Nq, H * D, dtype=q.dtype, device=q.device)
     lse = torch.empty(b, Vq, H, Nq, dtype=torch.float32, device=q.device)
-    lib = _lib.load()
-    with torch.cuda.device(q.device):
-        stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-        a, w = _view_args(q, k, v, qpos, kpos, words, base, F0, scale)
-        _lib.check(lib.spf_attn_views_forward(C.byref(a), C.byref(w), C.c_void_p(out.data_ptr()),
-                                              C.c_void_p(lse.data_ptr()), stream), "spf_attn_views_forward")
+    _launch("spf_attn_views_forward", q.device, _args(q, k, v, qpos, kpos, base, F0, scale),
+            _view_ext(q, k, v, qpos, kpos, words), out, lse)
     return out, lse
 
 
@@ -526,29 +507,14 @@ def attention_views_backward(q, k, v, qpos, kpos, words, base, F0, scale, out, l
         raise RuntimeError("rope_attention_views: dq, dk and dv must have the shapes of q, k and v")
     if any(t.stride(4) != 1 or t.dtype != q.dtype for t in (dq, dk, dv)):
         raise RuntimeError("rope_attention_views: dq, dk and dv must have unit stride along D and the inputs' dtype")
-    q, k, v, qpos, kpos = _rows5(q), _rows5(k), _rows5(v), _pos_rows(qpos), _pos_rows(kpos)
-    out, dout = out.contiguous(), dout.contiguous()
-    if dout.dtype != q.dtype or out.dtype != q.dtype:
-        raise RuntimeError(f"rope_attention: gradient dtype {dout.dtype} differs from the inputs' {q.dtype}")
+    q, k, v, qpos, kpos = _rows(q), _rows(k), _rows(v), _pos_rows(qpos), _pos_rows(kpos)
+    out, dout = _saved(out, dout, q.dtype)
     b, Vq, H, Nq, D = q.shape
     delta = torch.empty(b, Vq, H, Nq, dtype=torch.float32, device=q.device)
-    lib = _lib.load()
-    with torch.cuda.device(q.device):
-        stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-        a, w = _view_args(q, k, v, qpos, kpos, words, base, F0, scale)
-        w.dq_view_stride, w.dk_view_stride, w.dv_view_stride = dq.stride(1), dk.stride(1), dv.stride(1)
-        g = _lib.SpfAttnGrads()
-        g.dq, g.dk, g.dv, g.delta = dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr()
-        g.dq_stride, g.dk_stride, g.dv_stride = _strides5(dq), _strides5(dk), _strides5(dv)
-        _lib.check(lib.spf_attn_views_backward(C.byref(a), C.byref(w), C.byref(g), C.c_void_p(out.data_ptr()),
-                                               C.c_void_p(lse.data_ptr()), C.c_void_p(dout.data_ptr()), stream),
-                   "spf_attn_views_backward")
-
-
-def _token_major5(like, V, N):
-    """An empty [b,V,H,N,D] gradient on a token-major buffer (what a following reshape(b, V, N, C) wants)."""
-    b, _, H, _, D = like.shape
-    return torch.empty(b, V, N, H, D, dtype=like.dtype, device=like.device).transpose(2, 3)
+    w = _view_ext(q, k, v, qpos, kpos, words)
+    w.dq_view_stride, w.dk_view_stride, w.dv_view_stride = dq.stride(1), dk.stride(1), dv.stride(1)
+    _launch("spf_attn_views_backward", q.device, _args(q, k, v, qpos, kpos, base, F0, scale), w,
+            _grads(dq, dk, dv, delta), out, lse, dout)
 
 
 class _RopeAttentionViews(torch.autograd.Function):
@@ -563,8 +529,7 @@ class _RopeAttentionViews(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, dout):
         q, k, v, qpos, kpos, out, lse = ctx.saved_tensors
-        dq = _token_major5(q, q.shape[1], q.shape[3])
-        dk, dv = _token_major5(q, k.shape[1], k.shape[3]), _token_major5(q, k.shape[1], k.shape[3])
+        dq, dk, dv = _token_major(q), _token_major(k), _token_major(v)
         attention_views_backward(q, k, v, qpos, kpos, *ctx.cfg, out, lse, dout, dq, dk, dv)
         need = ctx.needs_input_grad
         return (dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None, None, None, None,
@@ -641,6 +606,20 @@ def _check_module(mod, mask=None) -> None:
         raise NotImplementedError("attn_drop > 0 in training mode is not supported by the fused kernel")
 
 
+def _module_rope(mod, x, what: str, head_dim: int, *pos, then=None):
+    """What the three module forwards settle before they project: the head dim, the rope configuration and that ``x``
+    (named ``what`` in the message) is on a device -- with ``then()``, forward_views' own checks, at the place between
+    them where they have always fired.  Returns (rope keyword arguments, positions); no rope: positions of None."""
+    if head_dim != HEAD_DIM:
+        raise ValueError(f"rope_attention: head dim must be {HEAD_DIM}, got {head_dim}")
+    if then is not None:
+        then()
+    cfg = _rope_cfg(mod.rope)
+    if not x.is_cuda:
+        raise RuntimeError(f"{what} is on the CPU; this build only runs on a HIP device (no CPU fallback)")
+    return cfg, pos if cfg else (None,) * len(pos)
+
+
 def _use_matrix16(mod, t: torch.Tensor) -> bool:
     """A flagged module takes the 16-bit matrix path for 16-bit projections and the float32 path, bit for bit, for
     float32 ones: one flag serves a model inside and outside autocast."""
@@ -666,14 +645,9 @@ class Attention(nn.Module):
     def forward(self, x, xpos):
         B, N, C = x.shape
         _check_module(self)
-        if C // self.num_heads != HEAD_DIM:
-            raise ValueError(f"rope_attention: head dim must be {HEAD_DIM}, got {C // self.num_heads}")
-        cfg = _rope_cfg(self.rope)
-        if not x.is_cuda:
-            raise RuntimeError("Attention: x is on the CPU; this build only runs on a HIP device (no CPU fallback)")
+        cfg, (xpos,) = _module_rope(self, x, "Attention: x", C // self.num_heads, xpos)
         qkv = self.qkv(x).reshape(B, N, 3, self.num_heads, C // self.num_heads)
-        x = rope_attention_packed(qkv, xpos if cfg else None, scale=self.scale, matrix16=_use_matrix16(self, qkv),
-                                  **cfg)
+        x = rope_attention_packed(qkv, xpos, scale=self.scale, matrix16=_use_matrix16(self, qkv), **cfg)
         x = self.proj(x)
         x = self.proj_drop(x)
         return x
@@ -703,17 +677,11 @@ class CrossAttention(nn.Module):
         Nv = value.shape[1]
         _check_module(self, mask)
         H, D = self.num_heads, C // self.num_heads
-        if D != HEAD_DIM:
-            raise ValueError(f"rope_attention: head dim must be {HEAD_DIM}, got {D}")
-        cfg = _rope_cfg(self.rope)
-        if not query.is_cuda:
-            raise RuntimeError("CrossAttention: query is on the CPU; this build only runs on a HIP device "
-                               "(no CPU fallback)")
+        cfg, (qpos, kpos) = _module_rope(self, query, "CrossAttention: query", D, qpos, kpos)
         q = self.projq(query).reshape(B, Nq, H, D).permute(0, 2, 1, 3)
         k = self.projk(key).reshape(B, Nk, H, D).permute(0, 2, 1, 3)
         v = self.projv(value).reshape(B, Nv, H, D).permute(0, 2, 1, 3)
-        x = rope_attention(q, k, v, qpos if cfg else None, kpos if cfg else None, scale=self.scale,
-                           matrix16=_use_matrix16(self, q), **cfg)
+        x = rope_attention(q, k, v, qpos, kpos, scale=self.scale, matrix16=_use_matrix16(self, q), **cfg)
         x = self.proj(x)
         x = self.proj_drop(x)
         return x
@@ -729,21 +697,18 @@ class CrossAttention(nn.Module):
         b, Vq, Nq, C_ = query.shape
         _, Vk, Nk, _ = key.shape
         H, D = self.num_heads, C_ // self.num_heads
-        if D != HEAD_DIM:
-            raise ValueError(f"rope_attention: head dim must be {HEAD_DIM}, got {D}")
-        words, aq, ak = allow_words(allow)
-        if (aq, ak) != (Vq, Vk) or key.shape[0] != b:
-            raise RuntimeError(f"CrossAttention.forward_views: allow is [{aq}, {ak}], query {tuple(query.shape)}, key "
-                               f"{tuple(key.shape)}")
-        cfg = _rope_cfg(self.rope)
-        if not query.is_cuda:
-            raise RuntimeError("CrossAttention: query is on the CPU; this build only runs on a HIP device "
-                               "(no CPU fallback)")
+
+        def allow_fits():
+            _, aq, ak = allow_words(allow)
+            if (aq, ak) != (Vq, Vk) or key.shape[0] != b:
+                raise RuntimeError(f"CrossAttention.forward_views: allow is [{aq}, {ak}], query {tuple(query.shape)}, "
+                                   f"key {tuple(key.shape)}")
+
+        cfg, (qpos, kpos) = _module_rope(self, query, "CrossAttention: query", D, qpos, kpos, then=allow_fits)
         q = self.projq(query).reshape(b, Vq, Nq, H, D).transpose(2, 3)
         k = self.projk(key).reshape(b, Vk, Nk, H, D).transpose(2, 3)
         v = self.projv(key).reshape(b, Vk, Nk, H, D).transpose(2, 3)
-        x = rope_attention_views(q, k, v, qpos if cfg else None, kpos if cfg else None, allow=allow, scale=self.scale,
-                                 **cfg)
+        x = rope_attention_views(q, k, v, qpos, kpos, allow=allow, scale=self.scale, **cfg)
         x = self.proj(x)
         x = self.proj_drop(x)
         return x

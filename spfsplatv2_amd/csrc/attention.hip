@@ -37,31 +37,19 @@
 // scene's query views, and query view i reads key view s iff bit s of a host-known word allow[i] is set.  The walk over
 // the other side becomes a walk over the allowed views in ascending order and, inside, over each view's tiles; an
 // excluded view is never loaded.  Everything about views is a function of blockIdx and kernel arguments: scalar registers.
-#include "rope_math.h"
+//
+// attention_tiles.h holds what this file shares with attention16.hip: the tile sizes, AttnArgs / AttnGradArgs and their
+// fill, load4 / store4, Stage and stage_load, acc_row, unrotate_half and store_row.  This file owns the float32 LDS image
+// (stage_commit, own_rows), everything of MASK, NORM and VIEWS, and the row-dot kernel, which attention16.hip launches
+// through launch_attn_delta.
+#include "attention_tiles.h"
 
 namespace spf {
 
 namespace {
 
-typedef float f16v __attribute__((ext_vector_type(16)));
-
-constexpr int kAttnD = 64;          // head dim (the only one)
-constexpr int kAttnT = 32;          // rows of a staged tile = rows a wave owns
-constexpr int kAttnOwn = 128;       // rows a block owns
 constexpr int kAttnLd = 65;         // LDS pitch of a staged row, floats
 
-struct AttnArgs {
-    const void *q, *k, *v;
-    const int64_t *qpos, *kpos;
-    int64_t qs[3], ks[3], vs[3];    // element strides: batch, token, head
-    int B, H, Nq, Nk;
-    float scale;
-    RopeFreq f;                     // +F0 / base^(q/16)
-};
-struct AttnGradArgs {
-    void *dq, *dk, *dv;
-    int64_t dqs[3], dks[3], dvs[3];
-};
 // What the flagged instantiations read on top of AttnArgs.  MASK: score += mask[b,h,q,k], read in place through element
 // strides (0: broadcast; the key stride is 1), float32 additive or uint8 (nonzero: the key takes part, zero: -inf).
 // NORM: LayerNorm(64) with weight and bias of every q and every k row while it is staged, before the rotation.
@@ -102,57 +90,6 @@ __device__ __forceinline__ int view_step(uint32_t& rest) {
     return d + 1;
 }
 
-template <typename T> __device__ __forceinline__ void load4(const T* p, float* f);
-template <> __device__ __forceinline__ void load4<float>(const float* p, float* f) {
-    const f4a v = *reinterpret_cast<const f4a*>(p);
-    f[0] = v[0]; f[1] = v[1]; f[2] = v[2]; f[3] = v[3];
-}
-template <typename H> struct __attribute__((aligned(8))) Half4 { H h[4]; };
-template <typename H> __device__ __forceinline__ void load4h(const H* p, float* f) {
-    const Half4<H> v = *reinterpret_cast<const Half4<H>*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) f[i] = to_f<H>(v.h[i]);
-}
-template <> __device__ __forceinline__ void load4<__half>(const __half* p, float* f) { load4h(p, f); }
-template <> __device__ __forceinline__ void load4<__hip_bfloat16>(const __hip_bfloat16* p, float* f) { load4h(p, f); }
-
-template <typename T> __device__ __forceinline__ void store4(T* p, float a, float b, float c, float d);
-template <> __device__ __forceinline__ void store4<float>(float* p, float a, float b, float c, float d) {
-    *reinterpret_cast<f4a*>(p) = f4a{a, b, c, d};
-}
-template <typename H> __device__ __forceinline__ void store4h(H* p, float a, float b, float c, float d) {
-    Half4<H> v;
-    v.h[0] = from_f<H>(a); v.h[1] = from_f<H>(b); v.h[2] = from_f<H>(c); v.h[3] = from_f<H>(d);
-    *reinterpret_cast<Half4<H>*>(p) = v;
-}
-template <> __device__ __forceinline__ void store4<__half>(__half* p, float a, float b, float c, float d) { store4h(p, a, b, c, d); }
-template <> __device__ __forceinline__ void store4<__hip_bfloat16>(__hip_bfloat16* p, float a, float b, float c, float d) { store4h(p, a, b, c, d); }
-
-// One lane's share of a staged tile of 32 rows x 64: row tid >> 3, and of that row the four (u, v) pairs with
-// frequencies q0 .. q0 + 3 of half x (y positions rotate d < 32, x positions d >= 32; u at 32 x + q, v at 32 x + 16 + q).
-struct Stage {
-    float u[4], v[4], p;
-};
-// NARROW (the VIEWS kernels, whose `base` moves from view to view): the lane's offset into the view is formed in 32
-// bits -- a uniform base plus a 32-bit lane offset is one address register per lane instead of two, which is what keeps
-// the VIEWS dk/dv pass inside its plain sibling's registers; the host refuses a view whose rows reach past 2^31 elements.
-template <typename T, bool NARROW = false>
-__device__ __forceinline__ void stage_load(Stage& r, const T* __restrict__ base, int64_t stride_n,
-                                           const int64_t* __restrict__ pos, int row0, int N, int tid) {
-    const int row = row0 + (tid >> 3), part = tid & 7, x = part >> 2, q0 = (part & 3) * 4;
-    r.p = 0.f;
-    if (row < N) {
-        const T* __restrict__ s;
-        if constexpr (NARROW) s = base + (uint32_t)(row * (int)stride_n + 32 * x + q0);
-        else s = base + (int64_t)row * stride_n + 32 * x + q0;
-        load4<T>(s, r.u);
-        load4<T>(s + 16, r.v);
-        if (pos) r.p = NARROW ? (float)pos[(uint32_t)(row * 2 + x)] : (float)pos[(int64_t)row * 2 + x];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) r.u[k] = r.v[k] = 0.f;
-    }
-}
 // rotate (rot) by +angle, scale by mult, write into the LDS image
 __device__ __forceinline__ void stage_commit(const Stage& r, float* __restrict__ s_t, bool rot, const RopeFreq& f,
                                              float mult, int tid) {
@@ -172,8 +109,6 @@ __device__ __forceinline__ void stage_commit(const Stage& r, float* __restrict__
         d[16 + k] = v * mult;
     }
 }
-
-__device__ __forceinline__ int acc_row(int r, int kl) { return (r & 3) + 8 * (r >> 2) + 4 * kl; }
 
 // ---- NORM ----------------------------------------------------------------------------------------------------------
 // The four parameter vectors in LDS: [0] q weight, [1] q bias, [2] k weight, [3] k bias (only kernels that call this
@@ -305,34 +240,6 @@ __device__ __forceinline__ void own_rows(float (&ra)[32], const T* __restrict__ 
                 if (b) rb[s] = s_b[il * kAttnLd + 2 * s + kl];
             }
         }
-    }
-}
-
-// one half (y or x) of a row's gradient rotated by -angle; p = the row's position along that axis
-__device__ __forceinline__ void unrotate_half(f16v& a, float p, const RopeFreq& f, int kl) {
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {               // u: registers 0..7 (d < 16 of the half), v: registers 8..15 (d + 16)
-        float sn, cs;
-        rope_sincos(p * f.inv[(r & 3) + 8 * (r >> 2) + 4 * kl], sn, cs);
-        const float u = a[r], v = a[r + 8];
-        a[r] = fmaf(u, cs, v * sn);
-        a[r + 8] = fmaf(v, cs, -(u * sn));
-    }
-}
-
-// gradient of a rotated row back to the unrotated one (rotation by -angle) and its store: acc0 / acc1 hold d < 32 / d >= 32
-// of the row on this lane (rows of the accumulator = d), `g` = its address, pos = the row's (y, x) or null
-template <typename T>
-__device__ __forceinline__ void store_row(T* __restrict__ g, f16v acc0, f16v acc1, float mult, const int64_t* __restrict__ pos,
-                                          const RopeFreq& f, int kl) {
-#pragma unroll
-    for (int x = 0; x < 2; ++x) {
-        f16v a = x ? acc1 : acc0;
-        if (pos) unrotate_half(a, (float)pos[x], f, kl);
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq)
-            store4<T>(g + 32 * x + 8 * gq + 4 * kl, a[4 * gq] * mult, a[4 * gq + 1] * mult, a[4 * gq + 2] * mult,
-                      a[4 * gq + 3] * mult);
     }
 }
 
@@ -931,12 +838,7 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn_dq_kernel(typename ArgsOf<
 template <bool X>
 typename ArgsOf<X>::type make_args(const SpfAttn& p, [[maybe_unused]] const SpfAttnExt* e) {
     typename ArgsOf<X>::type a;
-    a.q = p.q; a.k = p.k; a.v = p.v;
-    a.qpos = p.qpos; a.kpos = p.kpos;
-    for (int i = 0; i < 3; ++i) { a.qs[i] = p.q_stride[i]; a.ks[i] = p.k_stride[i]; a.vs[i] = p.v_stride[i]; }
-    a.B = p.B; a.H = p.H; a.Nq = p.Nq; a.Nk = p.Nk;
-    a.scale = p.scale;
-    a.f = rope_freq(kAttnD, p.base, p.F0);
+    static_cast<AttnArgs&>(a) = make_attn_args(p);
     if constexpr (X) {
         a.x.mask = e->mask;
         for (int i = 0; i < 3; ++i) a.x.ms[i] = e->mask_stride[i];
@@ -947,15 +849,6 @@ typename ArgsOf<X>::type make_args(const SpfAttn& p, [[maybe_unused]] const SpfA
     }
     return a;
 }
-
-AttnGradArgs make_grad_args(const SpfAttnGrads& gr) {
-    AttnGradArgs g;
-    g.dq = gr.dq; g.dk = gr.dk; g.dv = gr.dv;
-    for (int i = 0; i < 3; ++i) { g.dqs[i] = gr.dq_stride[i]; g.dks[i] = gr.dk_stride[i]; g.dvs[i] = gr.dv_stride[i]; }
-    return g;
-}
-
-inline int attn_blocks(int n) { return (n + kAttnOwn - 1) / kAttnOwn; }
 
 template <typename T, bool MASK, bool NORM>
 hipError_t attn_forward(const SpfAttn& p, const SpfAttnExt* e, void* out, float* lse, hipStream_t stream) {
@@ -968,18 +861,15 @@ template <typename T, bool MASK, bool NORM>
 hipError_t attn_backward(const SpfAttn& p, const SpfAttnGrads& gr, const SpfAttnExt* e, const void* out, const float* lse,
                          const void* dout, hipStream_t stream) {
     auto a = make_args<MASK || NORM>(p, e);
-    const AttnGradArgs g = make_grad_args(gr);
+    const AttnGradArgs g = make_attn_grad_args(gr);
     const T* go = static_cast<const T*>(dout);
-    const int64_t rows = (int64_t)p.B * p.Nq * p.H;
     const int qblk = attn_blocks(p.Nq), kblk = attn_blocks(p.Nk);
     [[maybe_unused]] float *part_q = nullptr, *part_k = nullptr;    // NORM: the two passes' partials, q blocks first
     if constexpr (NORM) {
         part_q = e->partials;
         part_k = e->partials + (int64_t)p.B * p.H * qblk * 2 * kAttnD;
     }
-    spf_attn_delta_kernel<T><<<(unsigned)((rows + kBlock - 1) / kBlock), kBlock, 0, stream>>>(
-        static_cast<const T*>(out), go, gr.delta, p.B, p.H, p.Nq);
-    hipError_t err = hipGetLastError();
+    hipError_t err = launch_attn_delta(p.dtype, out, dout, gr.delta, p.B, p.H, p.Nq, stream);
     if (err != hipSuccess) return err;
     if constexpr (NORM) a.x.part = part_q;
     spf_attn_dq_kernel<T, MASK, NORM><<<dim3(qblk, p.H, p.B), kBlock, 0, stream>>>(a, g, go, lse, gr.delta);
@@ -1021,7 +911,7 @@ hipError_t attn_dispatch(int dtype, const SpfAttnExt* e, F f) {
 // words: SpfAttnViews.allow itself (forward, dq pass) or its transpose (dk/dv pass)
 AttnArgsV make_view_args(const SpfAttn& p, const SpfAttnViews& w, bool transpose) {
     AttnArgsV a;
-    static_cast<AttnArgs&>(a) = make_args<false>(p, nullptr);
+    static_cast<AttnArgs&>(a) = make_attn_args(p);
     a.w.Vq = w.Vq; a.w.Vk = w.Vk;
     for (int i = 0; i < 32; ++i) a.w.words[i] = 0;
     for (int i = 0; i < w.Vq; ++i)
@@ -1047,12 +937,9 @@ hipError_t attn_views_forward(const SpfAttn& p, const SpfAttnViews& w, void* out
 template <typename T>
 hipError_t attn_views_backward(const SpfAttn& p, const SpfAttnViews& w, const SpfAttnGrads& gr, const void* out,
                                const float* lse, const void* dout, hipStream_t stream) {
-    const AttnGradArgs g = make_grad_args(gr);
+    const AttnGradArgs g = make_attn_grad_args(gr);
     const T* go = static_cast<const T*>(dout);
-    const int64_t rows = (int64_t)p.B * w.Vq * p.Nq * p.H;
-    spf_attn_delta_kernel<T><<<(unsigned)((rows + kBlock - 1) / kBlock), kBlock, 0, stream>>>(
-        static_cast<const T*>(out), go, gr.delta, p.B * w.Vq, p.H, p.Nq);
-    hipError_t err = hipGetLastError();
+    hipError_t err = launch_attn_delta(p.dtype, out, dout, gr.delta, p.B * w.Vq, p.H, p.Nq, stream);
     if (err != hipSuccess) return err;
     spf_attn_dq_kernel<T, false, false, true><<<dim3(attn_blocks(p.Nq), p.H, p.B * w.Vq), kBlock, 0, stream>>>(
         make_view_args(p, w, false), g, go, lse, gr.delta);
@@ -1063,7 +950,25 @@ hipError_t attn_views_backward(const SpfAttn& p, const SpfAttnViews& w, const Sp
     return hipGetLastError();
 }
 
+template <typename T>
+hipError_t attn_delta(const void* out, const void* dout, float* delta, int B, int H, int Nq, hipStream_t stream) {
+    const int64_t rows = (int64_t)B * Nq * H;
+    spf_attn_delta_kernel<T><<<(unsigned)((rows + kBlock - 1) / kBlock), kBlock, 0, stream>>>(
+        static_cast<const T*>(out), static_cast<const T*>(dout), delta, B, H, Nq);
+    return hipGetLastError();
+}
+
 }  // namespace
+
+// The row-dot pre-pass of every backward: this file's three and attention16.hip's.
+hipError_t launch_attn_delta(int dtype, const void* out, const void* dout, float* delta, int B, int H, int Nq,
+                             hipStream_t stream) {
+    switch (dtype) {
+        case 0: return attn_delta<float>(out, dout, delta, B, H, Nq, stream);
+        case 1: return attn_delta<__half>(out, dout, delta, B, H, Nq, stream);
+        default: return attn_delta<__hip_bfloat16>(out, dout, delta, B, H, Nq, stream);
+    }
+}
 
 hipError_t launch_attn_views_forward(const SpfAttn& p, const SpfAttnViews& w, void* out, float* lse, hipStream_t stream) {
     switch (p.dtype) {

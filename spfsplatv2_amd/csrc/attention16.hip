@@ -27,41 +27,26 @@
 // not carried: the gate against eager 16-bit is met without it and it costs 10 % of the step (DESIGN.md 7k has the
 // figures of both forms: it lowers dq's error about 3 x where the logits reach +-80 and nowhere else), so the two passes
 // are independent of each other.  Every sum has a fixed order: bitwise reproducible.
-#include "rope_math.h"
+//
+// attention_tiles.h holds what this file shares with attention.hip: the tile sizes, AttnArgs / AttnGradArgs and their
+// fill, load4 / store4, Stage and stage_load, acc_row, unrotate_half and store_row; the row-dot pre-pass is
+// attention.hip's kernel behind launch_attn_delta.  This file owns the 16-bit LDS images (stage_commit, own_rows), the
+// operand fragments and the three matrix kernels.
+#include "attention_tiles.h"
 
 namespace spf {
 
 namespace {
 
-typedef float f16v __attribute__((ext_vector_type(16)));
 typedef short s8v __attribute__((ext_vector_type(8)));          // a matrix operand: 8 x 16 bits
 typedef short s4v __attribute__((ext_vector_type(4)));
 typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 typedef __bf16 b8v __attribute__((ext_vector_type(8)));
 typedef unsigned short bits16;
 
-constexpr int kD = 64;              // head dim (the only one)
-constexpr int kT = 32;              // rows of a staged tile = rows a wave owns
-constexpr int kOwn = 128;           // rows a block owns
 constexpr int kRowLd = 72;          // pitch of the row image, elements
 constexpr int kTrLd = 36;           // pitch of the transposed image, elements
 
-struct Args16 {
-    const void *q, *k, *v;
-    const int64_t *qpos, *kpos;
-    int64_t qs[3], ks[3], vs[3];    // element strides: batch, token, head
-    int B, H, Nq, Nk;
-    float scale;
-    RopeFreq f;
-};
-struct GradArgs16 {
-    void *dq, *dk, *dv;
-    int64_t dqs[3], dks[3], dvs[3];
-};
-
-template <typename T> __device__ __forceinline__ float bits_to_f(bits16 b);
-template <> __device__ __forceinline__ float bits_to_f<__half>(bits16 b) { return __half2float(__ushort_as_half(b)); }
-template <> __device__ __forceinline__ float bits_to_f<__hip_bfloat16>(bits16 b) { return __uint_as_float((uint32_t)b << 16); }
 template <typename T> __device__ __forceinline__ bits16 f_to_bits(float v);
 template <> __device__ __forceinline__ bits16 f_to_bits<__half>(float v) { return __half_as_ushort(__float2half(v)); }
 template <> __device__ __forceinline__ bits16 f_to_bits<__hip_bfloat16>(float v) {
@@ -76,38 +61,8 @@ template <> __device__ __forceinline__ f16v mfma16<__hip_bfloat16>(s8v a, s8v b,
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(b8v, a), __builtin_bit_cast(b8v, b), c, 0, 0, 0);
 }
 
-struct __attribute__((aligned(8))) Bits4 { bits16 h[4]; };
-template <typename T> __device__ __forceinline__ void load4(const T* p, float* f) {
-    const Bits4 v = *reinterpret_cast<const Bits4*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) f[i] = bits_to_f<T>(v.h[i]);
-}
-template <typename T> __device__ __forceinline__ void store4(T* p, float a, float b, float c, float d) {
-    Bits4 v;
-    v.h[0] = f_to_bits<T>(a); v.h[1] = f_to_bits<T>(b); v.h[2] = f_to_bits<T>(c); v.h[3] = f_to_bits<T>(d);
-    *reinterpret_cast<Bits4*>(p) = v;
-}
+struct __attribute__((aligned(8))) Bits4 { bits16 h[4]; };    // four elements of an LDS image
 
-// One lane's share of a staged tile of 32 rows x 64 (attention.hip's split): row tid >> 3, and of that row the four
-// (u, v) pairs with frequencies q0 .. q0 + 3 of half x (u at 32 x + q, v at 32 x + 16 + q).
-struct Stage {
-    float u[4], v[4], p;
-};
-template <typename T>
-__device__ __forceinline__ void stage_load(Stage& r, const T* __restrict__ base, int64_t stride_n,
-                                           const int64_t* __restrict__ pos, int row0, int N, int tid) {
-    const int row = row0 + (tid >> 3), part = tid & 7, x = part >> 2, q0 = (part & 3) * 4;
-    r.p = 0.f;
-    if (row < N) {
-        const T* __restrict__ s = base + (int64_t)row * stride_n + 32 * x + q0;
-        load4<T>(s, r.u);
-        load4<T>(s + 16, r.v);
-        if (pos) r.p = (float)pos[(int64_t)row * 2 + x];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) r.u[k] = r.v[k] = 0.f;
-    }
-}
 // rotate (rot) by +angle in float32, round once to T, write the images the kernel reads (ROW: s_row, TR: s_tr)
 template <typename T, bool ROW, bool TR>
 __device__ __forceinline__ void stage_commit(const Stage& r, bits16* __restrict__ s_row, bits16* __restrict__ s_tr, bool rot,
@@ -160,8 +115,6 @@ template <typename T> __device__ __forceinline__ s8v acc_frag(const f16v& x, int
     return r;
 }
 
-__device__ __forceinline__ int acc_row(int r, int kl) { return (r & 3) + 8 * (r >> 2) + 4 * kl; }
-
 // The rows a wave owns, as B operands: stage the block's 128 rows 32 at a time through the row images s_a (and s_b for a
 // second operand with the same rows, never rotated); each wave keeps its own chunk.
 template <typename T>
@@ -172,8 +125,8 @@ __device__ __forceinline__ void own_rows(s8v (&ra)[4], const T* __restrict__ a, 
 #pragma unroll 1
     for (int w = 0; w < 4; ++w) {
         Stage sa, sb;
-        stage_load<T>(sa, a, a_sn, pos, row0 + kT * w, N, tid);
-        if (b) stage_load<T>(sb, b, b_sn, nullptr, row0 + kT * w, N, tid);
+        stage_load<T>(sa, a, a_sn, pos, row0 + kAttnT * w, N, tid);
+        if (b) stage_load<T>(sb, b, b_sn, nullptr, row0 + kAttnT * w, N, tid);
         __syncthreads();
         stage_commit<T, true, false>(sa, s_a, nullptr, pos != nullptr, f, tid);
         if (b) stage_commit<T, true, false>(sb, s_b, nullptr, false, f, tid);
@@ -188,41 +141,13 @@ __device__ __forceinline__ void own_rows(s8v (&ra)[4], const T* __restrict__ a, 
     }
 }
 
-// one half (y or x) of a row's gradient rotated by -angle; p = the row's position along that axis
-__device__ __forceinline__ void unrotate_half(f16v& a, float p, const RopeFreq& f, int kl) {
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {               // u: registers 0..7 (d < 16 of the half), v: registers 8..15 (d + 16)
-        float sn, cs;
-        rope_sincos(p * f.inv[(r & 3) + 8 * (r >> 2) + 4 * kl], sn, cs);
-        const float u = a[r], v = a[r + 8];
-        a[r] = fmaf(u, cs, v * sn);
-        a[r + 8] = fmaf(v, cs, -(u * sn));
-    }
-}
-
-// A row of a transposed result (rows of the accumulator = d, acc0: d < 32, acc1: d >= 32) times mult, rotated back when
-// pos is given, rounded once and stored at g.
-template <typename T>
-__device__ __forceinline__ void store_row(T* __restrict__ g, f16v acc0, f16v acc1, float mult, const int64_t* __restrict__ pos,
-                                          const RopeFreq& f, int kl) {
-#pragma unroll
-    for (int x = 0; x < 2; ++x) {
-        f16v a = x ? acc1 : acc0;
-        if (pos) unrotate_half(a, (float)pos[x], f, kl);
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq)
-            store4<T>(g + 32 * x + 8 * gq + 4 * kl, a[4 * gq] * mult, a[4 * gq + 1] * mult, a[4 * gq + 2] * mult,
-                      a[4 * gq + 3] * mult);
-    }
-}
-
 // ---- forward -------------------------------------------------------------------------------------------------------
 template <typename T>
-__global__ __launch_bounds__(kBlock) void spf_attn16_fwd_kernel(Args16 a, T* __restrict__ out, float* __restrict__ lse) {
-    __shared__ __attribute__((aligned(16))) bits16 s_k[kT * kRowLd];
-    __shared__ __attribute__((aligned(16))) bits16 s_vt[kD * kTrLd];
+__global__ __launch_bounds__(kBlock) void spf_attn16_fwd_kernel(AttnArgs a, T* __restrict__ out, float* __restrict__ lse) {
+    __shared__ __attribute__((aligned(16))) bits16 s_k[kAttnT * kRowLd];
+    __shared__ __attribute__((aligned(16))) bits16 s_vt[kAttnD * kTrLd];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, il = lane & 31, kl = lane >> 5;
-    const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * kOwn;
+    const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * kAttnOwn;
     const T* __restrict__ qb = static_cast<const T*>(a.q) + b * a.qs[0] + h * a.qs[2];
     const T* __restrict__ kb = static_cast<const T*>(a.k) + b * a.ks[0] + h * a.ks[2];
     const T* __restrict__ vb = static_cast<const T*>(a.v) + b * a.vs[0] + h * a.vs[2];
@@ -231,8 +156,8 @@ __global__ __launch_bounds__(kBlock) void spf_attn16_fwd_kernel(Args16 a, T* __r
 
     s8v qf[4], unused[4];
     own_rows<T>(qf, qb, a.qs[1], qp, unused, nullptr, 0, q0, a.Nq, s_k, nullptr, a.f, tid);
-    const bool active = q0 + kT * wave < a.Nq;          // wave-uniform: a wave without queries only helps staging
-    const int qi = q0 + kT * wave + il;
+    const bool active = q0 + kAttnT * wave < a.Nq;          // wave-uniform: a wave without queries only helps staging
+    const int qi = q0 + kAttnT * wave + il;
 
     f16v o0, o1;
 #pragma unroll
@@ -242,14 +167,14 @@ __global__ __launch_bounds__(kBlock) void spf_attn16_fwd_kernel(Args16 a, T* __r
     stage_load<T>(sk, kb, a.ks[1], kp, 0, a.Nk, tid);
     stage_load<T>(sv, vb, a.vs[1], nullptr, 0, a.Nk, tid);
 #pragma unroll 1
-    for (int k0 = 0; k0 < a.Nk; k0 += kT) {
+    for (int k0 = 0; k0 < a.Nk; k0 += kAttnT) {
         __syncthreads();                                // the previous tile's readers are done
         stage_commit<T, true, false>(sk, s_k, nullptr, kp != nullptr, a.f, tid);
         stage_commit<T, false, true>(sv, nullptr, s_vt, false, a.f, tid);
         __syncthreads();
-        if (k0 + kT < a.Nk) {                           // in flight under the matrix instructions below
-            stage_load<T>(sk, kb, a.ks[1], kp, k0 + kT, a.Nk, tid);
-            stage_load<T>(sv, vb, a.vs[1], nullptr, k0 + kT, a.Nk, tid);
+        if (k0 + kAttnT < a.Nk) {                           // in flight under the matrix instructions below
+            stage_load<T>(sk, kb, a.ks[1], kp, k0 + kAttnT, a.Nk, tid);
+            stage_load<T>(sv, vb, a.vs[1], nullptr, k0 + kAttnT, a.Nk, tid);
         }
         if (!active) continue;
         f16v s;                                         // S^T: rows = keys, column = this lane's query
@@ -259,7 +184,7 @@ __global__ __launch_bounds__(kBlock) void spf_attn16_fwd_kernel(Args16 a, T* __r
         for (int st = 0; st < 4; ++st) s = mfma16<T>(row_frag(s_k, il, kl, st), qf[st], s);
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] *= a.scale;
-        if (k0 + kT > a.Nk) {                           // padded keys: probability 0
+        if (k0 + kAttnT > a.Nk) {                           // padded keys: probability 0
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 if (k0 + acc_row(r, kl) >= a.Nk) s[r] = -INFINITY;
@@ -291,53 +216,31 @@ __global__ __launch_bounds__(kBlock) void spf_attn16_fwd_kernel(Args16 a, T* __r
     const float lt = l + __shfl_xor(l, 32, kWave);
     if (qi >= a.Nq) return;
     if (kl == 0) lse[((int64_t)b * a.H + h) * a.Nq + qi] = m + logf(lt);
-    store_row<T>(out + (((int64_t)b * a.Nq + qi) * a.H + h) * kD, o0, o1, 1.f / lt, nullptr, a.f, kl);
+    store_row<T>(out + (((int64_t)b * a.Nq + qi) * a.H + h) * kAttnD, o0, o1, 1.f / lt, nullptr, a.f, kl);
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------
-// delta[b,h,q] = sum_d dout[b,q,h,d] * out[b,q,h,d], one lane per row, one float32 fma chain over d in ascending order
-// (attention.hip's row-dot kernel for the two element types of this file).
-template <typename T>
-__global__ __launch_bounds__(kBlock) void spf_attn16_delta_kernel(const T* __restrict__ out, const T* __restrict__ dout,
-                                                                  float* __restrict__ delta, int B, int H, int Nq) {
-    const int64_t rows = (int64_t)B * Nq * H, row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (row >= rows) return;
-    float acc = 0.f;
-#pragma unroll
-    for (int part = 0; part < 16; ++part) {
-        float o[4], g[4];
-        load4<T>(out + row * kD + 4 * part, o);
-        load4<T>(dout + row * kD + 4 * part, g);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc = fmaf(g[e], o[e], acc);
-    }
-    const int64_t bq = row / H;
-    const int h = (int)(row - bq * H);
-    const int64_t b = bq / Nq;
-    delta[(b * H + h) * Nq + (bq - b * Nq)] = acc;
-}
-
 // dq: the block owns 128 queries, walks the keys.
 template <typename T>
-__global__ __launch_bounds__(kBlock, 2) void spf_attn16_dq_kernel(Args16 a, GradArgs16 g, const T* __restrict__ dout,
+__global__ __launch_bounds__(kBlock, 2) void spf_attn16_dq_kernel(AttnArgs a, AttnGradArgs g, const T* __restrict__ dout,
                                                                   const float* __restrict__ lse,
                                                                   const float* __restrict__ delta) {
-    __shared__ __attribute__((aligned(16))) bits16 s_k[kT * kRowLd];
-    __shared__ __attribute__((aligned(16))) bits16 s_v[kT * kRowLd];
-    __shared__ __attribute__((aligned(16))) bits16 s_kt[kD * kTrLd];
+    __shared__ __attribute__((aligned(16))) bits16 s_k[kAttnT * kRowLd];
+    __shared__ __attribute__((aligned(16))) bits16 s_v[kAttnT * kRowLd];
+    __shared__ __attribute__((aligned(16))) bits16 s_kt[kAttnD * kTrLd];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, il = lane & 31, kl = lane >> 5;
-    const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * kOwn;
+    const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * kAttnOwn;
     const T* __restrict__ qb = static_cast<const T*>(a.q) + b * a.qs[0] + h * a.qs[2];
     const T* __restrict__ kb = static_cast<const T*>(a.k) + b * a.ks[0] + h * a.ks[2];
     const T* __restrict__ vb = static_cast<const T*>(a.v) + b * a.vs[0] + h * a.vs[2];
-    const T* __restrict__ gb = dout + ((int64_t)b * a.Nq * a.H + h) * kD;
+    const T* __restrict__ gb = dout + ((int64_t)b * a.Nq * a.H + h) * kAttnD;
     const int64_t* __restrict__ qp = a.qpos ? a.qpos + (int64_t)b * a.Nq * 2 : nullptr;
     const int64_t* __restrict__ kp = a.kpos ? a.kpos + (int64_t)b * a.Nk * 2 : nullptr;
 
     s8v qf[4], gf[4];
-    own_rows<T>(qf, qb, a.qs[1], qp, gf, gb, (int64_t)a.H * kD, q0, a.Nq, s_k, s_v, a.f, tid);
-    const bool active = q0 + kT * wave < a.Nq;
-    const int qi = q0 + kT * wave + il;
+    own_rows<T>(qf, qb, a.qs[1], qp, gf, gb, (int64_t)a.H * kAttnD, q0, a.Nq, s_k, s_v, a.f, tid);
+    const bool active = q0 + kAttnT * wave < a.Nq;
+    const int qi = q0 + kAttnT * wave + il;
     float my_lse = INFINITY, my_dl = 0.f;               // a padded query: probability 0
     if (qi < a.Nq) {
         my_lse = lse[((int64_t)b * a.H + h) * a.Nq + qi];
@@ -351,14 +254,14 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn16_dq_kernel(Args16 a, Grad
     stage_load<T>(sk, kb, a.ks[1], kp, 0, a.Nk, tid);
     stage_load<T>(sv, vb, a.vs[1], nullptr, 0, a.Nk, tid);
 #pragma unroll 1
-    for (int k0 = 0; k0 < a.Nk; k0 += kT) {
+    for (int k0 = 0; k0 < a.Nk; k0 += kAttnT) {
         __syncthreads();
         stage_commit<T, true, true>(sk, s_k, s_kt, kp != nullptr, a.f, tid);
         stage_commit<T, true, false>(sv, s_v, nullptr, false, a.f, tid);
         __syncthreads();
-        if (k0 + kT < a.Nk) {
-            stage_load<T>(sk, kb, a.ks[1], kp, k0 + kT, a.Nk, tid);
-            stage_load<T>(sv, vb, a.vs[1], nullptr, k0 + kT, a.Nk, tid);
+        if (k0 + kAttnT < a.Nk) {
+            stage_load<T>(sk, kb, a.ks[1], kp, k0 + kAttnT, a.Nk, tid);
+            stage_load<T>(sv, vb, a.vs[1], nullptr, k0 + kAttnT, a.Nk, tid);
         }
         if (!active) continue;
         f16v s, dp;                                     // S^T, dP^T: rows = keys, column = this lane's query
@@ -389,21 +292,21 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn16_dq_kernel(Args16 a, Grad
 
 // dk, dv: the block owns 128 keys, walks the queries.
 template <typename T>
-__global__ __launch_bounds__(kBlock, 2) void spf_attn16_dkdv_kernel(Args16 a, GradArgs16 g, const T* __restrict__ dout,
+__global__ __launch_bounds__(kBlock, 2) void spf_attn16_dkdv_kernel(AttnArgs a, AttnGradArgs g, const T* __restrict__ dout,
                                                                     const float* __restrict__ lse,
                                                                     const float* __restrict__ delta) {
-    __shared__ __attribute__((aligned(16))) bits16 s_q[kT * kRowLd];
-    __shared__ __attribute__((aligned(16))) bits16 s_do[kT * kRowLd];
-    __shared__ __attribute__((aligned(16))) bits16 s_qt[kD * kTrLd];
-    __shared__ __attribute__((aligned(16))) bits16 s_dot[kD * kTrLd];
-    __shared__ float s_lse[kT], s_dl[kT];
+    __shared__ __attribute__((aligned(16))) bits16 s_q[kAttnT * kRowLd];
+    __shared__ __attribute__((aligned(16))) bits16 s_do[kAttnT * kRowLd];
+    __shared__ __attribute__((aligned(16))) bits16 s_qt[kAttnD * kTrLd];
+    __shared__ __attribute__((aligned(16))) bits16 s_dot[kAttnD * kTrLd];
+    __shared__ float s_lse[kAttnT], s_dl[kAttnT];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, il = lane & 31, kl = lane >> 5;
-    const int b = blockIdx.z, h = blockIdx.y, k0 = blockIdx.x * kOwn;
+    const int b = blockIdx.z, h = blockIdx.y, k0 = blockIdx.x * kAttnOwn;
     const T* __restrict__ qb = static_cast<const T*>(a.q) + b * a.qs[0] + h * a.qs[2];
     const T* __restrict__ kb = static_cast<const T*>(a.k) + b * a.ks[0] + h * a.ks[2];
     const T* __restrict__ vb = static_cast<const T*>(a.v) + b * a.vs[0] + h * a.vs[2];
-    const T* __restrict__ gb = dout + ((int64_t)b * a.Nq * a.H + h) * kD;
-    const int64_t g_sn = (int64_t)a.H * kD;
+    const T* __restrict__ gb = dout + ((int64_t)b * a.Nq * a.H + h) * kAttnD;
+    const int64_t g_sn = (int64_t)a.H * kAttnD;
     const int64_t* __restrict__ qp = a.qpos ? a.qpos + (int64_t)b * a.Nq * 2 : nullptr;
     const int64_t* __restrict__ kp = a.kpos ? a.kpos + (int64_t)b * a.Nk * 2 : nullptr;
     const float* __restrict__ lse_r = lse + ((int64_t)b * a.H + h) * a.Nq;
@@ -411,7 +314,7 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn16_dkdv_kernel(Args16 a, Gr
 
     s8v kf[4], vf[4];
     own_rows<T>(kf, kb, a.ks[1], kp, vf, vb, a.vs[1], k0, a.Nk, s_q, s_do, a.f, tid);
-    const bool active = k0 + kT * wave < a.Nk;
+    const bool active = k0 + kAttnT * wave < a.Nk;
 
     f16v dk0, dk1, dv0, dv1;
 #pragma unroll
@@ -420,19 +323,19 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn16_dkdv_kernel(Args16 a, Gr
     float rl = INFINITY, rd = 0.f;                      // a padded query: probability 0
     stage_load<T>(sq, qb, a.qs[1], qp, 0, a.Nq, tid);
     stage_load<T>(sd, gb, g_sn, nullptr, 0, a.Nq, tid);
-    if (tid < kT && tid < a.Nq) { rl = lse_r[tid]; rd = dl_r[tid]; }
+    if (tid < kAttnT && tid < a.Nq) { rl = lse_r[tid]; rd = dl_r[tid]; }
 #pragma unroll 1
-    for (int q0 = 0; q0 < a.Nq; q0 += kT) {
+    for (int q0 = 0; q0 < a.Nq; q0 += kAttnT) {
         __syncthreads();
         stage_commit<T, true, true>(sq, s_q, s_qt, qp != nullptr, a.f, tid);
         stage_commit<T, true, true>(sd, s_do, s_dot, false, a.f, tid);
-        if (tid < kT) { s_lse[tid] = rl; s_dl[tid] = rd; }
+        if (tid < kAttnT) { s_lse[tid] = rl; s_dl[tid] = rd; }
         __syncthreads();
-        if (q0 + kT < a.Nq) {
-            stage_load<T>(sq, qb, a.qs[1], qp, q0 + kT, a.Nq, tid);
-            stage_load<T>(sd, gb, g_sn, nullptr, q0 + kT, a.Nq, tid);
+        if (q0 + kAttnT < a.Nq) {
+            stage_load<T>(sq, qb, a.qs[1], qp, q0 + kAttnT, a.Nq, tid);
+            stage_load<T>(sd, gb, g_sn, nullptr, q0 + kAttnT, a.Nq, tid);
             rl = INFINITY; rd = 0.f;
-            if (tid < kT && q0 + kT + tid < a.Nq) { rl = lse_r[q0 + kT + tid]; rd = dl_r[q0 + kT + tid]; }
+            if (tid < kAttnT && q0 + kAttnT + tid < a.Nq) { rl = lse_r[q0 + kAttnT + tid]; rd = dl_r[q0 + kAttnT + tid]; }
         }
         if (!active) continue;
         f16v s, dp;                                     // S, dP: rows = queries, column = this lane's key
@@ -460,7 +363,7 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn16_dkdv_kernel(Args16 a, Gr
         }
     }
     if (!active) return;
-    const int key = k0 + kT * wave + il;
+    const int key = k0 + kAttnT * wave + il;
     if (key >= a.Nk) return;
     store_row<T>(static_cast<T*>(g.dv) + b * g.dvs[0] + (int64_t)key * g.dvs[1] + h * g.dvs[2], dv0, dv1, 1.f, nullptr, a.f,
                  kl);
@@ -468,42 +371,25 @@ __global__ __launch_bounds__(kBlock, 2) void spf_attn16_dkdv_kernel(Args16 a, Gr
                  kp ? kp + (int64_t)key * 2 : nullptr, a.f, kl);
 }
 
-Args16 make_args(const SpfAttn& p) {
-    Args16 a;
-    a.q = p.q; a.k = p.k; a.v = p.v;
-    a.qpos = p.qpos; a.kpos = p.kpos;
-    for (int i = 0; i < 3; ++i) { a.qs[i] = p.q_stride[i]; a.ks[i] = p.k_stride[i]; a.vs[i] = p.v_stride[i]; }
-    a.B = p.B; a.H = p.H; a.Nq = p.Nq; a.Nk = p.Nk;
-    a.scale = p.scale;
-    a.f = rope_freq(kD, p.base, p.F0);
-    return a;
-}
-
-inline int blocks_of(int n) { return (n + kOwn - 1) / kOwn; }
-
 template <typename T>
 hipError_t forward16(const SpfAttn& p, void* out, float* lse, hipStream_t stream) {
-    spf_attn16_fwd_kernel<T><<<dim3(blocks_of(p.Nq), p.H, p.B), kBlock, 0, stream>>>(make_args(p), static_cast<T*>(out), lse);
+    spf_attn16_fwd_kernel<T><<<dim3(attn_blocks(p.Nq), p.H, p.B), kBlock, 0, stream>>>(make_attn_args(p),
+                                                                                       static_cast<T*>(out), lse);
     return hipGetLastError();
 }
 
 template <typename T>
 hipError_t backward16(const SpfAttn& p, const SpfAttnGrads& gr, const void* out, const float* lse, const void* dout,
                       hipStream_t stream) {
-    const Args16 a = make_args(p);
-    GradArgs16 g;
-    g.dq = gr.dq; g.dk = gr.dk; g.dv = gr.dv;
-    for (int i = 0; i < 3; ++i) { g.dqs[i] = gr.dq_stride[i]; g.dks[i] = gr.dk_stride[i]; g.dvs[i] = gr.dv_stride[i]; }
+    const AttnArgs a = make_attn_args(p);
+    const AttnGradArgs g = make_attn_grad_args(gr);
     const T* go = static_cast<const T*>(dout);
-    const int64_t rows = (int64_t)p.B * p.Nq * p.H;
-    spf_attn16_delta_kernel<T><<<(unsigned)((rows + kBlock - 1) / kBlock), kBlock, 0, stream>>>(
-        static_cast<const T*>(out), go, gr.delta, p.B, p.H, p.Nq);
-    hipError_t err = hipGetLastError();
+    hipError_t err = launch_attn_delta(p.dtype, out, dout, gr.delta, p.B, p.H, p.Nq, stream);
     if (err != hipSuccess) return err;
-    spf_attn16_dq_kernel<T><<<dim3(blocks_of(p.Nq), p.H, p.B), kBlock, 0, stream>>>(a, g, go, lse, gr.delta);
+    spf_attn16_dq_kernel<T><<<dim3(attn_blocks(p.Nq), p.H, p.B), kBlock, 0, stream>>>(a, g, go, lse, gr.delta);
     err = hipGetLastError();
     if (err != hipSuccess) return err;
-    spf_attn16_dkdv_kernel<T><<<dim3(blocks_of(p.Nk), p.H, p.B), kBlock, 0, stream>>>(a, g, go, lse, gr.delta);
+    spf_attn16_dkdv_kernel<T><<<dim3(attn_blocks(p.Nk), p.H, p.B), kBlock, 0, stream>>>(a, g, go, lse, gr.delta);
     return hipGetLastError();
 }
 

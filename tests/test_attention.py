@@ -127,6 +127,19 @@ def test_module_errors_raise_before_any_launch():
         spf.CrossAttention(128, num_heads=1)(x, x, x, pos, pos)
     with pytest.raises(TypeError, match="cuRoPE2D"):
         spf.Attention(128, rope=object(), num_heads=2)(x, pos)
+    # the modules' own wording of the CPU refusal, whole
+    with pytest.raises(RuntimeError, match=r"^Attention: x is on the CPU; this build only runs on a HIP device "
+                                           r"\(no CPU fallback\)$"):
+        att(x, pos)
+    with pytest.raises(RuntimeError, match=r"^CrossAttention: query is on the CPU; this build only runs on a HIP device "
+                                           r"\(no CPU fallback\)$"):
+        cross(x, x, x, pos, pos)
+    with pytest.raises(RuntimeError, match=r"^CrossAttention: query is on the CPU; this build only runs on a HIP device "
+                                           r"\(no CPU fallback\)$"):
+        cross.forward_views(x[None], x[None], pos[None], pos[None], [[True]])
+    with pytest.raises(TypeError, match="cuRoPE2D"):                  # the rope's refusal comes before the CPU's
+        bad = spf.CrossAttention(128, rope=object(), num_heads=2)
+        bad.forward_views(x[None], x[None], pos[None], pos[None], [[True]])
 
 
 def _attn(**kw):
