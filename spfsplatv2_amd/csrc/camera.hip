@@ -5,7 +5,7 @@
 // camera translation, get_fov (src/geometry/projection.py:269-283), tan(fov/2), get_projection_matrix
 // (cuda_splatting.py:15-42), extrinsics.inverse() and the two transposes.  On MI355X those ~100 launches of
 // a few microseconds each cost more host time than the whole rasterizer costs device time.
-#include "spf_common.h"
+#include "point_slots.h"
 
 namespace spf {
 
@@ -146,9 +146,9 @@ __global__ void spf_camera_bwd_kernel(SpfCamera c, const float* __restrict__ dL_
 // single wave had (the kernel is pure latency: 1,954 records per render on the 500,000-Gaussian workload took 13.8 us).
 __global__ __launch_bounds__(kBlock) void spf_camera_bwd_reduce_kernel(SpfCamera c, const float* __restrict__ vpartial,
                                                                        int nblk, float* __restrict__ dL_dext) {
-    __shared__ float s_w[kBlock / kWave][12];
+    __shared__ SumRow<12> s_sum;
     __shared__ float s_dv[16];
-    const int r = blockIdx.x, lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const int r = blockIdx.x;
     float acc[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) acc[k] = 0.f;
@@ -159,22 +159,13 @@ __global__ __launch_bounds__(kBlock) void spf_camera_bwd_reduce_kernel(SpfCamera
         acc[4] += b4.x; acc[5] += b4.y; acc[6] += b4.z; acc[7] += b4.w;
         acc[8] += c4.x; acc[9] += c4.y; acc[10] += c4.z; acc[11] += c4.w;
     }
-#pragma unroll
-    for (int k = 0; k < 12; ++k) acc[k] = wave_sum(acc[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 12; ++k) s_w[wave][k] = acc[k];
-    }
-    __syncthreads();
+    block_sum(acc, s_sum);
     if (threadIdx.x == 0) {
-        float tot[12];
-#pragma unroll
-        for (int k = 0; k < 12; ++k) tot[k] = (s_w[0][k] + s_w[1][k]) + (s_w[2][k] + s_w[3][k]);
         // partial k < 9: dL/dVm[4i+j] with k = 3i+j (i, j < 3); k = 9+j: dL/dVm[12+j]; the last column gets none
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) s_dv[4 * i + j] = j < 3 ? tot[i < 3 ? 3 * i + j : 9 + j] : 0.f;
+            for (int j = 0; j < 4; ++j) s_dv[4 * i + j] = j < 3 ? acc[i < 3 ? 3 * i + j : 9 + j] : 0.f;
         camera_bwd_one(c, r, s_dv, dL_dext);
     }
 }

@@ -4,7 +4,7 @@
 // eager PyTorch runs as four elementwise/reduction kernels forward and four more backward over the 25 MB image batch.
 // Here: one pass forward (read both images, deterministic two-level sum) and one pass backward
 // (grad = (2 * weight / N) * dL/dloss * (prediction - image), the upstream scalar read on the device: no sync).
-#include "spf_common.h"
+#include "point_slots.h"
 
 namespace spf {
 
@@ -22,7 +22,7 @@ __global__ __launch_bounds__(kBlock) void spf_mse_fwd_kernel(const float* __rest
                                                              const float* __restrict__ target, int64_t n,
                                                              float* __restrict__ partial, float scale2,
                                                              float* __restrict__ unit) {
-    __shared__ float s_w[kBlock / kWave];
+    __shared__ SumRow<1> s_sum;
     const int64_t n4 = n >> 2;
     const float4* __restrict__ p4 = reinterpret_cast<const float4*>(pred);
     const float4* __restrict__ t4 = reinterpret_cast<const float4*>(target);
@@ -39,10 +39,8 @@ __global__ __launch_bounds__(kBlock) void spf_mse_fwd_kernel(const float* __rest
         acc += d * d;
         if (GRAD) unit[(n4 << 2) + threadIdx.x] = scale2 * d;
     }
-    const float w = wave_sum(acc);
-    if ((threadIdx.x & (kWave - 1)) == 0) s_w[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+    const float tot = block_sum(acc, s_sum);
+    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
 // grad[i] *= dL/dloss, in place -- and nothing at all when dL/dloss is exactly 1 (every block leaves after one scalar
@@ -62,13 +60,11 @@ __global__ __launch_bounds__(kBlock) void spf_mse_scale_kernel(float* __restrict
 
 __global__ __launch_bounds__(kBlock) void spf_mse_final_kernel(const float* __restrict__ partial, int nblocks,
                                                                float scale, float* __restrict__ loss) {
-    __shared__ float s_w[kBlock / kWave];
-    float tot = 0.f;
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) tot += partial[b];
-    const float w = wave_sum(tot);
-    if ((threadIdx.x & (kWave - 1)) == 0) s_w[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) *loss = scale * ((s_w[0] + s_w[1]) + (s_w[2] + s_w[3]));
+    __shared__ SumRow<1> s_sum;
+    float acc = 0.f;
+    for (int b = threadIdx.x; b < nblocks; b += kBlock) acc += partial[b];
+    const float tot = block_sum(acc, s_sum);
+    if (threadIdx.x == 0) *loss = scale * tot;
 }
 
 __global__ __launch_bounds__(kBlock) void spf_mse_bwd_kernel(const float* __restrict__ pred,

@@ -28,7 +28,7 @@
 //   spf_lpips_head_bwd_kernel   dL/da and / or dL/db of one tap; the upstream gradient is read on the device.  Where a
 //                               feature vector is all zero the 1 / ||a|| term is taken as 0 (autograd gives NaN there).
 // No atomics anywhere: results are run-to-run identical and an image's numbers do not depend on its batch.
-#include "spf_common.h"
+#include "point_slots.h"
 
 namespace spf {
 
@@ -397,7 +397,7 @@ __global__ __launch_bounds__(kBlock) void spf_lpips_head_kernel(const float* __r
                                                                 const float* __restrict__ lin, int HW, int nblk,
                                                                 float* __restrict__ partial) {
     constexpr int C = CPL * 64;
-    __shared__ float s_w[4];
+    __shared__ SumRow<1> s_sum;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = blockIdx.y;
     float l[CPL];
 #pragma unroll
@@ -424,9 +424,11 @@ __global__ __launch_bounds__(kBlock) void spf_lpips_head_kernel(const float* __r
         }
         accw += wave_sum(d);
     }
-    if (lane == 0) s_w[wave] = accw;
+    // accw is a wave total already (the same in every lane), so the row is filled here and not by block_sum; it is
+    // written once per block: nobody reads it before this write
+    if (lane == 0) s_sum.w[wave][0] = __float_as_uint(accw);
     __syncthreads();
-    if (threadIdx.x == 0) partial[(int64_t)n * nblk + blockIdx.x] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+    if (threadIdx.x == 0) partial[(int64_t)n * nblk + blockIdx.x] = sum_row_f32(s_sum, 0);
 }
 
 struct LpipsHeadTaps {
@@ -445,14 +447,7 @@ __global__ __launch_bounds__(kBlock) void spf_lpips_head_sum_kernel(const float*
         const float* __restrict__ p = partial + t.off[k] + (int64_t)n * t.nblk[k];
         double acc = 0.0;
         for (int i = threadIdx.x; i < t.nblk[k]; i += kBlock) acc += (double)p[i];
-        s_d[threadIdx.x] = acc;
-        __syncthreads();
-        for (int s = kBlock / 2; s > 0; s >>= 1) {
-            if ((int)threadIdx.x < s) s_d[threadIdx.x] += s_d[threadIdx.x + s];
-            __syncthreads();
-        }
-        tot += s_d[0] * t.inv_hw[k];
-        __syncthreads();
+        tot += block_tree_sum<kBlock>(acc, s_d) * t.inv_hw[k];
     }
     if (threadIdx.x == 0) out[n] = (float)tot;
 }
@@ -462,13 +457,8 @@ __global__ __launch_bounds__(kBlock) void spf_lpips_mean_kernel(const float* __r
     __shared__ double s_d[kBlock];
     double acc = 0.0;
     for (int i = threadIdx.x; i < N; i += kBlock) acc += (double)out[i];
-    s_d[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) s_d[threadIdx.x] += s_d[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) mean[0] = (float)((double)weight * (s_d[0] / (double)N));
+    const double tot = block_tree_sum<kBlock>(acc, s_d);
+    if (threadIdx.x == 0) mean[0] = (float)((double)weight * (tot / (double)N));
 }
 
 // dA, dB: [N,HW,C] or null.  Upstream of pair n: up[n], or with `is_mean` up[0] * mean_scale (= weight / N).

@@ -16,14 +16,12 @@
 //                             H W points, re-read from L2 each round (a scene is 768 KB at 256 x 256; keeping x/z, y/z
 //                             of 64 points per lane would take 128 VGPRs at four waves per SIMD, and LDS holds a third
 //                             of them); per-point float32, the two running sums float64 in a fixed order
-#include "spf_common.h"
+#include "point_slots.h"
 #include "pose_math.h"
 
 namespace spf {
 
 constexpr int kPoseBlock = 64;
-constexpr int kDepthChunk = 4 * kBlock;
-constexpr int kDepthMaxGrid = 2048;
 constexpr int kFocalBlock = 1024;
 
 __device__ __forceinline__ PoseScene pose_scene(const float* enc, int64_t stride_b, int64_t stride_v, int scene, int v,
@@ -68,24 +66,6 @@ hipError_t launch_pose_compose_bwd(const float* enc, int64_t stride_b, int64_t s
 }
 
 // ---- depth projection --------------------------------------------------------------------------------------------
-// Four points of a slot: three 16-byte loads when the image's base is 16-byte aligned and all four exist.
-__device__ __forceinline__ void depth_load4(const float* __restrict__ img, bool aligned, int p0, int n, float (&v)[12]) {
-    if (aligned && p0 + 3 < n) {
-        const float4* p4 = reinterpret_cast<const float4*>(img + 3 * (int64_t)p0);
-        const float4 a = p4[0], b = p4[1], c = p4[2];
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-        v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-        v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const bool in = p0 + k < n;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[3 * k + c] = in ? img[3 * (int64_t)(p0 + k) + c] : 0.f;
-        }
-    }
-}
-
 // Row 2 of W = inverse(pose) (float64, general), rounded to float32.
 __device__ __forceinline__ void depth_row(const float* __restrict__ poses, int img, float* __restrict__ s_row) {
     double P[16], Wd[16];
@@ -107,19 +87,13 @@ __global__ __launch_bounds__(kBlock) void spf_depth_fwd_kernel(const float* __re
         __syncthreads();
         const float w0 = s_row[0], w1 = s_row[1], w2 = s_row[2], w3 = s_row[3];
         const float* base = pts + (int64_t)img * stride_img;
-        const int p0 = chunk * kDepthChunk + 4 * threadIdx.x;
+        const int p0 = chunk * kSlotPoints + 4 * threadIdx.x;
         float v[12], o[4];
-        depth_load4(base, (reinterpret_cast<uintptr_t>(base) & 15) == 0, p0, n, v);
+        load4_xyz(base, aligned16(base), p0, n, v);
 #pragma unroll
         for (int k = 0; k < 4; ++k) o[k] = w0 * v[3 * k] + w1 * v[3 * k + 1] + w2 * v[3 * k + 2] + w3;
         float* out = depth + (int64_t)img * n;
-        if ((reinterpret_cast<uintptr_t>(out) & 15) == 0 && p0 + 3 < n) {
-            *reinterpret_cast<float4*>(out + p0) = make_float4(o[0], o[1], o[2], o[3]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (p0 + k < n) out[p0 + k] = o[k];
-        }
+        store4(out, aligned16(out), p0, n, o);
     }
 }
 
@@ -129,16 +103,16 @@ __global__ __launch_bounds__(kBlock) void spf_depth_bwd_kernel(const float* __re
                                                                int64_t nslots, const float* __restrict__ gdepth,
                                                                float* __restrict__ dpts, float* __restrict__ gpartial) {
     __shared__ float s_row[4];
-    __shared__ float s_g[kBlock / kWave][4];
+    __shared__ SumRow<4> s_sum;
     for (int64_t slot = blockIdx.x; slot < nslots; slot += gridDim.x) {
         const int img = (int)(slot / nchunk), chunk = (int)(slot - (int64_t)img * nchunk);
-        __syncthreads();
+        __syncthreads();                                  // the previous slot's readers of s_row are done
         if (threadIdx.x == 0) depth_row(poses, img, s_row);
         __syncthreads();
         const float w0 = s_row[0], w1 = s_row[1], w2 = s_row[2];
         const float* base = pts + (int64_t)img * stride_img;
         const float* gin = gdepth + (int64_t)img * n;
-        const int p0 = chunk * kDepthChunk + 4 * threadIdx.x;
+        const int p0 = chunk * kSlotPoints + 4 * threadIdx.x;
         float g[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) g[k] = p0 + k < n ? gin[p0 + k] : 0.f;
@@ -151,23 +125,11 @@ __global__ __launch_bounds__(kBlock) void spf_depth_bwd_kernel(const float* __re
                 o[3 * k + 1] = g[k] * w1;
                 o[3 * k + 2] = g[k] * w2;
             }
-            if ((reinterpret_cast<uintptr_t>(out) & 15) == 0 && p0 + 3 < n) {
-                float4* o4 = reinterpret_cast<float4*>(out + 3 * (int64_t)p0);
-                o4[0] = make_float4(o[0], o[1], o[2], o[3]);
-                o4[1] = make_float4(o[4], o[5], o[6], o[7]);
-                o4[2] = make_float4(o[8], o[9], o[10], o[11]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (p0 + k < n) {
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) out[3 * (int64_t)(p0 + k) + c] = o[3 * k + c];
-                    }
-            }
+            store4_xyz(out, aligned16(out), p0, n, o);
         }
-        if (gpartial) {
+        if (gpartial) {                             // (the same for the whole block: block_sum's barriers are uniform)
             float v[12];
-            depth_load4(base, (reinterpret_cast<uintptr_t>(base) & 15) == 0, p0, n, v);
+            load4_xyz(base, aligned16(base), p0, n, v);
             float a[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {           // (g is 0 past the end, and so are the points loaded there)
@@ -176,16 +138,10 @@ __global__ __launch_bounds__(kBlock) void spf_depth_bwd_kernel(const float* __re
                 a[2] += g[k] * v[3 * k + 2];
                 a[3] += g[k];
             }
+            block_sum(a, s_sum);
+            if (threadIdx.x == 0) {
 #pragma unroll
-            for (int c = 0; c < 4; ++c) a[c] = wave_sum(a[c]);
-            if ((threadIdx.x & (kWave - 1)) == 0) {
-#pragma unroll
-                for (int c = 0; c < 4; ++c) s_g[threadIdx.x >> 6][c] = a[c];
-            }
-            __syncthreads();
-            if (threadIdx.x < 4) {
-                const int t = threadIdx.x;
-                gpartial[4 * slot + t] = (s_g[0][t] + s_g[1][t]) + (s_g[2][t] + s_g[3][t]);
+                for (int c = 0; c < 4; ++c) gpartial[4 * slot + c] = a[c];
             }
         }
     }
@@ -195,24 +151,18 @@ __global__ __launch_bounds__(kBlock) void spf_depth_bwd_kernel(const float* __re
 __global__ __launch_bounds__(kBlock) void spf_depth_cam_kernel(const float* __restrict__ poses, int nchunk,
                                                                const float* __restrict__ gpartial,
                                                                float* __restrict__ dposes) {
-    __shared__ float s_w[kBlock / kWave][4];
-    const int img = blockIdx.x, lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    __shared__ SumRow<4> s_sum;
+    const int img = blockIdx.x;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int c = threadIdx.x; c < nchunk; c += kBlock) {
         const float4 x = *reinterpret_cast<const float4*>(gpartial + 4 * ((int64_t)img * nchunk + c));
         acc[0] += x.x; acc[1] += x.y; acc[2] += x.z; acc[3] += x.w;
     }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc[k] = wave_sum(acc[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s_w[wave][k] = acc[k];
-    }
-    __syncthreads();
+    block_sum(acc, s_sum);
     if (threadIdx.x != 0) return;
     double tot[4], P[16], Wd[16];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) tot[k] = (double)((s_w[0][k] + s_w[1][k]) + (s_w[2][k] + s_w[3][k]));
+    for (int k = 0; k < 4; ++k) tot[k] = (double)acc[k];
 #pragma unroll
     for (int i = 0; i < 16; ++i) P[i] = (double)poses[16 * (int64_t)img + i];
     inv4<double>(P, Wd);
@@ -226,18 +176,16 @@ __global__ __launch_bounds__(kBlock) void spf_depth_cam_kernel(const float* __re
 }
 
 int64_t depth_slots(int N, int n, int* nchunk) {
-    const int nc = (n + kDepthChunk - 1) / kDepthChunk;
+    const int nc = (int)slot_chunks(n);
     if (nchunk) *nchunk = nc;
     return (int64_t)N * nc;
 }
-
-static int depth_grid(int64_t nslots) { return (int)(nslots < kDepthMaxGrid ? nslots : kDepthMaxGrid); }
 
 hipError_t launch_depth_fwd(const float* pts, int64_t stride_img, const float* poses, int N, int n, float* depth,
                             hipStream_t stream) {
     int nchunk = 0;
     const int64_t nslots = depth_slots(N, n, &nchunk);
-    spf_depth_fwd_kernel<<<depth_grid(nslots), kBlock, 0, stream>>>(pts, stride_img, poses, n, nchunk, nslots, depth);
+    spf_depth_fwd_kernel<<<slot_grid(nslots), kBlock, 0, stream>>>(pts, stride_img, poses, n, nchunk, nslots, depth);
     return hipGetLastError();
 }
 
@@ -245,28 +193,13 @@ hipError_t launch_depth_bwd(const float* pts, int64_t stride_img, const float* p
                             float* dpts, float* gpartial, float* dposes, hipStream_t stream) {
     int nchunk = 0;
     const int64_t nslots = depth_slots(N, n, &nchunk);
-    spf_depth_bwd_kernel<<<depth_grid(nslots), kBlock, 0, stream>>>(pts, stride_img, poses, n, nchunk, nslots, gdepth,
+    spf_depth_bwd_kernel<<<slot_grid(nslots), kBlock, 0, stream>>>(pts, stride_img, poses, n, nchunk, nslots, gdepth,
                                                                     dpts, gpartial);
     if (gpartial) spf_depth_cam_kernel<<<N, kBlock, 0, stream>>>(poses, nchunk, gpartial, dposes);
     return hipGetLastError();
 }
 
 // ---- pose errors -------------------------------------------------------------------------------------------------
-// Fixed-order block sum of three doubles per lane; the totals land in s[0][0..2].
-template <int NT>
-__device__ __forceinline__ void block_sum3(double (*s)[3], const double* x) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) s[threadIdx.x][k] = x[k];
-    __syncthreads();
-    for (int half = NT / 2; half > 0; half >>= 1) {
-        if ((int)threadIdx.x < half) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) s[threadIdx.x][k] += s[threadIdx.x + half][k];
-        }
-        __syncthreads();
-    }
-}
-
 __global__ __launch_bounds__(kBlock) void spf_pose_error_kernel(const float* __restrict__ pred,
                                                                 const float* __restrict__ gt, int N,
                                                                 float* __restrict__ errors, float* __restrict__ means) {
@@ -281,8 +214,11 @@ __global__ __launch_bounds__(kBlock) void spf_pose_error_kernel(const float* __r
             acc[k] += e[k];
         }
     }
-    block_sum3<kBlock>(s, acc);
-    if (threadIdx.x < 3) means[threadIdx.x] = (float)(s[0][threadIdx.x] / (double)N);
+    block_tree_sum<kBlock>(acc, s);
+    if (threadIdx.x < 3) {                               // one float64 division per lane, not three in a row
+        const double tot = threadIdx.x == 0 ? acc[0] : (threadIdx.x == 1 ? acc[1] : acc[2]);
+        means[threadIdx.x] = (float)(tot / (double)N);
+    }
 }
 
 hipError_t launch_pose_error(const float* pred, const float* gt, int N, float* errors, float* means,
@@ -312,11 +248,7 @@ __device__ __forceinline__ void focal_round(const FocalArgs& a, const float* __r
     for (int p0 = 4 * threadIdx.x; p0 < n; p0 += 4 * kFocalBlock) {
         float v[12];
         if (wide && p0 + 3 < n) {
-            const float4* p4 = reinterpret_cast<const float4*>(base + 3 * (int64_t)p0);
-            const float4 x = p4[0], y = p4[1], z = p4[2];
-            v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-            v[4] = y.x; v[5] = y.y; v[6] = y.z; v[7] = y.w;
-            v[8] = z.x; v[9] = z.y; v[10] = z.z; v[11] = z.w;
+            load12(base + 3 * (int64_t)p0, v);
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -350,10 +282,9 @@ __device__ __forceinline__ void focal_round(const FocalArgs& a, const float* __r
             }
         }
     }
-    __syncthreads();                                             // the previous round's readers of s[0] are done
-    block_sum3<kFocalBlock>(s, acc);
-    s1 = s[0][0];
-    s2 = s[0][1];
+    block_tree_sum<kFocalBlock>(acc, s);
+    s1 = acc[0];
+    s2 = acc[1];
 }
 
 __global__ __launch_bounds__(kFocalBlock) void spf_focal_kernel(FocalArgs a, float* __restrict__ focal,
@@ -361,7 +292,7 @@ __global__ __launch_bounds__(kFocalBlock) void spf_focal_kernel(FocalArgs a, flo
     __shared__ double s[kFocalBlock][3];
     const int scene = blockIdx.x;
     const float* base = a.pts + scene * a.stride_scene;
-    const bool wide = a.stride_row == 3 * (int64_t)a.W && (reinterpret_cast<uintptr_t>(base) & 15) == 0;
+    const bool wide = a.stride_row == 3 * (int64_t)a.W && aligned16(base);
     const float ppx = a.pp ? a.pp[scene * a.pp_stride] : (float)a.W / 2.f;
     const float ppy = a.pp ? a.pp[scene * a.pp_stride + 1] : (float)a.H / 2.f;
     double s1, s2;

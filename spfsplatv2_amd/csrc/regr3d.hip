@@ -24,12 +24,10 @@
 // so nothing per point is kept anywhere.  No float atomics; every float sum is lane -> wave -> block -> slot -> row in a
 // fixed order, and a slot's content depends on (row, chunk) only: results are run-to-run identical and do not depend
 // on the batch strides.
-#include "spf_common.h"
+#include "point_slots.h"
 
 namespace spf {
 
-constexpr int kRegrChunk = 4 * kBlock;    // points per slot
-constexpr int kRegrMaxGrid = 2048;        // memory-bound: a few blocks per CU, grid-stride over the slots
 constexpr int kRegrSeg = 8;               // slots per block of a histogram pass (8,192 points share one LDS flush)
 constexpr int kRegrBins = 2048;           // bins of the widest digit (11 bits)
 constexpr int kRegrRanks = 4;             // floor / ceil of the two quantile ranks
@@ -58,7 +56,7 @@ __host__ __device__ inline RegrScratch regr_scratch(int B, int nchunk) {
     return s;
 }
 
-int regr3d_chunks(int H, int W) { return (int)(((int64_t)H * W + kRegrChunk - 1) / kRegrChunk); }
+int regr3d_chunks(int H, int W) { return (int)slot_chunks((int64_t)H * W); }
 int64_t regr3d_scratch_words(int B, int H, int W) { return regr_scratch(B, regr3d_chunks(H, W)).words; }
 
 // |p| by one explicit chain, so that every pass forms the same bits
@@ -70,27 +68,8 @@ __device__ __forceinline__ const float* regr_gt(const SpfRegr3d& a, int v, int b
 __device__ __forceinline__ const float* regr_pr(const SpfRegr3d& a, int v, int b) {
     return v == 0 ? a.pr_pts1 + (int64_t)b * a.stride_pr1 : a.pr_pts2 + (int64_t)b * a.stride_pr2;
 }
-__device__ __forceinline__ bool regr_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// Four points of a slot (lane-owned: points p0 .. p0 + 3 of the row): three 16-byte loads when the row's base is 16-byte
-// aligned and all four exist, scalar loads otherwise (a point past the end reads as 0 and is never counted).
-__device__ __forceinline__ void regr_load4(const float* __restrict__ row, bool aligned, int p0, int n, float (&v)[12]) {
-    if (aligned && p0 + 3 < n) {
-        const float4* p4 = reinterpret_cast<const float4*>(row + 3 * (int64_t)p0);
-        const float4 a = p4[0], b = p4[1], c = p4[2];
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-        v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-        v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const bool in = p0 + k < n;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[3 * k + c] = in ? row[3 * (int64_t)(p0 + k) + c] : 0.f;
-        }
-    }
-}
-// The four confidences of the same points (one 16-byte load), or +inf when the mask does not read them (dist_clip)
+// The four confidences of a lane's points (one 16-byte load), or +inf when the mask does not read them (dist_clip)
 __device__ __forceinline__ void regr_conf4(const SpfRegr3d& a, int v, int b, int p0, int n, float (&c)[4]) {
     if (a.has_dist_clip) {
 #pragma unroll
@@ -98,32 +77,11 @@ __device__ __forceinline__ void regr_conf4(const SpfRegr3d& a, int v, int b, int
         return;
     }
     const float* row = (v == 0 ? a.conf1 : a.conf2) + (int64_t)b * n;
-    if (regr_aligned(row) && p0 + 3 < n) {
-        const float4 x = *reinterpret_cast<const float4*>(row + p0);
-        c[0] = x.x; c[1] = x.y; c[2] = x.z; c[3] = x.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) c[k] = p0 + k < n ? row[p0 + k] : 0.f;
-    }
+    load4(row, aligned16(row), p0, n, c);
 }
 // valid (loss_point.py:214-215, 232-237): NaN compares false everywhere, as in torch
 __device__ __forceinline__ bool regr_valid(float dis, float conf, float qlo, float qhi) {
     return dis >= qlo && dis <= qhi && conf >= kRegrConfMin;
-}
-
-__device__ __forceinline__ float regr_block_sum(float x, float* __restrict__ s_w) {
-    const float ws = wave_sum(x);
-    __syncthreads();                                   // the previous use of s_w is over
-    if ((threadIdx.x & (kWave - 1)) == 0) s_w[threadIdx.x >> 6] = ws;
-    __syncthreads();
-    return (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
-}
-__device__ __forceinline__ uint32_t regr_block_sum_u32(uint32_t x, uint32_t* __restrict__ s_n) {
-    const uint32_t wn = wave_sum_u32(x);
-    __syncthreads();
-    if ((threadIdx.x & (kWave - 1)) == 0) s_n[threadIdx.x >> 6] = wn;
-    __syncthreads();
-    return (s_n[0] + s_n[1]) + (s_n[2] + s_n[3]);
 }
 
 // ---- selection -----------------------------------------------------------------------------------------------------
@@ -162,12 +120,12 @@ __global__ __launch_bounds__(kBlock) void spf_regr3d_hist_kernel(SpfRegr3d a, in
         for (int i = threadIdx.x; i < kRegrRanks * kRegrBins; i += kBlock) s_hist[i] = 0u;
         __syncthreads();
         const float* base = regr_gt(a, v, b);
-        const bool al = regr_aligned(base);
+        const bool al = aligned16(base);
         const int c_end = min(nchunk, (seg + 1) * kRegrSeg);
         for (int chunk = seg * kRegrSeg; chunk < c_end; ++chunk) {
-            const int p0 = chunk * kRegrChunk + 4 * threadIdx.x;
+            const int p0 = chunk * kSlotPoints + 4 * threadIdx.x;
             float x[12];
-            regr_load4(base, al, p0, n, x);
+            load4_xyz(base, al, p0, n, x);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 if (p0 + k >= n) continue;
@@ -277,8 +235,7 @@ __global__ __launch_bounds__(kBlock) void spf_regr3d_clip_kernel(int rows, float
 __global__ __launch_bounds__(kBlock) void spf_regr3d_mask_kernel(SpfRegr3d a, int nchunk, int64_t nslots,
                                                                  const float* __restrict__ q, uint32_t* __restrict__ pcnt,
                                                                  float* __restrict__ ppr, float* __restrict__ pgt) {
-    __shared__ float s_w[kBlock / kWave];
-    __shared__ uint32_t s_n[kBlock / kWave];
+    __shared__ SumRow<3> s_sum;
     const int n = a.H * a.W;
     for (int64_t slot = blockIdx.x; slot < nslots; slot += gridDim.x) {
         const int row = (int)(slot / nchunk), chunk = (int)(slot - (int64_t)row * nchunk);
@@ -286,28 +243,26 @@ __global__ __launch_bounds__(kBlock) void spf_regr3d_mask_kernel(SpfRegr3d a, in
         const float qlo = q[2 * row], qhi = q[2 * row + 1];
         const float* gt = regr_gt(a, v, b);
         const float* pr = regr_pr(a, v, b);
-        const int p0 = chunk * kRegrChunk + 4 * threadIdx.x;
+        const int p0 = chunk * kSlotPoints + 4 * threadIdx.x;
         float x[12], y[12], cf[4];
-        regr_load4(gt, regr_aligned(gt), p0, n, x);
-        regr_load4(pr, regr_aligned(pr), p0, n, y);
+        load4_xyz(gt, aligned16(gt), p0, n, x);
+        load4_xyz(pr, aligned16(pr), p0, n, y);
         regr_conf4(a, v, b, p0, n, cf);
-        uint32_t cnt = 0u;
-        float spr = 0.f, sgt = 0.f;
+        uint32_t cnt[1] = {0u};
+        float s[2] = {0.f, 0.f};                          // sums of |pr| and of |gt|
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float dis = regr_norm3(x[3 * k], x[3 * k + 1], x[3 * k + 2]);
             const bool valid = p0 + k < n && regr_valid(dis, cf[k], qlo, qhi);
-            cnt += valid ? 1u : 0u;
-            sgt += valid ? dis : 0.f;
-            spr += valid ? regr_norm3(y[3 * k], y[3 * k + 1], y[3 * k + 2]) : 0.f;
+            cnt[0] += valid ? 1u : 0u;
+            s[1] += valid ? dis : 0.f;
+            s[0] += valid ? regr_norm3(y[3 * k], y[3 * k + 1], y[3 * k + 2]) : 0.f;
         }
-        const uint32_t bn = regr_block_sum_u32(cnt, s_n);
-        const float bpr = regr_block_sum(spr, s_w);
-        const float bgt = regr_block_sum(sgt, s_w);
+        block_sum(s, cnt, s_sum);
         if (threadIdx.x == 0) {
-            pcnt[slot] = bn;
-            ppr[slot] = bpr;
-            pgt[slot] = bgt;
+            pcnt[slot] = cnt[0];
+            ppr[slot] = s[0];
+            pgt[slot] = s[1];
         }
     }
 }
@@ -318,22 +273,22 @@ __global__ __launch_bounds__(kBlock) void spf_regr3d_norm_kernel(int B, int nchu
                                                                  const uint32_t* __restrict__ pcnt,
                                                                  const float* __restrict__ ppr,
                                                                  const float* __restrict__ pgt, float* __restrict__ stats) {
-    __shared__ float s_w[kBlock / kWave];
-    __shared__ uint32_t s_n[kBlock / kWave];
+    __shared__ SumRow<4> s_sum;
     const int b = blockIdx.x;
-    uint32_t c0 = 0u, c1 = 0u;
-    float spr = 0.f, sgt = 0.f;
+    uint32_t cnt[2] = {0u, 0u};                           // valid points of view 0, of view 1
+    float s[2] = {0.f, 0.f};                              // sums of |pr| and of |gt|
     for (int k = threadIdx.x; k < 2 * nchunk; k += kBlock) {
         const int v = k / nchunk, c = k - v * nchunk;
         const int64_t slot = ((int64_t)v * B + b) * nchunk + c;
         const uint32_t cc = pcnt[slot];
-        c0 += v == 0 ? cc : 0u;
-        c1 += v == 0 ? 0u : cc;
-        spr += ppr[slot];
-        sgt += pgt[slot];
+        cnt[0] += v == 0 ? cc : 0u;
+        cnt[1] += v == 0 ? 0u : cc;
+        s[0] += ppr[slot];
+        s[1] += pgt[slot];
     }
-    const uint32_t n0 = regr_block_sum_u32(c0, s_n), n1 = regr_block_sum_u32(c1, s_n);
-    const float tpr = regr_block_sum(spr, s_w), tgt = regr_block_sum(sgt, s_w);
+    block_sum(s, cnt, s_sum);
+    const uint32_t n0 = cnt[0], n1 = cnt[1];
+    const float tpr = s[0], tgt = s[1];
     if (threadIdx.x == 0) {
         int32_t* nv = reinterpret_cast<int32_t*>(stats);
         nv[b] = (int32_t)n0;
@@ -365,7 +320,7 @@ __device__ __forceinline__ RegrPt regr_point(const float* __restrict__ pr, const
 __global__ __launch_bounds__(kBlock) void spf_regr3d_loss_kernel(SpfRegr3d a, int nchunk, int64_t nslots,
                                                                  const float* __restrict__ stats,
                                                                  float* __restrict__ ploss, float* __restrict__ pdot) {
-    __shared__ float s_w[kBlock / kWave];
+    __shared__ SumRow<2> s_sum;
     const int n = a.H * a.W;
     const float* q = stats + 2 * (int64_t)a.B;
     for (int64_t slot = blockIdx.x; slot < nslots; slot += gridDim.x) {
@@ -375,25 +330,24 @@ __global__ __launch_bounds__(kBlock) void spf_regr3d_loss_kernel(SpfRegr3d a, in
         const float nf_pr = stats[6 * (int64_t)a.B + b], nf_gt = stats[7 * (int64_t)a.B + b];
         const float* gt = regr_gt(a, v, b);
         const float* pr = regr_pr(a, v, b);
-        const int p0 = chunk * kRegrChunk + 4 * threadIdx.x;
+        const int p0 = chunk * kSlotPoints + 4 * threadIdx.x;
         float x[12], y[12], cf[4];
-        regr_load4(gt, regr_aligned(gt), p0, n, x);
-        regr_load4(pr, regr_aligned(pr), p0, n, y);
+        load4_xyz(gt, aligned16(gt), p0, n, x);
+        load4_xyz(pr, aligned16(pr), p0, n, y);
         regr_conf4(a, v, b, p0, n, cf);
-        float se = 0.f, sd = 0.f;
+        float s[2] = {0.f, 0.f};                          // sums of e and of u . pr
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float dis = regr_norm3(x[3 * k], x[3 * k + 1], x[3 * k + 2]);
             const bool valid = p0 + k < n && regr_valid(dis, cf[k], qlo, qhi);
             const RegrPt r = regr_point(y + 3 * k, x + 3 * k, nf_pr, nf_gt);
-            se += valid ? r.e : 0.f;
-            sd += valid ? fmaf(r.uz, y[3 * k + 2], fmaf(r.uy, y[3 * k + 1], r.ux * y[3 * k])) : 0.f;
+            s[0] += valid ? r.e : 0.f;
+            s[1] += valid ? fmaf(r.uz, y[3 * k + 2], fmaf(r.uy, y[3 * k + 1], r.ux * y[3 * k])) : 0.f;
         }
-        const float be = regr_block_sum(se, s_w);
-        const float bd = regr_block_sum(sd, s_w);
+        block_sum(s, s_sum);
         if (threadIdx.x == 0) {
-            ploss[slot] = be;
-            pdot[slot] = bd;
+            ploss[slot] = s[0];
+            pdot[slot] = s[1];
         }
     }
 }
@@ -405,31 +359,33 @@ __global__ __launch_bounds__(kBlock) void spf_regr3d_final_kernel(int B, int nch
                                                                   const float* __restrict__ ploss,
                                                                   const float* __restrict__ pdot, float* __restrict__ T,
                                                                   float* __restrict__ scale, float* __restrict__ loss) {
-    __shared__ float s_w[kBlock / kWave];
-    __shared__ uint32_t s_n[kBlock / kWave];
+    __shared__ SumRow<2> s_t;
+    __shared__ SumRow<4> s_sum;
     if ((int)blockIdx.x < B) {
         const int b = blockIdx.x;
-        for (int v = 0; v < 2; ++v) {
-            float acc = 0.f;
-            for (int c = threadIdx.x; c < nchunk; c += kBlock) acc += pdot[((int64_t)v * B + b) * nchunk + c];
-            const float tot = regr_block_sum(acc, s_w);
-            if (threadIdx.x == 0) T[(int64_t)v * B + b] = tot;
+        float acc[2] = {0.f, 0.f};
+#pragma unroll
+        for (int v = 0; v < 2; ++v)
+            for (int c = threadIdx.x; c < nchunk; c += kBlock) acc[v] += pdot[((int64_t)v * B + b) * nchunk + c];
+        block_sum(acc, s_t);
+        if (threadIdx.x == 0) {
+            T[b] = acc[0];
+            T[(int64_t)B + b] = acc[1];
         }
         return;
     }
     const int32_t* nv = reinterpret_cast<const int32_t*>(stats);
-    float lv[2];
-    uint32_t Nv[2];
+    float lv[2] = {0.f, 0.f};
+    uint32_t Nv[2] = {0u, 0u};
+    const int64_t m = (int64_t)B * nchunk;
 #pragma unroll
     for (int v = 0; v < 2; ++v) {
-        uint32_t cnt = 0u;
-        for (int b = threadIdx.x; b < B; b += kBlock) cnt += (uint32_t)nv[(int64_t)v * B + b];
-        Nv[v] = regr_block_sum_u32(cnt, s_n);
-        float acc = 0.f;
-        const int64_t m = (int64_t)B * nchunk;
-        for (int64_t k = threadIdx.x; k < m; k += kBlock) acc += ploss[(int64_t)v * m + k];
-        lv[v] = regr_block_sum(acc, s_w) / (float)Nv[v];
+        for (int b = threadIdx.x; b < B; b += kBlock) Nv[v] += (uint32_t)nv[(int64_t)v * B + b];
+        for (int64_t k = threadIdx.x; k < m; k += kBlock) lv[v] += ploss[(int64_t)v * m + k];
     }
+    block_sum(lv, Nv, s_sum);
+#pragma unroll
+    for (int v = 0; v < 2; ++v) lv[v] = lv[v] / (float)Nv[v];
     if (threadIdx.x == 0) {
         loss[0] = disable_view1 ? lv[1] : lv[0] + lv[1];
         scale[0] = (Nv[0] && !disable_view1) ? 1.f / (float)Nv[0] : 0.f;
@@ -462,10 +418,10 @@ __global__ __launch_bounds__(kBlock) void spf_regr3d_bwd_kernel(SpfRegr3d a, int
         const float through = (a.normalize && nb && nf_pr > kRegrNfMin) ? g * S / (nf_pr * nf_pr * (float)nb) : 0.f;
         const float* gt = regr_gt(a, v, b);
         const float* pr = regr_pr(a, v, b);
-        const int p0 = chunk * kRegrChunk + 4 * threadIdx.x;
+        const int p0 = chunk * kSlotPoints + 4 * threadIdx.x;
         float x[12], y[12], cf[4], o[12];
-        regr_load4(gt, regr_aligned(gt), p0, n, x);
-        regr_load4(pr, regr_aligned(pr), p0, n, y);
+        load4_xyz(gt, aligned16(gt), p0, n, x);
+        load4_xyz(pr, aligned16(pr), p0, n, y);
         regr_conf4(a, v, b, p0, n, cf);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -479,30 +435,16 @@ __global__ __launch_bounds__(kBlock) void spf_regr3d_bwd_kernel(SpfRegr3d a, int
             o[3 * k + 2] = valid ? direct * r.uz - w * y[3 * k + 2] : 0.f;
         }
         float* out = (v == 0 ? d_pr1 : d_pr2) + (int64_t)b * n * 3;
-        if (regr_aligned(out) && p0 + 3 < n) {
-            float4* o4 = reinterpret_cast<float4*>(out + 3 * (int64_t)p0);
-            o4[0] = make_float4(o[0], o[1], o[2], o[3]);
-            o4[1] = make_float4(o[4], o[5], o[6], o[7]);
-            o4[2] = make_float4(o[8], o[9], o[10], o[11]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (p0 + k < n) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) out[3 * (int64_t)(p0 + k) + c] = o[3 * k + c];
-                }
-        }
+        store4_xyz(out, aligned16(out), p0, n, o);
     }
 }
-
-static int regr_grid(int64_t nslots) { return (int)(nslots < kRegrMaxGrid ? nslots : kRegrMaxGrid); }
 
 template <int PASS>
 static void regr_select_pass(const SpfRegr3d& a, int nchunk, uint32_t* hist, uint32_t* sel, float* q,
                              hipStream_t stream) {
     const int nseg = (nchunk + kRegrSeg - 1) / kRegrSeg;
     const int64_t nslots = 2 * (int64_t)a.B * nseg;
-    spf_regr3d_hist_kernel<PASS><<<regr_grid(nslots), kBlock, 0, stream>>>(a, nchunk, nseg, nslots, sel, hist);
+    spf_regr3d_hist_kernel<PASS><<<slot_grid(nslots), kBlock, 0, stream>>>(a, nchunk, nseg, nslots, sel, hist);
     spf_regr3d_pick_kernel<PASS><<<2 * a.B, kBlock, 0, stream>>>(a.H * a.W, sel, hist, q);
 }
 
@@ -517,17 +459,17 @@ hipError_t launch_regr3d_fwd(const SpfRegr3d& a, void* scratch, float* stats, fl
         spf_regr3d_clip_kernel<<<(rows + kBlock - 1) / kBlock, kBlock, 0, stream>>>(rows, a.dist_clip, q);
     } else {
         const int64_t hw = s.sel - s.hist;
-        spf_regr3d_zero_kernel<<<regr_grid((hw + kBlock - 1) / kBlock), kBlock, 0, stream>>>(w + s.hist, hw);
+        spf_regr3d_zero_kernel<<<slot_grid((hw + kBlock - 1) / kBlock), kBlock, 0, stream>>>(w + s.hist, hw);
         regr_select_pass<0>(a, nchunk, w + s.hist, w + s.sel, q, stream);
         regr_select_pass<1>(a, nchunk, w + s.hist, w + s.sel, q, stream);
         regr_select_pass<2>(a, nchunk, w + s.hist, w + s.sel, q, stream);
     }
     const int64_t nslots = (int64_t)rows * nchunk;
-    spf_regr3d_mask_kernel<<<regr_grid(nslots), kBlock, 0, stream>>>(a, nchunk, nslots, q, w + s.pcnt, f + s.ppr,
+    spf_regr3d_mask_kernel<<<slot_grid(nslots), kBlock, 0, stream>>>(a, nchunk, nslots, q, w + s.pcnt, f + s.ppr,
                                                                      f + s.pgt);
     spf_regr3d_norm_kernel<<<a.B, kBlock, 0, stream>>>(a.B, nchunk, a.normalize, a.gt_scale, w + s.pcnt, f + s.ppr,
                                                        f + s.pgt, stats);
-    spf_regr3d_loss_kernel<<<regr_grid(nslots), kBlock, 0, stream>>>(a, nchunk, nslots, stats, f + s.ploss, f + s.pdot);
+    spf_regr3d_loss_kernel<<<slot_grid(nslots), kBlock, 0, stream>>>(a, nchunk, nslots, stats, f + s.ploss, f + s.pdot);
     spf_regr3d_final_kernel<<<a.B + 1, kBlock, 0, stream>>>(a.B, nchunk, a.disable_view1, stats, f + s.ploss, f + s.pdot,
                                                             f + s.T, f + s.scale, loss);
     return hipGetLastError();
@@ -540,7 +482,7 @@ hipError_t launch_regr3d_bwd(const SpfRegr3d& a, const void* scratch, const floa
     const float* f = static_cast<const float*>(scratch);
     const int v_first = d_pr1 ? 0 : 1, n_views = (d_pr1 ? 1 : 0) + (d_pr2 ? 1 : 0);
     const int64_t nslots = (int64_t)n_views * a.B * nchunk;
-    spf_regr3d_bwd_kernel<<<regr_grid(nslots), kBlock, 0, stream>>>(a, nchunk, nslots, v_first, stats, f + s.T,
+    spf_regr3d_bwd_kernel<<<slot_grid(nslots), kBlock, 0, stream>>>(a, nchunk, nslots, v_first, stats, f + s.T,
                                                                     f + s.scale, dL_dloss, d_pr1, d_pr2);
     return hipGetLastError();
 }

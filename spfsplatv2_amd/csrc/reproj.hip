@@ -14,12 +14,10 @@
 //                             dL/dposes and scaled back to dL/dintrinsics
 // No atomics; a slot's content depends on the image and the chunk only, so a view's sums are formed in the same order
 // whether it comes alone or in a batch: the batched call equals the per-view loop bitwise.
-#include "spf_common.h"
+#include "point_slots.h"
 
 namespace spf {
 
-constexpr int kReprojChunk = 4 * kBlock;   // points per slot: four per lane (three 16-byte loads)
-constexpr int kReprojMaxGrid = 2048;       // memory-bound: a few blocks per CU, grid-stride over the slots
 constexpr int kReprojCam = 21;             // W rows 0-2 (3x4, world -> camera) then K' (3x3, pixel units)
 constexpr int kReprojGrad = 24;            // floats per backward partial: dW[12], dK'[9], padding
 
@@ -86,25 +84,6 @@ __device__ __forceinline__ float reproj_dterm(float e, float lw, float soft) {
     return e > soft ? soft / (1.f + soft * e) : 1.f;
 }
 
-// Four points of a slot (lane-owned: points p0 .. p0 + 3 of the image): three 16-byte loads when the image's base is
-// 16-byte aligned and all four exist, scalar loads otherwise.
-__device__ __forceinline__ void reproj_load4(const float* __restrict__ img, bool aligned, int p0, int n, float (&v)[12]) {
-    if (aligned && p0 + 3 < n) {
-        const float4* p4 = reinterpret_cast<const float4*>(img + 3 * (int64_t)p0);
-        const float4 a = p4[0], b = p4[1], c = p4[2];
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-        v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-        v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const bool in = p0 + k < n;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[3 * k + c] = in ? img[3 * (int64_t)(p0 + k) + c] : 0.f;
-        }
-    }
-}
-
 __device__ __forceinline__ const float* reproj_image(const SpfReproj& a, int img) {
     const int b = img / a.V, v = img - b * a.V;
     return a.pts3d + (int64_t)b * a.stride_b + (int64_t)v * a.stride_v;
@@ -114,23 +93,22 @@ template <int MODE>
 __global__ __launch_bounds__(kBlock) void spf_reproj_fwd_kernel(SpfReproj a, int nchunk, int64_t nslots,
                                                                 float* __restrict__ psum, uint32_t* __restrict__ pcnt) {
     __shared__ float s_cam[kReprojCam];
-    __shared__ float s_w[kBlock / kWave];
-    __shared__ uint32_t s_n[kBlock / kWave];
+    __shared__ SumRow<2> s_sum;
     const int n = a.H * a.W;
     for (int64_t slot = blockIdx.x; slot < nslots; slot += gridDim.x) {
         const int img = (int)(slot / nchunk), chunk = (int)(slot - (int64_t)img * nchunk);
-        __syncthreads();                                  // the previous slot's readers of s_cam / s_w are done
+        __syncthreads();                                  // the previous slot's readers of s_cam are done
         if (threadIdx.x == 0) reproj_camera(a, img, s_cam);
         __syncthreads();
         float cam[kReprojCam];
 #pragma unroll
         for (int i = 0; i < kReprojCam; ++i) cam[i] = s_cam[i];
         const float* base = reproj_image(a, img);
-        const int p0 = chunk * kReprojChunk + 4 * threadIdx.x;
+        const int p0 = chunk * kSlotPoints + 4 * threadIdx.x;
         float v[12];
-        reproj_load4(base, (reinterpret_cast<uintptr_t>(base) & 15) == 0, p0, n, v);
-        float acc = 0.f;
-        uint32_t cnt = 0;
+        load4_xyz(base, aligned16(base), p0, n, v);
+        float acc[1] = {0.f};
+        uint32_t cnt[1] = {0u};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int p = p0 + k;
@@ -138,20 +116,14 @@ __global__ __launch_bounds__(kBlock) void spf_reproj_fwd_kernel(SpfReproj a, int
                 const int i = p / a.W, j = p - i * a.W;
                 const ReprojPt r = reproj_point(cam, v[3 * k], v[3 * k + 1], v[3 * k + 2], (float)j, (float)i);
                 const bool valid = !(r.e > a.hard_clamp);         // NaN counts as valid (and propagates)
-                acc += valid ? reproj_term<MODE>(r.e, a.lw, a.soft_clamp) : 0.f;
-                cnt += valid ? 1u : 0u;
+                acc[0] += valid ? reproj_term<MODE>(r.e, a.lw, a.soft_clamp) : 0.f;
+                cnt[0] += valid ? 1u : 0u;
             }
         }
-        const float ws = wave_sum(acc);
-        const uint32_t wn = wave_sum_u32(cnt);
-        if ((threadIdx.x & (kWave - 1)) == 0) {
-            s_w[threadIdx.x >> 6] = ws;
-            s_n[threadIdx.x >> 6] = wn;
-        }
-        __syncthreads();
+        block_sum(acc, cnt, s_sum);
         if (threadIdx.x == 0) {
-            psum[slot] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
-            pcnt[slot] = (s_n[0] + s_n[1]) + (s_n[2] + s_n[3]);
+            psum[slot] = acc[0];
+            pcnt[slot] = cnt[0];
         }
     }
 }
@@ -163,28 +135,21 @@ __global__ __launch_bounds__(kBlock) void spf_reproj_reduce_kernel(const float* 
                                                                    const uint32_t* __restrict__ pcnt, int B, int V,
                                                                    int nchunk, float weight, float lw_mul,
                                                                    float* __restrict__ loss, float* __restrict__ scale) {
-    __shared__ float s_w[kBlock / kWave];
-    __shared__ uint32_t s_n[kBlock / kWave];
+    __shared__ SumRow<2> s_sum;
     const int v = blockIdx.x;
     const int64_t m = (int64_t)B * nchunk;
-    float acc = 0.f;
-    uint32_t cnt = 0;
+    float acc[1] = {0.f};
+    uint32_t cnt[1] = {0u};
     for (int64_t k = threadIdx.x; k < m; k += kBlock) {
         const int64_t b = k / nchunk, c = k - b * nchunk;
         const int64_t slot = (b * V + v) * nchunk + c;
-        acc += psum[slot];
-        cnt += pcnt[slot];
+        acc[0] += psum[slot];
+        cnt[0] += pcnt[slot];
     }
-    const float ws = wave_sum(acc);
-    const uint32_t wn = wave_sum_u32(cnt);
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        s_w[threadIdx.x >> 6] = ws;
-        s_n[threadIdx.x >> 6] = wn;
-    }
-    __syncthreads();
+    block_sum(acc, cnt, s_sum);
     if (threadIdx.x == 0) {
-        const float tot = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
-        const uint32_t nv = (s_n[0] + s_n[1]) + (s_n[2] + s_n[3]);
+        const float tot = acc[0];
+        const uint32_t nv = cnt[0];
         loss[v] = nv ? (weight * (lw_mul * tot)) / (float)nv : 0.f;
         scale[v] = nv ? weight / (float)nv : 0.f;
     }
@@ -197,11 +162,11 @@ __global__ __launch_bounds__(kBlock) void spf_reproj_bwd_kernel(SpfReproj a, int
                                                                 const float* __restrict__ dL_dloss,
                                                                 float* __restrict__ dpts, float* __restrict__ gpartial) {
     __shared__ float s_cam[kReprojCam];
-    __shared__ float s_g[kBlock / kWave][kReprojGrad];
+    __shared__ SumRow<kReprojGrad> s_g;
     const int n = a.H * a.W;
     for (int64_t slot = blockIdx.x; slot < nslots; slot += gridDim.x) {
         const int img = (int)(slot / nchunk), chunk = (int)(slot - (int64_t)img * nchunk);
-        __syncthreads();
+        __syncthreads();                                  // the previous slot's readers of s_cam are done
         if (threadIdx.x == 0) reproj_camera(a, img, s_cam);
         __syncthreads();
         float cam[kReprojCam];
@@ -210,9 +175,9 @@ __global__ __launch_bounds__(kBlock) void spf_reproj_bwd_kernel(SpfReproj a, int
         const int view = img % a.V;
         const float gs = dL_dloss[view] * scale[view];           // upstream gradient read on the device: no sync
         const float* base = reproj_image(a, img);
-        const int p0 = chunk * kReprojChunk + 4 * threadIdx.x;
+        const int p0 = chunk * kSlotPoints + 4 * threadIdx.x;
         float v[12], o[12];
-        reproj_load4(base, (reinterpret_cast<uintptr_t>(base) & 15) == 0, p0, n, v);
+        load4_xyz(base, aligned16(base), p0, n, v);
         float g[kReprojGrad];
 #pragma unroll
         for (int k = 0; k < kReprojGrad; ++k) g[k] = 0.f;
@@ -255,19 +220,7 @@ __global__ __launch_bounds__(kBlock) void spf_reproj_bwd_kernel(SpfReproj a, int
         }
         if (GPTS) {
             float* out = dpts + (int64_t)img * n * 3;
-            if ((reinterpret_cast<uintptr_t>(out) & 15) == 0 && p0 + 3 < n) {
-                float4* o4 = reinterpret_cast<float4*>(out + 3 * (int64_t)p0);
-                o4[0] = make_float4(o[0], o[1], o[2], o[3]);
-                o4[1] = make_float4(o[4], o[5], o[6], o[7]);
-                o4[2] = make_float4(o[8], o[9], o[10], o[11]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (p0 + k < n) {
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) out[3 * (int64_t)(p0 + k) + c] = o[3 * k + c];
-                    }
-            }
+            store4_xyz(out, aligned16(out), p0, n, o);
         }
         if (GCAM) {
             float lo[12], hi[12], slo[3], shi[3];
@@ -278,19 +231,18 @@ __global__ __launch_bounds__(kBlock) void spf_reproj_bwd_kernel(SpfReproj a, int
             }
             wave_sum12(lo, slo);
             wave_sum12(hi, shi);
+            // the row filled from wave_sum12's lane layout, with block_sum's two barriers (point_slots.h)
             const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+            __syncthreads();                              // the previous slot's readers of s_g are done
             if (lane < 4) {
 #pragma unroll
                 for (int jj = 0; jj < 3; ++jj) {
-                    s_g[wave][4 * jj + lane] = slo[jj];
-                    s_g[wave][12 + 4 * jj + lane] = shi[jj];
+                    s_g.w[wave][4 * jj + lane] = __float_as_uint(slo[jj]);
+                    s_g.w[wave][12 + 4 * jj + lane] = __float_as_uint(shi[jj]);
                 }
             }
             __syncthreads();
-            if (threadIdx.x < kReprojGrad) {
-                const int t = threadIdx.x;
-                gpartial[slot * kReprojGrad + t] = (s_g[0][t] + s_g[1][t]) + (s_g[2][t] + s_g[3][t]);
-            }
+            if (threadIdx.x < kReprojGrad) gpartial[slot * kReprojGrad + threadIdx.x] = sum_row_f32(s_g, threadIdx.x);
         }
     }
 }
@@ -300,8 +252,8 @@ __global__ __launch_bounds__(kBlock) void spf_reproj_bwd_kernel(SpfReproj a, int
 __global__ __launch_bounds__(kBlock) void spf_reproj_cam_kernel(SpfReproj a, int nchunk,
                                                                 const float* __restrict__ gpartial,
                                                                 float* __restrict__ dposes, float* __restrict__ dintr) {
-    __shared__ float s_w[kBlock / kWave][kReprojGrad];
-    const int img = blockIdx.x, lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    __shared__ SumRow<kReprojGrad> s_sum;
+    const int img = blockIdx.x;
     float acc[kReprojGrad];
 #pragma unroll
     for (int k = 0; k < kReprojGrad; ++k) acc[k] = 0.f;
@@ -313,17 +265,11 @@ __global__ __launch_bounds__(kBlock) void spf_reproj_cam_kernel(SpfReproj a, int
             acc[4 * q] += x.x; acc[4 * q + 1] += x.y; acc[4 * q + 2] += x.z; acc[4 * q + 3] += x.w;
         }
     }
-#pragma unroll
-    for (int k = 0; k < kReprojGrad; ++k) acc[k] = wave_sum(acc[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < kReprojGrad; ++k) s_w[wave][k] = acc[k];
-    }
-    __syncthreads();
+    block_sum(acc, s_sum);
     if (threadIdx.x != 0) return;
     double tot[21];
 #pragma unroll
-    for (int k = 0; k < 21; ++k) tot[k] = (double)((s_w[0][k] + s_w[1][k]) + (s_w[2][k] + s_w[3][k]));
+    for (int k = 0; k < 21; ++k) tot[k] = (double)acc[k];
     if (dposes) {
         double P[16], Wd[16], T1[16];
 #pragma unroll
@@ -362,17 +308,15 @@ __global__ __launch_bounds__(kBlock) void spf_reproj_cam_kernel(SpfReproj a, int
 
 int64_t reproj_slots(int B, int V, int H, int W, int* nchunk) {
     const int64_t n = (int64_t)H * W;
-    const int64_t nc = (n + kReprojChunk - 1) / kReprojChunk;
+    const int64_t nc = slot_chunks(n);
     if (nchunk) *nchunk = (int)nc;
     return (int64_t)B * V * nc;
 }
 
-static int reproj_grid(int64_t nslots) { return (int)(nslots < kReprojMaxGrid ? nslots : kReprojMaxGrid); }
-
 template <int MODE>
 static void reproj_fwd_launch(const SpfReproj& a, int nchunk, int64_t nslots, float* psum, uint32_t* pcnt,
                               hipStream_t stream) {
-    spf_reproj_fwd_kernel<MODE><<<reproj_grid(nslots), kBlock, 0, stream>>>(a, nchunk, nslots, psum, pcnt);
+    spf_reproj_fwd_kernel<MODE><<<slot_grid(nslots), kBlock, 0, stream>>>(a, nchunk, nslots, psum, pcnt);
 }
 
 hipError_t launch_reproj_fwd(const SpfReproj& a, void* partial, float* loss, float* scale, hipStream_t stream) {
@@ -394,7 +338,7 @@ hipError_t launch_reproj_fwd(const SpfReproj& a, void* partial, float* loss, flo
 template <int MODE>
 static void reproj_bwd_launch(const SpfReproj& a, int nchunk, int64_t nslots, const float* scale, const float* dL_dloss,
                               float* dpts, float* gpartial, hipStream_t stream) {
-    const int grid = reproj_grid(nslots);
+    const int grid = slot_grid(nslots);
     if (dpts && gpartial)
         spf_reproj_bwd_kernel<MODE, true, true><<<grid, kBlock, 0, stream>>>(a, nchunk, nslots, scale, dL_dloss, dpts,
                                                                               gpartial);

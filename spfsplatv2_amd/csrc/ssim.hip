@@ -27,11 +27,10 @@
 // LDS access: in every pass consecutive lanes take consecutive columns of one row (the column index is the fast one),
 // so the row pass reads and the column pass reads are both stride-1 across a wave: conflict-free (MI355X: 64 banks of
 // 4 bytes, ds_read_b32 serviced in two 32-lane groups).
-#include "spf_common.h"
+#include "point_slots.h"
 
 namespace spf {
 
-constexpr int kSsimMaxGrid = 2048;         // a few blocks per CU; grid-stride over the slots
 constexpr int kSsimHead = 40;              // floats ahead of the tiles in LDS: the window (33) and the four wave sums
 constexpr size_t kLdsDefault = 64 * 1024;  // dynamic LDS a kernel gets without asking
 constexpr size_t kLdsMax = 152 * 1024;     // what one workgroup may ask for (160 KiB per CU on gfx950)
@@ -230,14 +229,6 @@ __device__ __forceinline__ void ssim_col_moments_rows(const float* __restrict__ 
     }
 }
 
-// Sum over the block, valid in thread 0 (fixed order: lanes by the DPP ladder, then the four waves).
-__device__ __forceinline__ float ssim_block_sum(float v, float* __restrict__ s_w) {
-    const float w = wave_sum(v);
-    if ((threadIdx.x & (kWave - 1)) == 0) s_w[threadIdx.x >> 6] = w;
-    __syncthreads();
-    return (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
-}
-
 template <int WS>
 __global__ __launch_bounds__(kBlock) void spf_ssim_fwd_kernel(SpfSsim a, int TX, int TY, int ntx, int nty,
                                                               int64_t nslots, float* __restrict__ partial) {
@@ -245,7 +236,7 @@ __global__ __launch_bounds__(kBlock) void spf_ssim_fwd_kernel(SpfSsim a, int TX,
     const int ws = WS ? WS : a.ws, h = ws - 1;
     const int RI = TY + h, CI = TX + h, Hv = a.H - h, Wv = a.W - h;
     float* s_win = s_mem;
-    float* s_w = s_mem + 36;
+    SumRow<1>& s_sum = *reinterpret_cast<SumRow<1>*>(s_mem + 36);
     float* s_x = s_mem + kSsimHead;
     float* s_y = s_x + RI * CI;
     float* s_m = s_y + RI * CI;
@@ -292,17 +283,8 @@ __global__ __launch_bounds__(kBlock) void spf_ssim_fwd_kernel(SpfSsim a, int TX,
                 }
             }
         }
-        const float tot = ssim_block_sum(acc, s_w);
+        const float tot = block_sum(acc, s_sum);
         if (threadIdx.x == 0) partial[slot] = tot;
-    }
-}
-
-// Sum of s_d[0 .. kBlock) in a fixed tree; the result is in s_d[0] after the call.
-__device__ __forceinline__ void ssim_tree_sum(double* __restrict__ s_d) {
-    __syncthreads();
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) s_d[threadIdx.x] += s_d[threadIdx.x + s];
-        __syncthreads();
     }
 }
 
@@ -312,9 +294,8 @@ __global__ __launch_bounds__(kBlock) void spf_ssim_plane_kernel(const float* __r
     const float* __restrict__ p = partial + (int64_t)blockIdx.x * ntiles;
     double acc = 0.0;
     for (int t = threadIdx.x; t < ntiles; t += kBlock) acc += (double)p[t];
-    s_d[threadIdx.x] = acc;
-    ssim_tree_sum(s_d);
-    if (threadIdx.x == 0) plane_mean[blockIdx.x] = (float)(s_d[0] * inv_valid);
+    const double tot = block_tree_sum<kBlock>(acc, s_d);
+    if (threadIdx.x == 0) plane_mean[blockIdx.x] = (float)(tot * inv_valid);
 }
 
 // relu(NaN) stays NaN, as torch.relu
@@ -335,9 +316,8 @@ __global__ __launch_bounds__(kBlock) void spf_ssim_finalize_kernel(const float* 
     const int64_t np = (int64_t)N * C;
     double acc = 0.0;
     for (int64_t i = threadIdx.x; i < np; i += kBlock) acc += (double)ssim_relu(plane_mean[i], nonneg);
-    s_d[threadIdx.x] = acc;
-    ssim_tree_sum(s_d);
-    if (threadIdx.x == 0) out[0] = (float)(s_d[0] / (double)np);
+    const double tot = block_tree_sum<kBlock>(acc, s_d);
+    if (threadIdx.x == 0) out[0] = (float)(tot / (double)np);
 }
 
 // Derivative maps in LDS: [b, c, aX (GX), aY (GY)].
@@ -470,12 +450,9 @@ __global__ __launch_bounds__(kBlock) void spf_psnr_kernel(const float* __restric
         const float d = psnr_clip(g[i]) - psnr_clip(p[i]);
         acc += (double)(d * d);
     }
-    s_d[threadIdx.x] = acc;
-    ssim_tree_sum(s_d);
-    if (threadIdx.x == 0) psnr[blockIdx.x] = -10.f * log10f((float)(s_d[0] / (double)n));
+    const double tot = block_tree_sum<kBlock>(acc, s_d);
+    if (threadIdx.x == 0) psnr[blockIdx.x] = -10.f * log10f((float)(tot / (double)n));
 }
-
-static int ssim_grid(int64_t nslots) { return (int)(nslots < kSsimMaxGrid ? nslots : kSsimMaxGrid); }
 
 template <typename K>
 static hipError_t ssim_allow_lds(K kernel, size_t lds) {
@@ -489,9 +466,9 @@ hipError_t launch_ssim_fwd(const SpfSsim& a, float* partial, float* plane_mean, 
     const int ntiles = t.ntx * t.nty;
     const int64_t nslots = (int64_t)a.N * a.C * ntiles;
     if (a.ws == 11)
-        spf_ssim_fwd_kernel<11><<<ssim_grid(nslots), kBlock, t.lds, stream>>>(a, t.tx, t.ty, t.ntx, t.nty, nslots, partial);
+        spf_ssim_fwd_kernel<11><<<slot_grid(nslots), kBlock, t.lds, stream>>>(a, t.tx, t.ty, t.ntx, t.nty, nslots, partial);
     else
-        spf_ssim_fwd_kernel<0><<<ssim_grid(nslots), kBlock, t.lds, stream>>>(a, t.tx, t.ty, t.ntx, t.nty, nslots, partial);
+        spf_ssim_fwd_kernel<0><<<slot_grid(nslots), kBlock, t.lds, stream>>>(a, t.tx, t.ty, t.ntx, t.nty, nslots, partial);
     const double inv_valid = 1.0 / ((double)(a.H - a.ws + 1) * (double)(a.W - a.ws + 1));
     spf_ssim_plane_kernel<<<a.N * a.C, kBlock, 0, stream>>>(partial, ntiles, inv_valid, plane_mean);
     spf_ssim_finalize_kernel<<<1, kBlock, 0, stream>>>(plane_mean, a.N, a.C, a.size_average, a.nonnegative, out);
@@ -504,7 +481,7 @@ static hipError_t ssim_bwd_launch(const SpfSsim& a, const float* plane_mean, con
     const SsimTiling t = ssim_bwd_tiling(a.H, a.W, a.ws, 2 + (GX ? 1 : 0) + (GY ? 1 : 0));
     const int64_t nslots = (int64_t)a.N * a.C * t.ntx * t.nty;
     if (hipError_t e = ssim_allow_lds(spf_ssim_bwd_kernel<WS, GX, GY>, t.lds)) return e;
-    spf_ssim_bwd_kernel<WS, GX, GY><<<ssim_grid(nslots), kBlock, t.lds, stream>>>(a, t.tx, t.ty, t.ntx, t.nty, nslots,
+    spf_ssim_bwd_kernel<WS, GX, GY><<<slot_grid(nslots), kBlock, t.lds, stream>>>(a, t.tx, t.ty, t.ntx, t.nty, nslots,
                                                                                  plane_mean, dL_dout, dX, dY);
     return hipGetLastError();
 }

@@ -175,7 +175,7 @@ def _hold_depth(case, got, yard, truth):
     hold(case + "/d_poses", got[2], yard[2], truth[2], GRAD)
 
 
-@pytest.mark.parametrize("shape", [(2, 768), (3, 1551), (1, 65536)])
+@pytest.mark.parametrize("shape", [(2, 768), (2, 1026), (3, 1551), (1, 65536)])
 def test_depth_matches_the_oracle_and_a_strided_misaligned_view(hip_lib, shape):
     N, n = shape
     gen = torch.Generator().manual_seed(N * 7 + n)

@@ -248,9 +248,9 @@ def test_hip_matches_reference_goldens(hip_lib, name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape", [(2, 17, 13), (3, 64, 64), (2, 96, 112), (2, 256, 256)])
+@pytest.mark.parametrize("shape", [(2, 17, 13), (2, 27, 38), (3, 64, 64), (2, 96, 112), (2, 256, 256)])
 def test_hip_matches_oracle(hip_lib, shape):
-    """(2,96,112): 10,752 points, not a power of two, 11 slots and two histogram segments per row; (2,256,256): 64 slots
+    """(2,27,38): 1,026 points, a full slot and a second slot that holds two points; (2,96,112): 10,752 points, not a power of two, 11 slots and two histogram segments per row; (2,256,256): 64 slots
     and eight segments per row, thresholds deep inside the float32 pattern (all three digit passes decide)."""
     case, ref = _decided_case(*shape)
     assert go.decided(case)

@@ -17,7 +17,8 @@ from tests import reproj_oracle as ro
 
 GOLD = torch.load(Path(__file__).parent / "golden" / "reproj_goldens.pt")
 # (b33_grid_stride: 33 x 64 = 2,112 slots, more than the 2,048-block grid -- blocks loop over several slots)
-SHAPES = {"re10k": (16, 2, 256, 256), "re10k_10view": (3, 10, 256, 256), "b33_grid_stride": (33, 1, 256, 256)}
+SHAPES = {"re10k": (16, 2, 256, 256), "re10k_10view": (3, 10, 256, 256), "b33_grid_stride": (33, 1, 256, 256),
+          "slot_plus_2": (2, 2, 27, 38)}     # 1026 points: a full slot, then a slot that holds two points
 
 
 def _rel(a, b):
@@ -235,7 +236,8 @@ def _batched(pts, poses, ks, mode="dyntanh", step=30_000, **kw):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape,mode", [("re10k", "dyntanh"), ("re10k", "l1+sqrt"), ("re10k_10view", "dyntanh"),
-                                        ("re10k_10view", "l1+sqrt"), ("b33_grid_stride", "dyntanh")])
+                                        ("re10k_10view", "l1+sqrt"), ("b33_grid_stride", "dyntanh"),
+                                        ("slot_plus_2", "dyntanh")])
 def test_hip_matches_oracle_at_full_shape(hip_lib, shape, mode):
     b, v, h, w = SHAPES[shape]
     pts, poses, ks = _pixel_aligned_5d(5, b, v, h, w)
