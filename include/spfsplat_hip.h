@@ -41,6 +41,9 @@
  *   spf_pose_error          compute_pose_error (src/evaluation/metrics.py:70-99) for N pairs, with the three means.
  *   spf_focal_*             estimate_focal_knowing_depth 'weiszfeld' and estimate_intrinsics
  *                           (src/misc/intrinsics_utils.py:33-108,162-174), one focal per scene.
+ *   spf_optim_*             ModelWrapper.optimizer_step (src/model/model_wrapper.py:1113-1151): the NaN / large-gradient
+ *                           guard, clip_grad_norm_(parameters, 0.5) and the torch.optim.AdamW step that
+ *                           configure_optimizers (:1067-1111) sets up, for the whole parameter set at once.
  *
  * Return value of every int function: 0 = success, otherwise a negative SPF_E_* code;
  * spf_last_error() returns a host string describing the most recent failure on this thread.
@@ -63,7 +66,9 @@ extern "C" {
                               mask / q-k-LayerNorm extras (SpfAttnExt, spf_attn_forward_ext, spf_attn_backward_ext,
                               spf_attn_ext_scratch_floats) and its multi-view family (SpfAttnViews,
                               spf_attn_views_forward, spf_attn_views_backward) and the opt-in 16-bit matrix path of
-                              the plain call (spf_attn16_forward, spf_attn16_backward) */
+                              the plain call (spf_attn16_forward, spf_attn16_backward) and the guarded AdamW step
+                              (SpfOptimTensor, SpfOptimGroup, SpfOptimHyper, SpfOptimReport, SpfOptim, spf_optim_chunks,
+                              spf_optim_plan, spf_optim_scratch_bytes, spf_optim_step): four entry points added */
 
 #define SPF_OK 0
 #define SPF_E_INVALID (-1)   /* bad argument (null pointer, size, unsupported degree ...) */
@@ -778,6 +783,66 @@ int spf_attn_views_forward(const SpfAttn* args, const SpfAttnViews* views, void*
  * atomics: every dq, dk, dv row is written once, in a fixed order of sums -- bitwise reproducible. */
 int spf_attn_views_backward(const SpfAttn* args, const SpfAttnViews* views, const SpfAttnGrads* grads, const void* out,
                             const float* lse, const void* dout, void* stream);
+
+/* ---- the guarded AdamW step (spfsplatv2_amd/csrc/optim.hip) --------------------------------------------------------
+ * One call steps a whole parameter set: T float32 tensors of any sizes.  Three launches on the given stream and no
+ * host synchronisation: (A) per-chunk gradient statistics, (B) the verdict -- the reference's walk over the tensors
+ * (NaN before maximum, a maximum strictly above the threshold is "large", the first offender ends the walk), the total
+ * norm and the clip coefficient of clip_grad_norm_, and every present tensor's step counter and bias corrections --,
+ * (C) the AdamW update, which every block leaves after one read when the verdict is "skipped". */
+#define SPF_OPTIM_CHUNK 4096      /* floats per chunk: every tensor is cut into chunks of this size, the last one partial */
+#define SPF_OPTIM_MAX_GROUPS 8
+typedef struct SpfOptimTensor {   /* one entry of the static table */
+    float* param;
+    float* exp_avg;
+    float* exp_avg_sq;            /* numel floats each, 4-byte aligned (16-byte aligned bases take the vector path) */
+    int64_t numel;
+    int32_t group;                /* index into SpfOptimHyper.group */
+    int32_t reserved;
+} SpfOptimTensor;
+typedef struct SpfOptimGroup {
+    double lr, beta1, beta2, eps, weight_decay;
+} SpfOptimGroup;
+typedef struct SpfOptimHyper {    /* by value, every step: a scheduler changes lr without any copy */
+    int32_t num_groups;           /* 1 .. SPF_OPTIM_MAX_GROUPS */
+    int32_t guard;                /* 0: no NaN / large-gradient guard (non-finite gradients flow through, as in torch) */
+    int32_t clip;                 /* 0: no clip (clip_coef = 1) */
+    int32_t reserved;
+    double max_grad_value;        /* guard threshold, compared as float32: max |g| > threshold is large */
+    double max_norm;              /* clip_coef = min(1, max_norm / (total_norm + 1e-6)) */
+    SpfOptimGroup group[SPF_OPTIM_MAX_GROUPS];
+} SpfOptimHyper;
+typedef struct SpfOptimReport {   /* 32 bytes on the device, written by every step */
+    int32_t skipped, nan_detected, large_detected;
+    int32_t offender;             /* position in the guard order, -1 if none */
+    float max_gradient;           /* over the positions up to and including a large offender, excluding a NaN one */
+    float total_norm;             /* sqrt of the sum of squares of all present gradients */
+    float clip_coef;
+    float clip_coef_lo;           /* the coefficient minus its float32 value: pass C multiplies by both parts */
+} SpfOptimReport;
+typedef struct SpfOptim {
+    const SpfOptimTensor* table;  /* T entries */
+    const int64_t* chunk_start;   /* T + 1: first chunk of every tensor, and the total (spf_optim_plan fills a host copy) */
+    const uint64_t* grads;        /* T gradient addresses of this step, 0 = the tensor has no gradient */
+    const int32_t* guard_order;   /* T: the tensor at every position of the guard's walk (a permutation of 0 .. T-1) */
+    int32_t* step;                /* T step counters, the caller's persistent state; incremented for present tensors */
+    void* scratch;                /* spf_optim_scratch_bytes(T, chunks) bytes, 16-byte aligned */
+    void* report;                 /* one SpfOptimReport, 16-byte aligned */
+    int32_t T, reserved;
+    int64_t chunks;               /* chunk_start[T] */
+} SpfOptim;
+/* host only: chunks of one set, sum of ceil(numel[t] / SPF_OPTIM_CHUNK); -1 (SPF_E_INVALID) on a null array, T <= 0 or a
+ * numel <= 0 */
+int64_t spf_optim_chunks(const int64_t* numel /* host */, int32_t T);
+/* host only: checks a HOST copy of the table (null table or pointer, T <= 0, numel <= 0, num_groups outside
+ * 1 .. SPF_OPTIM_MAX_GROUPS, a group index out of range) and fills chunk_start[0 .. T] (host, may be null); returns the
+ * number of chunks or SPF_E_INVALID */
+int64_t spf_optim_plan(const SpfOptimTensor* table /* host */, int32_t T, int32_t num_groups,
+                       int64_t* chunk_start /* host, T + 1 */);
+int64_t spf_optim_scratch_bytes(int32_t T, int64_t chunks);
+/* the three launches (pass A is left out when neither guard nor clip is set).  Argument errors return SPF_E_INVALID
+ * before anything is launched; nothing is allocated or synchronised; no float atomics: bitwise repeatable. */
+int spf_optim_step(const SpfOptim* args, const SpfOptimHyper* hyper, void* stream);
 
 /* Per-stage device timing with HIP events recorded on the launch stream around every kernel
  * stage.  spf_stage_timing_enable(mask) clears the log and starts recording the stages whose bit

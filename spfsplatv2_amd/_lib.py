@@ -108,6 +108,29 @@ class SpfAttnViews(C.Structure):
                 ("dv_view_stride", C.c_int64)]
 
 
+OPTIM_CHUNK = 4096
+OPTIM_MAX_GROUPS = 8
+
+
+class SpfOptimTensor(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("numel", C.c_int64),
+                ("group", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SpfOptimGroup(C.Structure):
+    _fields_ = [(f, C.c_double) for f in ("lr", "beta1", "beta2", "eps", "weight_decay")]
+
+
+class SpfOptimHyper(C.Structure):
+    _fields_ = [("num_groups", C.c_int32), ("guard", C.c_int32), ("clip", C.c_int32), ("reserved", C.c_int32),
+                ("max_grad_value", C.c_double), ("max_norm", C.c_double), ("group", SpfOptimGroup * OPTIM_MAX_GROUPS)]
+
+
+class SpfOptim(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in ("table", "chunk_start", "grads", "guard_order", "step", "scratch",
+                                          "report")] + [("T", C.c_int32), ("reserved", C.c_int32), ("chunks", C.c_int64)]
+
+
 # Every symbol include/spfsplat_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "spf_abi_version": (C.c_int, []),
@@ -208,6 +231,10 @@ SYMBOLS = {
     "spf_attn_views_forward": (C.c_int, [C.POINTER(SpfAttn), C.POINTER(SpfAttnViews), C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_attn_views_backward": (C.c_int, [C.POINTER(SpfAttn), C.POINTER(SpfAttnViews), C.POINTER(SpfAttnGrads),
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_optim_chunks": (C.c_int64, [C.POINTER(C.c_int64), C.c_int32]),
+    "spf_optim_plan": (C.c_int64, [C.POINTER(SpfOptimTensor), C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "spf_optim_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
+    "spf_optim_step": (C.c_int, [C.POINTER(SpfOptim), C.POINTER(SpfOptimHyper), C.c_void_p]),
     "spf_stage_timing_enable": (C.c_int, [C.c_int32]),
     "spf_stage_timing_sample_every": (C.c_int, [C.c_int32]),
     "spf_stage_times_ms": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_int32)]),

@@ -81,6 +81,9 @@ hipError_t launch_attn_views_backward(const SpfAttn&, const SpfAttnViews&, const
                                       const void*, hipStream_t);
 hipError_t launch_rope2d(void*, void*, const int64_t*, int, int, int, int, int64_t, int64_t, int64_t, int, int, float,
                          float, hipStream_t);
+int64_t optim_chunks_of(int64_t);
+int64_t optim_scratch_bytes(int, int64_t);
+hipError_t launch_optim_step(const SpfOptim&, const SpfOptimHyper&, hipStream_t);
 }  // namespace spf
 
 namespace {
@@ -1319,6 +1322,66 @@ int spf_lpips_head_backward(const float* fa, const float* fb, const float* lin, 
     if (!fa || !fb || !lin || !up) return fail(SPF_E_INVALID, "lpips head: null pointer");
     if (!d_a && !d_b) return fail(SPF_E_INVALID, "lpips head: no gradient requested");
     SPF_HIP(spf::launch_lpips_head_bwd(fa, fb, lin, n, hw, c, up, 0, 0.f, d_a, d_b, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int64_t spf_optim_chunks(const int64_t* numel, int32_t T) {
+    if (!numel) return fail(SPF_E_INVALID, "optim: numel is null");
+    if (T <= 0) return fail(SPF_E_INVALID, "optim: T must be positive (got %d)", T);
+    int64_t chunks = 0;
+    for (int32_t t = 0; t < T; ++t) {
+        if (numel[t] <= 0) return fail(SPF_E_INVALID, "optim: tensor %d has numel %lld; it must be positive", t, (long long)numel[t]);
+        chunks += spf::optim_chunks_of(numel[t]);
+    }
+    return chunks;
+}
+
+int64_t spf_optim_plan(const SpfOptimTensor* table, int32_t T, int32_t num_groups, int64_t* chunk_start) {
+    if (!table) return fail(SPF_E_INVALID, "optim: table is null");
+    if (T <= 0) return fail(SPF_E_INVALID, "optim: T must be positive (got %d)", T);
+    if (num_groups < 1 || num_groups > SPF_OPTIM_MAX_GROUPS)
+        return fail(SPF_E_INVALID, "optim: %d parameter groups; 1 .. %d are supported", num_groups, SPF_OPTIM_MAX_GROUPS);
+    int64_t chunks = 0;
+    for (int32_t t = 0; t < T; ++t) {
+        const SpfOptimTensor& e = table[t];
+        if (!e.param || !e.exp_avg || !e.exp_avg_sq) return fail(SPF_E_INVALID, "optim: tensor %d has a null pointer", t);
+        if (((uintptr_t)e.param | (uintptr_t)e.exp_avg | (uintptr_t)e.exp_avg_sq) & 3)
+            return fail(SPF_E_INVALID, "optim: tensor %d is not 4-byte aligned", t);
+        if (e.numel <= 0) return fail(SPF_E_INVALID, "optim: tensor %d has numel %lld; it must be positive", t, (long long)e.numel);
+        if (e.group < 0 || e.group >= num_groups)
+            return fail(SPF_E_INVALID, "optim: tensor %d names group %d, out of range 0 .. %d", t, e.group, num_groups - 1);
+        if (chunk_start) chunk_start[t] = chunks;
+        chunks += spf::optim_chunks_of(e.numel);
+    }
+    if (chunk_start) chunk_start[T] = chunks;
+    return chunks;
+}
+
+int64_t spf_optim_scratch_bytes(int32_t T, int64_t chunks) {
+    if (T <= 0 || chunks < T) return fail(SPF_E_INVALID, "optim: T must be positive and chunks >= T (got %d, %lld)", T, (long long)chunks);
+    return spf::optim_scratch_bytes(T, chunks);
+}
+
+int spf_optim_step(const SpfOptim* o, const SpfOptimHyper* hp, void* stream_) {
+    if (!o || !hp) return fail(SPF_E_INVALID, "optim: args / hyper is null");
+    if (!o->table) return fail(SPF_E_INVALID, "optim: table is null");
+    if (o->T <= 0) return fail(SPF_E_INVALID, "optim: T must be positive (got %d)", o->T);
+    if (o->chunks < o->T) return fail(SPF_E_INVALID, "optim: chunks = %lld is below T = %d", (long long)o->chunks, o->T);
+    if (!o->chunk_start || !o->grads || !o->guard_order || !o->step || !o->scratch || !o->report)
+        return fail(SPF_E_INVALID, "optim: null pointer");
+    if (((uintptr_t)o->scratch | (uintptr_t)o->report) & 15)
+        return fail(SPF_E_INVALID, "optim: scratch and report must be 16-byte aligned");
+    if (hp->num_groups < 1 || hp->num_groups > SPF_OPTIM_MAX_GROUPS)
+        return fail(SPF_E_INVALID, "optim: %d parameter groups; 1 .. %d are supported", hp->num_groups, SPF_OPTIM_MAX_GROUPS);
+    if (hp->guard && !(hp->max_grad_value >= 0.0)) return fail(SPF_E_INVALID, "optim: max_grad_value must be >= 0");
+    if (hp->clip && !(hp->max_norm >= 0.0)) return fail(SPF_E_INVALID, "optim: max_norm must be >= 0");
+    for (int32_t i = 0; i < hp->num_groups; ++i) {
+        const SpfOptimGroup& g = hp->group[i];
+        if (!(g.lr >= 0.0) || !(g.eps >= 0.0) || !(g.weight_decay >= 0.0) || !(g.beta1 >= 0.0 && g.beta1 < 1.0) ||
+            !(g.beta2 >= 0.0 && g.beta2 < 1.0))
+            return fail(SPF_E_INVALID, "optim: group %d: lr, eps, weight_decay must be >= 0 and the betas in [0, 1)", i);
+    }
+    SPF_HIP(spf::launch_optim_step(*o, *hp, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
 
