@@ -844,6 +844,45 @@ int64_t spf_optim_scratch_bytes(int32_t T, int64_t chunks);
  * before anything is launched; nothing is allocated or synchronised; no float atomics: bitwise repeatable. */
 int spf_optim_step(const SpfOptim* args, const SpfOptimHyper* hyper, void* stream);
 
+/* ---- the transformer block's row work (spfsplatv2_amd/csrc/block.hip) ------------------------------------------------
+ * Residual add + LayerNorm and bias + exact GELU, forward and backward, float32 only, for rows of C floats with
+ * C % 4 == 0 and 4 <= C <= 4096 (SPF_BLOCK_MAX_C).  Every pointer is 16-byte aligned and every stride a multiple of 4
+ * floats (all accesses are 16-byte vectors).  Nothing is allocated or synchronised; no float atomics: the parameter
+ * gradients are summed per block into `partials` and then by a reducer in a fixed order, bitwise reproducible.
+ * Argument errors return SPF_E_INVALID (spf_last_error) before anything is launched. */
+#define SPF_BLOCK_MAX_C 4096
+typedef struct SpfBlockNorm {
+    const float* x;               /* rows of C floats; row i starts at (i / x_inner) * x_outer_stride + (i % x_inner) * x_stride */
+    const float* r;               /* optional second addend, addressed the same way through its own three numbers */
+    const float* gamma;           /* optional [C], legal only with r: s = x + gamma * r (without it s = x + r) */
+    const float* weight;          /* [C] */
+    const float* bias;            /* [C]; not read by the backward */
+    int64_t x_inner, x_stride, x_outer_stride;   /* x_inner >= 1 rows per outer group; a dense [rows, C]: rows, C, 0 */
+    int64_t r_inner, r_stride, r_outer_stride;
+    int64_t rows;                 /* 1 .. 2^30 */
+    int32_t C;
+    float eps;
+} SpfBlockNorm;
+/* host only: the number of blocks that write one row of partial column sums each, of the norm backward (gelu = 0) or
+ * of the GELU backward (gelu = 1) on `rows` rows of C floats; SPF_E_INVALID on sizes out of range */
+int64_t spf_block_partial_blocks(int64_t rows, int32_t C, int32_t gelu);
+/* s [rows, C] (written only with r; may be null without), y [rows, C], stats [rows, 4]: per row of s the mean as two
+ * floats (a float32 mean and the mean of the deviations about it, i.e. what float32 dropped), 1 / sqrt(var + eps) and a
+ * pad; the biased variance is taken from the deviations about that two-part mean, its sum in float64 */
+int spf_block_add_norm_forward(const SpfBlockNorm* args, float* s, float* y, float* stats, void* stream);
+/* args->x: the saved s (the forward's x where it had no r); args->r and gamma: given only where the forward had a
+ * gamma.  dy [rows, C]; ds [rows, C] or null; dx [rows, C] = ds + LN'(dy); dr [rows, C] = gamma * dx (only with gamma:
+ * without it dr IS dx and the pointer must be null).  partials: K * spf_block_partial_blocks(rows, C, 0) * C floats,
+ * dparams: [K, C] = dweight, dbias[, dgamma], K = 2 without gamma, 3 with. */
+int spf_block_add_norm_backward(const SpfBlockNorm* args, const float* dy, const float* ds, const float* stats, float* dx,
+                                float* dr, float* partials, float* dparams, void* stream);
+/* h = GELU(u + bias), erf form; u, h [rows, C] dense, bias [C] or null */
+int spf_block_bias_gelu_forward(const float* u, const float* bias, int64_t rows, int32_t C, float* h, void* stream);
+/* du = dh * GELU'(u + bias); with a bias, dbias [C] = the column sums of du through partials
+ * (spf_block_partial_blocks(rows, C, 1) * C floats); without, both must be null */
+int spf_block_bias_gelu_backward(const float* u, const float* bias, const float* dh, int64_t rows, int32_t C, float* du,
+                                 float* partials, float* dbias, void* stream);
+
 /* Per-stage device timing with HIP events recorded on the launch stream around every kernel
  * stage.  spf_stage_timing_enable(mask) clears the log and starts recording the stages whose bit
  * (1 << SPF_STAGE_x) is set in `mask` (0 = off, -1 = all) (up to

@@ -131,6 +131,15 @@ class SpfOptim(C.Structure):
                                           "report")] + [("T", C.c_int32), ("reserved", C.c_int32), ("chunks", C.c_int64)]
 
 
+BLOCK_MAX_C = 4096
+
+
+class SpfBlockNorm(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in ("x", "r", "gamma", "weight", "bias")] + \
+               [(f, C.c_int64) for f in ("x_inner", "x_stride", "x_outer_stride", "r_inner", "r_stride", "r_outer_stride",
+                                         "rows")] + [("C", C.c_int32), ("eps", C.c_float)]
+
+
 # Every symbol include/spfsplat_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "spf_abi_version": (C.c_int, []),
@@ -235,6 +244,13 @@ SYMBOLS = {
     "spf_optim_plan": (C.c_int64, [C.POINTER(SpfOptimTensor), C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "spf_optim_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
     "spf_optim_step": (C.c_int, [C.POINTER(SpfOptim), C.POINTER(SpfOptimHyper), C.c_void_p]),
+    "spf_block_partial_blocks": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "spf_block_add_norm_forward": (C.c_int, [C.POINTER(SpfBlockNorm), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_block_add_norm_backward": (C.c_int, [C.POINTER(SpfBlockNorm), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_block_bias_gelu_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "spf_block_bias_gelu_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_stage_timing_enable": (C.c_int, [C.c_int32]),
     "spf_stage_timing_sample_every": (C.c_int, [C.c_int32]),
     "spf_stage_times_ms": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_int32)]),

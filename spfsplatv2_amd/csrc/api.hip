@@ -84,6 +84,13 @@ hipError_t launch_rope2d(void*, void*, const int64_t*, int, int, int, int, int64
 int64_t optim_chunks_of(int64_t);
 int64_t optim_scratch_bytes(int, int64_t);
 hipError_t launch_optim_step(const SpfOptim&, const SpfOptimHyper&, hipStream_t);
+int64_t block_partial_blocks(int64_t, int, int);
+hipError_t launch_block_norm_fwd(const SpfBlockNorm&, float*, float*, float*, hipStream_t);
+hipError_t launch_block_norm_bwd(const SpfBlockNorm&, const float*, const float*, const float*, float*, float*, float*,
+                                 float*, hipStream_t);
+hipError_t launch_block_gelu_fwd(const float*, const float*, int64_t, int, float*, hipStream_t);
+hipError_t launch_block_gelu_bwd(const float*, const float*, const float*, int64_t, int, float*, float*, float*,
+                                 hipStream_t);
 }  // namespace spf
 
 namespace {
@@ -1382,6 +1389,83 @@ int spf_optim_step(const SpfOptim* o, const SpfOptimHyper* hp, void* stream_) {
             return fail(SPF_E_INVALID, "optim: group %d: lr, eps, weight_decay must be >= 0 and the betas in [0, 1)", i);
     }
     SPF_HIP(spf::launch_optim_step(*o, *hp, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+// ---- the transformer block's row work ----------------------------------------------------------------------------------
+static bool block_sizes_ok(int64_t rows, int32_t C) {
+    return rows >= 1 && rows <= ((int64_t)1 << 30) && C >= 4 && C <= SPF_BLOCK_MAX_C && C % 4 == 0;
+}
+static int block_sizes_fail(const char* what, int64_t rows, int32_t C) {
+    return fail(SPF_E_INVALID, "%s: rows must be 1 .. 2^30 and C a multiple of 4 in 4 .. %d (got rows = %lld, C = %d)", what,
+                SPF_BLOCK_MAX_C, (long long)rows, C);
+}
+static bool block_aligned(std::initializer_list<const void*> ps) {
+    for (const void* p : ps)
+        if (reinterpret_cast<uintptr_t>(p) & 15) return false;
+    return true;
+}
+// one addressed operand of SpfBlockNorm: the group size and the two strides
+static bool block_rows_ok(int64_t inner, int64_t stride, int64_t outer_stride) {
+    return inner >= 1 && inner <= ((int64_t)1 << 30) && stride >= 0 && outer_stride >= 0 && stride % 4 == 0 &&
+           outer_stride % 4 == 0;
+}
+static int block_norm_check(const char* what, const SpfBlockNorm* a, bool backward) {
+    if (!a) return fail(SPF_E_INVALID, "%s: args is null", what);
+    if (!block_sizes_ok(a->rows, a->C)) return block_sizes_fail(what, a->rows, a->C);
+    if (!a->x || !a->weight || (!backward && !a->bias)) return fail(SPF_E_INVALID, "%s: null pointer (x, weight or bias)", what);
+    if (a->gamma && !a->r) return fail(SPF_E_INVALID, "%s: gamma is given without r", what);
+    if (backward && a->r && !a->gamma) return fail(SPF_E_INVALID, "%s: the backward reads r only with gamma; pass r = null", what);
+    if (!(a->eps >= 0.f)) return fail(SPF_E_INVALID, "%s: eps must be >= 0", what);
+    if (!block_rows_ok(a->x_inner, a->x_stride, a->x_outer_stride) || (a->r && !block_rows_ok(a->r_inner, a->r_stride, a->r_outer_stride)))
+        return fail(SPF_E_INVALID, "%s: group sizes must be >= 1 and strides non-negative multiples of 4 floats", what);
+    if (!block_aligned({a->x, a->r, a->gamma, a->weight, a->bias}))
+        return fail(SPF_E_INVALID, "%s: tensors must be 16-byte aligned", what);
+    return SPF_OK;
+}
+
+int64_t spf_block_partial_blocks(int64_t rows, int32_t C, int32_t gelu) {
+    if (!block_sizes_ok(rows, C)) return block_sizes_fail("block_partial_blocks", rows, C);
+    return spf::block_partial_blocks(rows, C, gelu != 0);
+}
+
+int spf_block_add_norm_forward(const SpfBlockNorm* a, float* s, float* y, float* stats, void* stream_) {
+    if (const int rc = block_norm_check("block_add_norm_forward", a, false)) return rc;
+    if (!y || !stats || (a->r && !s)) return fail(SPF_E_INVALID, "block_add_norm_forward: null output pointer");
+    if (!block_aligned({s, y, stats})) return fail(SPF_E_INVALID, "block_add_norm_forward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_block_norm_fwd(*a, s, y, stats, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_block_add_norm_backward(const SpfBlockNorm* a, const float* dy, const float* ds, const float* stats, float* dx,
+                                float* dr, float* partials, float* dparams, void* stream_) {
+    if (const int rc = block_norm_check("block_add_norm_backward", a, true)) return rc;
+    if (!dy || !stats || !dx || !partials || !dparams) return fail(SPF_E_INVALID, "block_add_norm_backward: null pointer");
+    if ((a->gamma != nullptr) != (dr != nullptr))
+        return fail(SPF_E_INVALID, "block_add_norm_backward: dr is written with gamma only (without it dr is dx)");
+    if (!block_aligned({dy, ds, stats, dx, dr, partials, dparams}))
+        return fail(SPF_E_INVALID, "block_add_norm_backward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_block_norm_bwd(*a, dy, ds, stats, dx, dr, partials, dparams, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_block_bias_gelu_forward(const float* u, const float* bias, int64_t rows, int32_t C, float* h, void* stream_) {
+    if (!block_sizes_ok(rows, C)) return block_sizes_fail("block_bias_gelu_forward", rows, C);
+    if (!u || !h) return fail(SPF_E_INVALID, "block_bias_gelu_forward: null pointer");
+    if (!block_aligned({u, bias, h})) return fail(SPF_E_INVALID, "block_bias_gelu_forward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_block_gelu_fwd(u, bias, rows, C, h, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_block_bias_gelu_backward(const float* u, const float* bias, const float* dh, int64_t rows, int32_t C, float* du,
+                                 float* partials, float* dbias, void* stream_) {
+    if (!block_sizes_ok(rows, C)) return block_sizes_fail("block_bias_gelu_backward", rows, C);
+    if (!u || !dh || !du) return fail(SPF_E_INVALID, "block_bias_gelu_backward: null pointer");
+    if (bias ? (!partials || !dbias) : (partials || dbias))
+        return fail(SPF_E_INVALID, "block_bias_gelu_backward: partials and dbias are given with a bias and only then");
+    if (!block_aligned({u, bias, dh, du, partials, dbias}))
+        return fail(SPF_E_INVALID, "block_bias_gelu_backward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_block_gelu_bwd(u, bias, dh, rows, C, du, partials, dbias, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
 
