@@ -883,6 +883,43 @@ int spf_block_bias_gelu_forward(const float* u, const float* bias, int64_t rows,
 int spf_block_bias_gelu_backward(const float* u, const float* bias, const float* dh, int64_t rows, int32_t C, float* du,
                                  float* partials, float* dbias, void* stream);
 
+/* ---- the DPT heads' work between their convolutions (spfsplatv2_amd/csrc/dpt.hip) -------------------------------------
+ * x2 bilinear upsample (+ skip), add + ReLU and the point-map postprocess, forward and backward, float32 only, NCHW
+ * contiguous.  Every pointer is 16-byte aligned; every tensor of a call holds fewer than 2^31 elements.  Nothing is
+ * allocated or synchronised; no float atomics: bitwise reproducible.  Argument errors return SPF_E_INVALID
+ * (spf_last_error) before anything is launched. */
+#define SPF_DPT_MAX_SIDE 16384
+/* host only: the most blocks any of these launches uses; the rest of the work is taken grid-stride (an upsample block
+ * takes 4,096 items of one plane per round, so a plane of up to 4,096 input pixels is one unit) */
+int32_t spf_dpt_max_grid(void);
+/* out [planes, 2h, 2w] = up2(x [planes, h, w]) + (skip | relu(skip) with relu_skip) [planes, 2h, 2w] (skip may be null).
+ * up2 is torch's bilinear rule with align_corners=True: scale = (in - 1) / (2 in - 1) in float32 (0 for in = 1),
+ * src = scale * dst, i0 = (int)src, i1 = i0 + (i0 < in - 1), lambda1 = src - i0. */
+int spf_dpt_upsample2x_forward(const float* x, const float* skip, int32_t relu_skip, int64_t planes, int32_t h, int32_t w,
+                               float* out, void* stream);
+/* dx [planes, h, w] = up2^T(dy), gathered per input pixel in a fixed order.  With the forward's ReLU flag: skip (the
+ * forward's) and dskip = dy * (skip > 0); without it both are null, because dskip IS dy.  dx may be null where dskip is
+ * written: the gather is then not run. */
+int spf_dpt_upsample2x_backward(const float* dy, const float* skip, int64_t planes, int32_t h, int32_t w, float* dx,
+                                float* dskip, void* stream);
+/* s = a + b (+ c), y = relu(s), n floats each; b, c optional (c only with b).  With a alone s must be null (s is a). */
+int spf_dpt_add_relu_forward(const float* a, const float* b, const float* c, int64_t n, float* s, float* y, void* stream);
+/* g = ds + dy * (mask > 0): the gradient of every addend; mask: the forward's s or y (the same sign), ds optional */
+int spf_dpt_add_relu_backward(const float* mask, const float* dy, const float* ds, int64_t n, float* g, void* stream);
+typedef struct SpfDptPoints {
+    const float* in;              /* [B, C, HW]: channels 0..2 xyz, channel 3 the confidence logit (has_conf) */
+    int64_t B, HW;
+    int32_t C, has_conf;
+    float depth_min, depth_max;   /* bounds of expm1(d); -inf, +inf: none */
+    float conf_min, conf_max;     /* conf = conf_min + min(exp(x), conf_max - conf_min) */
+} SpfDptPoints;
+/* pts3d [B, HW, 3] = xyz / max(d, 1e-8) * clip(expm1(d), depth_min, depth_max), d = |xyz|; conf [B, HW] (with has_conf
+ * and only then) */
+int spf_dpt_points_forward(const SpfDptPoints* args, float* pts3d, float* conf, void* stream);
+/* din [B, C, HW]: channels 0..2 (and 3 with has_conf) are written, what autograd gives for the expression above (d = 0:
+ * zero through the norm; d < 1e-8: nothing through the clip); further channels are left to the caller */
+int spf_dpt_points_backward(const SpfDptPoints* args, const float* dpts3d, const float* dconf, float* din, void* stream);
+
 /* Per-stage device timing with HIP events recorded on the launch stream around every kernel
  * stage.  spf_stage_timing_enable(mask) clears the log and starts recording the stages whose bit
  * (1 << SPF_STAGE_x) is set in `mask` (0 = off, -1 = all) (up to

@@ -140,6 +140,14 @@ class SpfBlockNorm(C.Structure):
                                          "rows")] + [("C", C.c_int32), ("eps", C.c_float)]
 
 
+DPT_MAX_SIDE = 16384
+
+
+class SpfDptPoints(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("B", C.c_int64), ("HW", C.c_int64), ("C", C.c_int32), ("has_conf", C.c_int32),
+                ("depth_min", C.c_float), ("depth_max", C.c_float), ("conf_min", C.c_float), ("conf_max", C.c_float)]
+
+
 # Every symbol include/spfsplat_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "spf_abi_version": (C.c_int, []),
@@ -251,6 +259,16 @@ SYMBOLS = {
     "spf_block_bias_gelu_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "spf_block_bias_gelu_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_dpt_max_grid": (C.c_int32, []),
+    "spf_dpt_upsample2x_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                             C.c_void_p]),
+    "spf_dpt_upsample2x_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+    "spf_dpt_add_relu_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "spf_dpt_add_relu_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "spf_dpt_points_forward": (C.c_int, [C.POINTER(SpfDptPoints), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_dpt_points_backward": (C.c_int, [C.POINTER(SpfDptPoints), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_stage_timing_enable": (C.c_int, [C.c_int32]),
     "spf_stage_timing_sample_every": (C.c_int, [C.c_int32]),
     "spf_stage_times_ms": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_int32)]),

@@ -91,6 +91,13 @@ hipError_t launch_block_norm_bwd(const SpfBlockNorm&, const float*, const float*
 hipError_t launch_block_gelu_fwd(const float*, const float*, int64_t, int, float*, hipStream_t);
 hipError_t launch_block_gelu_bwd(const float*, const float*, const float*, int64_t, int, float*, float*, float*,
                                  hipStream_t);
+int dpt_max_grid();
+hipError_t launch_dpt_up2_fwd(const float*, const float*, int, int64_t, int, int, float*, hipStream_t);
+hipError_t launch_dpt_up2_bwd(const float*, const float*, int64_t, int, int, float*, float*, hipStream_t);
+hipError_t launch_dpt_add_relu_fwd(const float*, const float*, const float*, int64_t, float*, float*, hipStream_t);
+hipError_t launch_dpt_add_relu_bwd(const float*, const float*, const float*, int64_t, float*, hipStream_t);
+hipError_t launch_dpt_points(int, const float*, const float*, const float*, int64_t, int64_t, int, int, float, float, float,
+                             float, float*, float*, float*, hipStream_t);
 }  // namespace spf
 
 namespace {
@@ -1466,6 +1473,103 @@ int spf_block_bias_gelu_backward(const float* u, const float* bias, const float*
     if (!block_aligned({u, bias, dh, du, partials, dbias}))
         return fail(SPF_E_INVALID, "block_bias_gelu_backward: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_block_gelu_bwd(u, bias, dh, rows, C, du, partials, dbias, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+// ---- the DPT heads' work between the convolutions ------------------------------------------------------------------------
+// every tensor of a call stays below 2^31 elements, so no index product can overflow
+static const int64_t kDptMaxElements = ((int64_t)1 << 31) - 1;
+
+int32_t spf_dpt_max_grid(void) { return spf::dpt_max_grid(); }
+
+static int dpt_up2_check(const char* what, int64_t planes, int32_t h, int32_t w) {
+    if (planes < 1 || h < 1 || w < 1)
+        return fail(SPF_E_INVALID, "%s: planes, h and w must be positive (got %lld, %d, %d)", what, (long long)planes, h, w);
+    if (h > SPF_DPT_MAX_SIDE || w > SPF_DPT_MAX_SIDE || planes > kDptMaxElements || planes * 4 * h * w > kDptMaxElements)
+        return fail(SPF_E_INVALID, "%s: h and w must not exceed %d and the output must stay below 2^31 elements (got "
+                    "planes = %lld, h = %d, w = %d)", what, SPF_DPT_MAX_SIDE, (long long)planes, h, w);
+    return SPF_OK;
+}
+
+int spf_dpt_upsample2x_forward(const float* x, const float* skip, int32_t relu_skip, int64_t planes, int32_t h, int32_t w,
+                               float* out, void* stream_) {
+    if (const int rc = dpt_up2_check("dpt_upsample2x_forward", planes, h, w)) return rc;
+    if (!x || !out) return fail(SPF_E_INVALID, "dpt_upsample2x_forward: null pointer (x or out)");
+    if (relu_skip && !skip) return fail(SPF_E_INVALID, "dpt_upsample2x_forward: relu_skip is set without skip");
+    if (!block_aligned({x, skip, out})) return fail(SPF_E_INVALID, "dpt_upsample2x_forward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_dpt_up2_fwd(x, skip, relu_skip != 0, planes, h, w, out, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_dpt_upsample2x_backward(const float* dy, const float* skip, int64_t planes, int32_t h, int32_t w, float* dx,
+                                float* dskip, void* stream_) {
+    if (const int rc = dpt_up2_check("dpt_upsample2x_backward", planes, h, w)) return rc;
+    if (!dy || (!dx && !dskip))
+        return fail(SPF_E_INVALID, "dpt_upsample2x_backward: null pointer (dy; dx may be null only where dskip is written)");
+    if ((skip != nullptr) != (dskip != nullptr))
+        return fail(SPF_E_INVALID, "dpt_upsample2x_backward: skip and dskip are given with the ReLU flag and only then "
+                    "(without it dskip is dy)");
+    if (!block_aligned({dy, skip, dx, dskip})) return fail(SPF_E_INVALID, "dpt_upsample2x_backward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_dpt_up2_bwd(dy, skip, planes, h, w, dx, dskip, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+static int dpt_count_check(const char* what, int64_t n) {
+    if (n < 1 || n > kDptMaxElements)
+        return fail(SPF_E_INVALID, "%s: n must be 1 .. 2^31 - 1 (got %lld)", what, (long long)n);
+    return SPF_OK;
+}
+
+int spf_dpt_add_relu_forward(const float* a, const float* b, const float* c, int64_t n, float* s, float* y, void* stream_) {
+    if (const int rc = dpt_count_check("dpt_add_relu_forward", n)) return rc;
+    if (!a || !y) return fail(SPF_E_INVALID, "dpt_add_relu_forward: null pointer (a or y)");
+    if (c && !b) return fail(SPF_E_INVALID, "dpt_add_relu_forward: c is given without b");
+    if ((b != nullptr) != (s != nullptr))
+        return fail(SPF_E_INVALID, "dpt_add_relu_forward: s is written with a second addend and only then (without one s is a)");
+    if (!block_aligned({a, b, c, s, y})) return fail(SPF_E_INVALID, "dpt_add_relu_forward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_dpt_add_relu_fwd(a, b, c, n, s, y, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_dpt_add_relu_backward(const float* mask, const float* dy, const float* ds, int64_t n, float* g, void* stream_) {
+    if (const int rc = dpt_count_check("dpt_add_relu_backward", n)) return rc;
+    if (!mask || !dy || !g) return fail(SPF_E_INVALID, "dpt_add_relu_backward: null pointer (mask, dy or g)");
+    if (!block_aligned({mask, dy, ds, g})) return fail(SPF_E_INVALID, "dpt_add_relu_backward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_dpt_add_relu_bwd(mask, dy, ds, n, g, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+static int dpt_points_check(const char* what, const SpfDptPoints* a) {
+    if (!a) return fail(SPF_E_INVALID, "%s: args is null", what);
+    if (a->B < 1 || a->HW < 1 || a->C < 3 + (a->has_conf ? 1 : 0) || a->C > 4096)
+        return fail(SPF_E_INVALID, "%s: B and HW must be positive and C at least 3 (4 with conf) (got %lld, %lld, %d)", what,
+                    (long long)a->B, (long long)a->HW, a->C);
+    if (a->B > kDptMaxElements || a->HW > kDptMaxElements || a->B * a->HW > kDptMaxElements / a->C)
+        return fail(SPF_E_INVALID, "%s: the head output must stay below 2^31 elements (got B = %lld, C = %d, HW = %lld)", what,
+                    (long long)a->B, a->C, (long long)a->HW);
+    if (!a->in) return fail(SPF_E_INVALID, "%s: null pointer (in)", what);
+    if (!(a->depth_min <= a->depth_max)) return fail(SPF_E_INVALID, "%s: depth bounds must be ordered", what);
+    if (a->has_conf && !(a->conf_max - a->conf_min >= 0.f)) return fail(SPF_E_INVALID, "%s: conf bounds must be ordered", what);
+    return SPF_OK;
+}
+
+int spf_dpt_points_forward(const SpfDptPoints* a, float* pts3d, float* conf, void* stream_) {
+    if (const int rc = dpt_points_check("dpt_points_forward", a)) return rc;
+    if (!pts3d || (a->has_conf != 0) != (conf != nullptr))
+        return fail(SPF_E_INVALID, "dpt_points_forward: null output pointer (pts3d; conf is given with has_conf and only then)");
+    if (!block_aligned({a->in, pts3d, conf})) return fail(SPF_E_INVALID, "dpt_points_forward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_dpt_points(1, a->in, nullptr, nullptr, a->B, a->HW, a->C, a->has_conf, a->depth_min, a->depth_max,
+                                   a->conf_min, a->conf_max, pts3d, conf, nullptr, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_dpt_points_backward(const SpfDptPoints* a, const float* dpts3d, const float* dconf, float* din, void* stream_) {
+    if (const int rc = dpt_points_check("dpt_points_backward", a)) return rc;
+    if (!dpts3d || !din || (a->has_conf != 0) != (dconf != nullptr))
+        return fail(SPF_E_INVALID, "dpt_points_backward: null pointer (dpts3d, din; dconf is given with has_conf and only then)");
+    if (!block_aligned({a->in, dpts3d, dconf, din})) return fail(SPF_E_INVALID, "dpt_points_backward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_dpt_points(0, a->in, dpts3d, dconf, a->B, a->HW, a->C, a->has_conf, a->depth_min, a->depth_max,
+                                   a->conf_min, a->conf_max, nullptr, nullptr, din, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
 
