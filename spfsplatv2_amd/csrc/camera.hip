@@ -68,15 +68,16 @@ __device__ __forceinline__ void camera_fwd_one(const SpfCamera& c, int r) {
     c.tanfov[2 * r] = tan_x;
     c.tanfov[2 * r + 1] = tan_y;
     if (c.view_scale) c.view_scale[r] = scale;
-    // perspective matrix (column-vector form P), stored transposed
-    const float top = tan_y * nr, bottom = -top, right = tan_x * nr, left = -right;
+    // perspective matrix (column-vector form P), stored transposed.  The frustum is symmetric (left = -right with
+    // right = tan_x * nr, bottom = -top), so P[2] = (right + left) / (right - left) and P[6] are exactly 0 in the
+    // reference's float32 ops and stay 0 here.  (Formed from right and left they were not: the compiler contracts the
+    // product into the sum, fma(tan_x, nr, left), which is the rounding error of tan_x * nr -- up to 2^-25 in the
+    // entry wherever that product is inexact.)
     float P[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) P[i] = 0.f;
     P[0] = (float)(1.0 / tan_xd);      // = 2 n / (right - left)
     P[5] = (float)(1.0 / tan_yd);      // = 2 n / (top - bottom)
-    P[2] = (right + left) / (right - left);
-    P[6] = (top + bottom) / (top - bottom);
     P[14] = 1.f;
     P[10] = fr / (fr - nr);
     P[11] = -(fr * nr) / (fr - nr);
