@@ -920,6 +920,52 @@ int spf_dpt_points_forward(const SpfDptPoints* args, float* pts3d, float* conf, 
  * zero through the norm; d < 1e-8: nothing through the clip); further channels are left to the caller */
 int spf_dpt_points_backward(const SpfDptPoints* args, const float* dpts3d, const float* dconf, float* din, void* stream);
 
+/* ---- the encoder tail (spfsplatv2_amd/csrc/tail.hip) ------------------------------------------------------------------
+ * The heads' outputs, where they lie, -> the decoder's Gaussians (encoder_spfsplatv2.py:218-224, 240, 248-268, 296-321):
+ * per view vi the gs_params head's raw[vi] [b, C = 1 + 7 + 3K, hw] (channel-major, dense) and the point head's pts[vi]
+ * [b, hw, 3]; Gaussian n = vi hw + p of batch item bi is pixel p of view vi.  Per Gaussian, x = raw channels of a pixel:
+ *   means = pts;  opacities = 0.5 (1 - (1 - p)^e + p^(1/e)), p = sigmoid(x[0]), e = exponent (map_pdf_to_opacity);
+ *   scales = min(0.001 softplus(x[1:4]), 0.3);  rotations = x[4:8] / (|x[4:8]| + eps);
+ *   harmonics[c][k] = x[8 + c K + k] sh_mask[k].
+ * K is one of 1, 4, 9, 16, 25 (sh_degree 0..4); any other K is SPF_E_INVALID.  float32 only; every pointer is 16-byte
+ * aligned; b hw C and b v hw 3 K stay below 2^31.  One launch per direction; nothing is allocated or synchronised; no
+ * atomics: bitwise reproducible.  Argument errors return SPF_E_INVALID (spf_last_error) before anything is launched. */
+#define SPF_TAIL_MAX_VIEWS 32
+typedef struct SpfTail {
+    const float* raw[SPF_TAIL_MAX_VIEWS];   /* the first v entries: [b, 8 + 3K, hw] each */
+    const float* pts[SPF_TAIL_MAX_VIEWS];   /* the first v entries: [b, hw, 3] each (backward: not read, may be NULL) */
+    const float* sh_mask;                   /* [K] */
+    int64_t hw;
+    int32_t b, v, K;
+    float exponent, eps;
+    int32_t reserved;
+} SpfTail;
+typedef struct SpfTailGrads {
+    float* d_raw[SPF_TAIL_MAX_VIEWS];       /* the first v entries: [b, 8 + 3K, hw] each, EVERY element is written */
+    float* d_pts[SPF_TAIL_MAX_VIEWS];       /* the first v entries: [b, hw, 3] each, every element is written */
+} SpfTailGrads;
+/* host only: the most blocks a launch of tail.hip uses; a block takes 64-pixel tiles of one (batch item, view),
+ * further tiles grid-stride */
+int32_t spf_tail_max_grid(void);
+/* means [b, v hw, 3], opacities [b, v hw], scales [b, v hw, 3], rotations [b, v hw, 4], harmonics [b, v hw, 3, K]; with
+ * harmonics_high != NULL (K = 25 only) the band split: harmonics [.., 3, 16] and harmonics_high [.., 3, 9]
+ * (SpfDims.sh_layout 2) */
+int spf_tail_forward(const SpfTail* args, float* means, float* opacities, float* scales, float* rotations,
+                     float* harmonics, float* harmonics_high, void* stream);
+/* Any upstream gradient may be NULL = zero (never read).  `split`: dL_dharmonics is [.., 3, 16] and band 4's gradient
+ * is dL_dharmonics_high [.., 3, 9], or NULL: those channels of d_raw are written as zeros.  The density channel's
+ * derivative is taken in logit form, 0.5 (e (1 - p)^e p + (1/e) p^(1/e) (1 - p)) with 1 - p = sigmoid(-x): finite for
+ * every finite logit. */
+int spf_tail_backward(const SpfTail* args, const float* dL_dmeans, const float* dL_dopacities, const float* dL_dscales,
+                      const float* dL_drotations, const float* dL_dharmonics, const float* dL_dharmonics_high,
+                      int32_t split, const SpfTailGrads* grads, void* stream);
+/* The opacity map alone, for a head output that is already in rows (encoder_spfsplatv2l.py:176,184):
+ * opacities[i] = map(logits[i * stride]), i < n (stride >= 1 in floats: channel 0 of a [.., 83] tensor read in place),
+ * and dL_dlogits[i] = dL_dopacities[i] * map'(logits[i * stride]) (both contiguous).  4-byte alignment suffices. */
+int spf_opacity_forward(const float* logits, int64_t stride, int64_t n, float exponent, float* opacities, void* stream);
+int spf_opacity_backward(const float* logits, int64_t stride, int64_t n, float exponent, const float* dL_dopacities,
+                         float* dL_dlogits, void* stream);
+
 /* Per-stage device timing with HIP events recorded on the launch stream around every kernel
  * stage.  spf_stage_timing_enable(mask) clears the log and starts recording the stages whose bit
  * (1 << SPF_STAGE_x) is set in `mask` (0 = off, -1 = all) (up to

@@ -148,6 +148,19 @@ class SpfDptPoints(C.Structure):
                 ("depth_min", C.c_float), ("depth_max", C.c_float), ("conf_min", C.c_float), ("conf_max", C.c_float)]
 
 
+TAIL_MAX_VIEWS = 32
+
+
+class SpfTail(C.Structure):
+    _fields_ = [("raw", C.c_void_p * TAIL_MAX_VIEWS), ("pts", C.c_void_p * TAIL_MAX_VIEWS), ("sh_mask", C.c_void_p),
+                ("hw", C.c_int64), ("b", C.c_int32), ("v", C.c_int32), ("K", C.c_int32), ("exponent", C.c_float),
+                ("eps", C.c_float), ("reserved", C.c_int32)]
+
+
+class SpfTailGrads(C.Structure):
+    _fields_ = [("d_raw", C.c_void_p * TAIL_MAX_VIEWS), ("d_pts", C.c_void_p * TAIL_MAX_VIEWS)]
+
+
 # Every symbol include/spfsplat_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "spf_abi_version": (C.c_int, []),
@@ -269,6 +282,13 @@ SYMBOLS = {
     "spf_dpt_add_relu_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "spf_dpt_points_forward": (C.c_int, [C.POINTER(SpfDptPoints), C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_dpt_points_backward": (C.c_int, [C.POINTER(SpfDptPoints), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_tail_max_grid": (C.c_int32, []),
+    "spf_tail_forward": (C.c_int, [C.POINTER(SpfTail), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "spf_tail_backward": (C.c_int, [C.POINTER(SpfTail), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_int32, C.POINTER(SpfTailGrads), C.c_void_p]),
+    "spf_opacity_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
+    "spf_opacity_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_stage_timing_enable": (C.c_int, [C.c_int32]),
     "spf_stage_timing_sample_every": (C.c_int, [C.c_int32]),
     "spf_stage_times_ms": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_int32)]),

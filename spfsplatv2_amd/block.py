@@ -29,6 +29,7 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._checks import check_device as _check_device, check_float32 as _check_float32
 from .attention import Attention, CrossAttention
 from .vggt_attention import VGGTAttention
 
@@ -36,18 +37,6 @@ MAX_C = _lib.BLOCK_MAX_C
 
 
 # ---- checks --------------------------------------------------------------------------------------------------------
-def _check_float32(what: str, *tensors) -> None:
-    for t in tensors:
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{what}: expected a tensor, got {type(t).__name__}")
-        if t.dtype in (torch.float16, torch.bfloat16):
-            raise NotImplementedError(f"{what}: {t.dtype} is not supported; these layers run in float32")
-        if t.dtype != torch.float32:
-            raise RuntimeError(f"{what}: unsupported dtype {t.dtype}")
-
-
 def _check_width(what: str, c: int) -> None:
     if c % 4 != 0 or not 4 <= c <= MAX_C:
         raise ValueError(f"{what}: the row width must be a multiple of 4 in 4 .. {MAX_C}, got {c}")
@@ -56,14 +45,6 @@ def _check_width(what: str, c: int) -> None:
 def _check_vector(what: str, name: str, v, c: int) -> None:
     if tuple(v.shape) != (c,):
         raise RuntimeError(f"{what}: {name} must have shape [{c}], got {list(v.shape)}")
-
-
-def _check_device(what: str, first, *others) -> None:
-    """The last check of every call."""
-    if not first.is_cuda:
-        raise RuntimeError(f"{what}: the tensors are on the CPU; this build only runs on a HIP device (no CPU fallback)")
-    if any(t is not None and t.device != first.device for t in others):
-        raise RuntimeError(f"{what}: the tensors are not on one device")
 
 
 def _check_norm_call(what, x, r, weight, bias, gamma) -> None:

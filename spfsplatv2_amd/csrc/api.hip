@@ -98,6 +98,12 @@ hipError_t launch_dpt_add_relu_fwd(const float*, const float*, const float*, int
 hipError_t launch_dpt_add_relu_bwd(const float*, const float*, const float*, int64_t, float*, hipStream_t);
 hipError_t launch_dpt_points(int, const float*, const float*, const float*, int64_t, int64_t, int, int, float, float, float,
                              float, float*, float*, float*, hipStream_t);
+int tail_max_grid();
+hipError_t launch_tail_fwd(const SpfTail&, float*, float*, float*, float*, float*, float*, hipStream_t);
+hipError_t launch_tail_bwd(const SpfTail&, const SpfTailGrads&, const float*, const float*, const float*, const float*,
+                           const float*, const float*, int, hipStream_t);
+hipError_t launch_opacity_fwd(const float*, int64_t, int64_t, float, float*, hipStream_t);
+hipError_t launch_opacity_bwd(const float*, int64_t, int64_t, float, const float*, float*, hipStream_t);
 }  // namespace spf
 
 namespace {
@@ -1570,6 +1576,85 @@ int spf_dpt_points_backward(const SpfDptPoints* a, const float* dpts3d, const fl
     if (!block_aligned({a->in, dpts3d, dconf, din})) return fail(SPF_E_INVALID, "dpt_points_backward: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_dpt_points(0, a->in, dpts3d, dconf, a->B, a->HW, a->C, a->has_conf, a->depth_min, a->depth_max,
                                    a->conf_min, a->conf_max, nullptr, nullptr, din, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+// ---- the encoder tail (tail.hip) ---------------------------------------------------------------------------------------
+int32_t spf_tail_max_grid(void) { return spf::tail_max_grid(); }
+
+static int tail_check(const char* what, const SpfTail* a, bool need_pts) {
+    if (!a) return fail(SPF_E_INVALID, "%s: args is null", what);
+    if (a->b < 1 || a->hw < 1 || a->v < 1 || a->v > SPF_TAIL_MAX_VIEWS)
+        return fail(SPF_E_INVALID, "%s: b and hw must be positive and v in 1..%d (got b = %d, v = %d, hw = %lld)", what,
+                    SPF_TAIL_MAX_VIEWS, a->b, a->v, (long long)a->hw);
+    if (a->K != 1 && a->K != 4 && a->K != 9 && a->K != 16 && a->K != 25)
+        return fail(SPF_E_INVALID, "%s: K must be one of 1, 4, 9, 16, 25 (got %d)", what, a->K);
+    const int64_t lim = ((int64_t)1 << 31) - 1;
+    if (a->hw > lim / ((int64_t)a->b * (8 + 3 * a->K)) || a->hw > lim / ((int64_t)a->b * a->v * 3 * a->K))
+        return fail(SPF_E_INVALID, "%s: b hw (8 + 3K) and b v hw 3K must stay below 2^31 (got b = %d, v = %d, hw = %lld, K = %d)",
+                    what, a->b, a->v, (long long)a->hw, a->K);
+    if (!(a->exponent > 0.f) || !(a->exponent < 3.0e38f)) return fail(SPF_E_INVALID, "%s: exponent must be positive and finite", what);
+    if (!a->sh_mask) return fail(SPF_E_INVALID, "%s: null pointer (sh_mask)", what);
+    for (int i = 0; i < a->v; ++i) {
+        if (!a->raw[i] || (need_pts && !a->pts[i])) return fail(SPF_E_INVALID, "%s: null pointer (raw or pts of view %d)", what, i);
+        if (!block_aligned({a->raw[i], a->pts[i]})) return fail(SPF_E_INVALID, "%s: tensors must be 16-byte aligned (view %d)", what, i);
+    }
+    return SPF_OK;
+}
+
+int spf_tail_forward(const SpfTail* a, float* means, float* opacities, float* scales, float* rotations, float* harmonics,
+                     float* harmonics_high, void* stream_) {
+    if (const int rc = tail_check("tail_forward", a, true)) return rc;
+    if (!means || !opacities || !scales || !rotations || !harmonics) return fail(SPF_E_INVALID, "tail_forward: null output pointer");
+    if (harmonics_high && a->K != 25) return fail(SPF_E_INVALID, "tail_forward: the band-split layout is the 16 + 9 split of K = 25 (got K = %d)", a->K);
+    if (!block_aligned({means, opacities, scales, rotations, harmonics, harmonics_high, a->sh_mask}))
+        return fail(SPF_E_INVALID, "tail_forward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_tail_fwd(*a, means, opacities, scales, rotations, harmonics, harmonics_high, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_tail_backward(const SpfTail* a, const float* dL_dmeans, const float* dL_dopacities, const float* dL_dscales,
+                      const float* dL_drotations, const float* dL_dharmonics, const float* dL_dharmonics_high, int32_t split,
+                      const SpfTailGrads* g, void* stream_) {
+    if (const int rc = tail_check("tail_backward", a, false)) return rc;
+    if (!g) return fail(SPF_E_INVALID, "tail_backward: grads is null");
+    if (split && a->K != 25) return fail(SPF_E_INVALID, "tail_backward: the band-split layout is the 16 + 9 split of K = 25 (got K = %d)", a->K);
+    if (!split && dL_dharmonics_high) return fail(SPF_E_INVALID, "tail_backward: dL_dharmonics_high without split");
+    for (int i = 0; i < a->v; ++i) {
+        if (!g->d_raw[i] || !g->d_pts[i]) return fail(SPF_E_INVALID, "tail_backward: null pointer (d_raw or d_pts of view %d)", i);
+        if (!block_aligned({g->d_raw[i], g->d_pts[i]})) return fail(SPF_E_INVALID, "tail_backward: tensors must be 16-byte aligned (view %d)", i);
+    }
+    if (!block_aligned({dL_dmeans, dL_dopacities, dL_dscales, dL_drotations, dL_dharmonics, dL_dharmonics_high, a->sh_mask}))
+        return fail(SPF_E_INVALID, "tail_backward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_tail_bwd(*a, *g, dL_dmeans, dL_dopacities, dL_dscales, dL_drotations, dL_dharmonics, dL_dharmonics_high,
+                                 split ? 1 : 0, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+static int opacity_check(const char* what, const float* logits, int64_t stride, int64_t n, float exponent) {
+    if (!logits) return fail(SPF_E_INVALID, "%s: null pointer (logits)", what);
+    if (n < 0 || stride < 1 || (n > 0 && stride > (((int64_t)1 << 62) / n)))
+        return fail(SPF_E_INVALID, "%s: n must be >= 0 and stride >= 1 (got n = %lld, stride = %lld)", what, (long long)n, (long long)stride);
+    if (!(exponent > 0.f) || !(exponent < 3.0e38f)) return fail(SPF_E_INVALID, "%s: exponent must be positive and finite", what);
+    return SPF_OK;
+}
+
+int spf_opacity_forward(const float* logits, int64_t stride, int64_t n, float exponent, float* opacities, void* stream_) {
+    if (const int rc = opacity_check("opacity_forward", logits, stride, n, exponent)) return rc;
+    if (!opacities) return fail(SPF_E_INVALID, "opacity_forward: null pointer (opacities)");
+    if (!aligned4({logits, opacities})) return fail(SPF_E_INVALID, "opacity_forward: tensors must be 4-byte aligned");
+    if (n == 0) return SPF_OK;
+    SPF_HIP(spf::launch_opacity_fwd(logits, stride, n, exponent, opacities, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_opacity_backward(const float* logits, int64_t stride, int64_t n, float exponent, const float* dL_dopacities,
+                         float* dL_dlogits, void* stream_) {
+    if (const int rc = opacity_check("opacity_backward", logits, stride, n, exponent)) return rc;
+    if (!dL_dopacities || !dL_dlogits) return fail(SPF_E_INVALID, "opacity_backward: null pointer (dL_dopacities or dL_dlogits)");
+    if (!aligned4({logits, dL_dopacities, dL_dlogits})) return fail(SPF_E_INVALID, "opacity_backward: tensors must be 4-byte aligned");
+    if (n == 0) return SPF_OK;
+    SPF_HIP(spf::launch_opacity_bwd(logits, stride, n, exponent, dL_dopacities, dL_dlogits, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
 
