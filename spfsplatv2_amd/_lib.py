@@ -10,6 +10,8 @@ import ctypes as C
 import os
 from pathlib import Path
 
+import torch
+
 # SPF_LIB_DIR: development only -- a profiling/experimental build kept next to the regular one (see build.py)
 LIB_PATH = Path(__file__).resolve().parent / os.environ.get("SPF_LIB_DIR", "_C") / "libspfsplat_hip.so"
 ABI_VERSION = 7
@@ -26,22 +28,22 @@ class SpfDims(C.Structure):
                 ("bin_cap", C.c_int32), ("pair_capacity", C.c_int64), ("raw_stride", C.c_int64), ("adapter_eps", C.c_float)]
 
 
-def _ptr_struct(name, fields, ctype=C.c_void_p):
+def _struct_of(name, fields, ctype=C.c_void_p):
     return type(name, (C.Structure,), {"_fields_": [(f, ctype) for f in fields]})
 
 
-SpfInputs = _ptr_struct("SpfInputs", ["means3D", "scales", "rotations", "opacities", "shs", "colors",
+SpfInputs = _struct_of("SpfInputs", ["means3D", "scales", "rotations", "opacities", "shs", "colors",
                                       "viewmatrix", "projmatrix", "tanfov", "bg", "view_scale", "viewmatrix64",
                                       "shs_high", "raw", "sh_mask"])
-SpfState = _ptr_struct("SpfState", ["rec", "radii", "rect", "zkey", "tile_count", "tile_start", "tile_fill",
+SpfState = _struct_of("SpfState", ["rec", "radii", "rect", "zkey", "tile_count", "tile_start", "tile_fill",
                                     "tile_flags", "counters", "pairs", "pair_off", "blk_total", "blk_base", "final_T",
                                     "n_contrib", "pair_cursor", "sh_clamp", "verdict_host"])
-SpfOutputs = _ptr_struct("SpfOutputs", ["image", "depth", "alpha"])
-SpfGrads = _ptr_struct("SpfGrads", ["dL_dimage", "dL_ddepth", "dL_dalpha", "gpair", "vpartial",
+SpfOutputs = _struct_of("SpfOutputs", ["image", "depth", "alpha"])
+SpfGrads = _struct_of("SpfGrads", ["dL_dimage", "dL_ddepth", "dL_dalpha", "gpair", "vpartial",
                                     "dL_dmeans3D", "dL_dscales", "dL_drotations", "dL_dopacities",
                                     "dL_dshs", "dL_dcolors", "dL_dviewmatrix", "dL_dmeans2D", "dL_dshs_high",
                                     "dL_draw"])
-SpfStateLayout = _ptr_struct("SpfStateLayout", ["rect_words", "tiles_words", "pair_idx_words", "zkey", "sh_clamp", "tile_flags",
+SpfStateLayout = _struct_of("SpfStateLayout", ["rect_words", "tiles_words", "pair_idx_words", "zkey", "sh_clamp", "tile_flags",
                                              "tile_start", "tile_fill", "counters", "pair_cursor", "blk_total", "blk_base"], C.c_int64)
 
 
@@ -361,6 +363,36 @@ def check(rc: int, what: str) -> None:
     if rc != 0:
         msg = load().spf_last_error().decode(errors="replace")
         raise SpfError(f"{what} failed (code {rc}): {msg}")
+
+
+def ptr(t):
+    """The data pointer of a tensor as a c_void_p; None (the null pointer) for None."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream_ptr(device):
+    """The current stream of `device` as a c_void_p."""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+_AS_IS = frozenset((int, float, bool, type(None)))      # tested first: half of a small kernel's arguments are sizes
+
+
+def cargs(args) -> list:
+    """Python arguments as ctypes ones: a tensor as its pointer, None as the null pointer, a structure by reference;
+    ints, bools, floats and ctypes scalars and arrays pass through for `argtypes` to convert.  Needs no GPU."""
+    return [a if a.__class__ in _AS_IS else C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor)
+            else C.byref(a) if isinstance(a, C.Structure) else a for a in args]
+
+
+def launch(name: str, device, *args) -> None:
+    """The one way Python starts a kernel: inside `device`, call the entry point `name` with `cargs(args)` and the
+    current stream of `device` LAST, and raise SpfError unless it returns 0.  Every launching entry point in SYMBOLS
+    takes its stream as its last argument -- keep that true.  Entry points that launch nothing (*_partial_blocks,
+    *_scratch_bytes, spf_optim_plan, ..) are plain calls on `load()`.  No sync, no allocation, no host read."""
+    fn = getattr(load(), name)
+    with torch.cuda.device(device):
+        check(fn(*cargs(args), stream_ptr(device)), name)
 
 
 def stage_timing_enable(stages=True) -> None:

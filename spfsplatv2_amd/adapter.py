@@ -5,7 +5,6 @@ a chain of ~10 elementwise torch kernels.  ``covariances`` -- which no consumer 
 (cuda_splatting.py:136) -- are only materialised on request."""
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import Optional
 
@@ -34,10 +33,6 @@ class GaussianAdapterCfg:
     sh_degree: int
 
 
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 from .rasterizer import raw_rows as _rows          # (rows read in place: see there)
 
 
@@ -58,7 +53,6 @@ class _AdapterFn(torch.autograd.Function):
         # (`raw_any`: the caller's tensor, whatever its shape; its [N, d_in] rows are taken HERE, outside autograd's view --
         #  as an autograd op the as_strided of a view costs a zero fill and a scatter copy of the whole tensor in backward)
         ctx.set_materialize_grads(False)
-        lib = _lib.load()
         raw = _rows(raw_any.detach(), d_in)
         ctx.raw_shape = tuple(raw_any.shape)
         N, Cn = raw.shape
@@ -68,18 +62,13 @@ class _AdapterFn(torch.autograd.Function):
         rot = torch.empty((N, 4), **f32)
         sh = torch.empty((N, 3, 16 if split else K), **f32)
         sh_hi = torch.empty((N, 3, 9), **f32) if split else None
-        with torch.cuda.device(raw.device):
-            _lib.check(lib.spf_adapter_forward(_p(raw), raw.stride(0), N, K, _p(mask), float(eps), _p(scales), _p(rot),
-                                               _p(sh), _p(sh_hi),
-                                               C.c_void_p(torch.cuda.current_stream(raw.device).cuda_stream)),
-                       "spf_adapter_forward")
+        _lib.launch("spf_adapter_forward", raw.device, raw, raw.stride(0), N, K, mask, float(eps), scales, rot, sh, sh_hi)
         ctx.save_for_backward(raw, mask)
         ctx.eps, ctx.split = float(eps), bool(split)
         return (scales, rot, sh, sh_hi) if split else (scales, rot, sh)
 
     @staticmethod
     def backward(ctx, g_scales, g_rot, g_sh, g_sh_hi=None):
-        lib = _lib.load()
         raw, mask = ctx.saved_tensors
         N, Cn = raw.shape
         K = (Cn - 7) // 3
@@ -88,11 +77,8 @@ class _AdapterFn(torch.autograd.Function):
         #  and the kernel then writes zeros for those channels without reading anything)
         g_scales, g_rot, g_sh, g_sh_hi = c(g_scales), c(g_rot), c(g_sh), c(g_sh_hi)
         g_raw = torch.empty((N, Cn), dtype=torch.float32, device=raw.device)
-        with torch.cuda.device(raw.device):
-            _lib.check(lib.spf_adapter_backward(_p(raw), raw.stride(0), N, K, _p(mask), ctx.eps, _p(g_scales), _p(g_rot),
-                                                _p(g_sh), _p(g_sh_hi), 1 if ctx.split else 0, _p(g_raw),
-                                                C.c_void_p(torch.cuda.current_stream(raw.device).cuda_stream)),
-                       "spf_adapter_backward")
+        _lib.launch("spf_adapter_backward", raw.device, raw, raw.stride(0), N, K, mask, ctx.eps, g_scales, g_rot, g_sh,
+                    g_sh_hi, 1 if ctx.split else 0, g_raw)
         return g_raw.view(ctx.raw_shape), None, None, None, None
 
 

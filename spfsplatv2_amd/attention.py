@@ -169,8 +169,7 @@ def _args(q, k, v, qpos, kpos, base, F0, scale) -> _lib.SpfAttn:
     """SpfAttn of a call on [B,H,N,D] or [b,V,H,N,D] tokens (B: the scenes then; the views travel in SpfAttnViews)."""
     a = _lib.SpfAttn()
     a.q, a.k, a.v = q.data_ptr(), k.data_ptr(), v.data_ptr()
-    a.qpos = qpos.data_ptr() if qpos is not None else None
-    a.kpos = kpos.data_ptr() if kpos is not None else None
+    a.qpos, a.kpos = _lib.ptr(qpos), _lib.ptr(kpos)
     a.q_stride, a.k_stride, a.v_stride = _strides(q), _strides(k), _strides(v)
     a.B, a.H, a.Nq, a.Nk, a.D = q.shape[0], q.shape[-3], q.shape[-2], k.shape[-2], q.shape[-1]
     a.dtype = _DTYPES[q.dtype]
@@ -191,16 +190,6 @@ def _saved(out, dout, dtype):
     if dout.dtype != dtype or out.dtype != dtype:
         raise RuntimeError(f"rope_attention: gradient dtype {dout.dtype} differs from the inputs' {dtype}")
     return out, dout
-
-
-def _launch(name: str, device, *args) -> None:
-    """Entry point ``name`` of the library on ``device``'s current stream; a tensor goes as its pointer, a structure by
-    reference, in the order given."""
-    lib = _lib.load()
-    with torch.cuda.device(device):
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        cargs = [C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else C.byref(a) for a in args]
-        _lib.check(getattr(lib, name)(*cargs, stream), name)
 
 
 def _mask_view(mask, shape):
@@ -248,9 +237,9 @@ def attention_forward(q, k, v, qpos, kpos, base, F0, scale, *, mask=None, q_norm
     q_norm, k_norm = _norm_tensors(q_norm), _norm_tensors(k_norm)
     a = _args(q, k, v, qpos, kpos, base, F0, scale)
     if matrix16:
-        _launch("spf_attn16_forward", q.device, a, out, lse)
+        _lib.launch("spf_attn16_forward", q.device, a, out, lse)
     else:                                               # (an empty SpfAttnExt: the library runs the plain kernels)
-        _launch("spf_attn_forward_ext", q.device, a, _ext(mask, q_norm, k_norm), out, lse)
+        _lib.launch("spf_attn_forward_ext", q.device, a, _ext(mask, q_norm, k_norm), out, lse)
     return out, lse
 
 
@@ -278,9 +267,10 @@ def attention_backward(q, k, v, qpos, kpos, base, F0, scale, out, lse, dout, dq,
         partials = torch.empty(n, dtype=torch.float32, device=q.device)
     a, g = _args(q, k, v, qpos, kpos, base, F0, scale), _grads(dq, dk, dv, delta)
     if matrix16:
-        _launch("spf_attn16_backward", q.device, a, g, out, lse, dout)
+        _lib.launch("spf_attn16_backward", q.device, a, g, out, lse, dout)
     else:
-        _launch("spf_attn_backward_ext", q.device, a, g, _ext(mask, q_norm, k_norm, dnorm, partials), out, lse, dout)
+        _lib.launch("spf_attn_backward_ext", q.device, a, g, _ext(mask, q_norm, k_norm, dnorm, partials), out, lse,
+                    dout)
     return dnorm
 
 
@@ -494,8 +484,8 @@ def attention_views_forward(q, k, v, qpos, kpos, words, base, F0, scale):
     b, Vq, H, Nq, D = q.shape
     out = torch.empty(b, Vq, Nq, H * D, dtype=q.dtype, device=q.device)
     lse = torch.empty(b, Vq, H, Nq, dtype=torch.float32, device=q.device)
-    _launch("spf_attn_views_forward", q.device, _args(q, k, v, qpos, kpos, base, F0, scale),
-            _view_ext(q, k, v, qpos, kpos, words), out, lse)
+    _lib.launch("spf_attn_views_forward", q.device, _args(q, k, v, qpos, kpos, base, F0, scale),
+                _view_ext(q, k, v, qpos, kpos, words), out, lse)
     return out, lse
 
 
@@ -513,8 +503,8 @@ def attention_views_backward(q, k, v, qpos, kpos, words, base, F0, scale, out, l
     delta = torch.empty(b, Vq, H, Nq, dtype=torch.float32, device=q.device)
     w = _view_ext(q, k, v, qpos, kpos, words)
     w.dq_view_stride, w.dk_view_stride, w.dv_view_stride = dq.stride(1), dk.stride(1), dv.stride(1)
-    _launch("spf_attn_views_backward", q.device, _args(q, k, v, qpos, kpos, base, F0, scale), w,
-            _grads(dq, dk, dv, delta), out, lse, dout)
+    _lib.launch("spf_attn_views_backward", q.device, _args(q, k, v, qpos, kpos, base, F0, scale), w,
+                _grads(dq, dk, dv, delta), out, lse, dout)
 
 
 class _RopeAttentionViews(torch.autograd.Function):

@@ -21,8 +21,6 @@ pass that produces the gradient of the tokens, summed without atomics: two runs 
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -107,9 +105,7 @@ def _norm_args(x, r, gamma, weight, bias, eps) -> _lib.SpfBlockNorm:
         a.r_inner, a.r_stride, a.r_outer_stride = _row_map(r)
     else:
         a.r_inner = 1
-    a.gamma = gamma.data_ptr() if gamma is not None else None
-    a.weight = weight.data_ptr()
-    a.bias = bias.data_ptr() if bias is not None else None
+    a.gamma, a.weight, a.bias = _lib.ptr(gamma), weight.data_ptr(), _lib.ptr(bias)
     a.rows, a.C, a.eps = x.numel() // x.shape[-1], x.shape[-1], float(eps)
     return a
 
@@ -121,20 +117,6 @@ def partial_blocks(rows: int, c: int, gelu: bool = False) -> int:
     if n < 0:
         raise _lib.SpfError("spf_block_partial_blocks rejected the sizes: " + _lib.load().spf_last_error().decode())
     return int(n)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr() if t is not None else None)
-
-
-def _call(name: str, device, *args) -> None:
-    """As attention._launch, with None for a null pointer and plain integers passed through."""
-    lib = _lib.load()
-    with torch.cuda.device(device):
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        cargs = [_ptr(a) if a is None or isinstance(a, torch.Tensor) else (a if isinstance(a, int) else C.byref(a))
-                 for a in args]
-        _lib.check(getattr(lib, name)(*cargs, stream), name)
 
 
 # ---- launches --------------------------------------------------------------------------------------------------------
@@ -151,7 +133,7 @@ def add_norm_forward(x, r, weight, bias, eps, gamma=None):
     s = torch.empty(x.shape, dtype=x.dtype, device=x.device) if r is not None else None
     y = torch.empty(x.shape, dtype=x.dtype, device=x.device)
     stats = torch.empty(rows, 4, dtype=torch.float32, device=x.device)
-    _call("spf_block_add_norm_forward", x.device, _norm_args(x, r, gamma, weight, bias, eps), s, y, stats)
+    _lib.launch("spf_block_add_norm_forward", x.device, _norm_args(x, r, gamma, weight, bias, eps), s, y, stats)
     return s, y, stats
 
 
@@ -174,8 +156,8 @@ def add_norm_backward(sx, r, weight, gamma, stats, dy, ds, eps):
     dr = torch.empty(sx.shape, dtype=sx.dtype, device=sx.device) if gamma is not None else None
     partials = torch.empty(kinds * partial_blocks(rows, c) * c, dtype=torch.float32, device=sx.device)
     dparams = torch.empty(kinds, c, dtype=torch.float32, device=sx.device)
-    _call("spf_block_add_norm_backward", sx.device, _norm_args(sx, r, gamma, weight, None, eps), dy, ds, stats, dx, dr,
-          partials, dparams)
+    _lib.launch("spf_block_add_norm_backward", sx.device, _norm_args(sx, r, gamma, weight, None, eps), dy, ds, stats,
+                dx, dr, partials, dparams)
     return dx, dr, dparams
 
 
@@ -195,7 +177,7 @@ def gelu_forward(u, bias):
     u = u.contiguous()
     bias = bias.detach().contiguous() if bias is not None else None
     h = torch.empty(u.shape, dtype=u.dtype, device=u.device)
-    _call("spf_block_bias_gelu_forward", u.device, u, bias, u.numel() // u.shape[-1], u.shape[-1], h)
+    _lib.launch("spf_block_bias_gelu_forward", u.device, u, bias, u.numel() // u.shape[-1], u.shape[-1], h)
     return h
 
 
@@ -214,7 +196,7 @@ def gelu_backward(u, bias, dh):
         bias = bias.detach().contiguous()
         partials = torch.empty(partial_blocks(rows, c, True) * c, dtype=torch.float32, device=u.device)
         dbias = torch.empty(c, dtype=torch.float32, device=u.device)
-    _call("spf_block_bias_gelu_backward", u.device, u, bias, dh, rows, c, du, partials, dbias)
+    _lib.launch("spf_block_bias_gelu_backward", u.device, u, bias, dh, rows, c, du, partials, dbias)
     return du, dbias
 
 

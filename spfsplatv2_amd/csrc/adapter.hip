@@ -14,6 +14,7 @@
 // (Round 4's two kernels -- one lane per Gaussian for the seven geometric channels, a flat scale-copy for the harmonics --
 // read every raw row twice, 28 bytes of it at a 328-byte stride, and needed a contiguous copy of a strided input first.)
 #include "spf_common.h"
+#include "launchers.h"
 
 namespace spf {
 

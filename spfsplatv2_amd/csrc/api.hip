@@ -7,104 +7,7 @@
 
 #include <initializer_list>
 
-#include "spf_common.h"
-
-namespace spf {
-hipError_t launch_project_fwd(const SpfDims&, const SpfInputs&, const SpfState&, int, int, hipStream_t,
-                              const float* cov3D = nullptr);
-hipError_t launch_project_bwd(const SpfDims&, const SpfInputs&, const SpfState&, const SpfGrads&, int, uint64_t, hipStream_t,
-                              const float* cov3D = nullptr, float* dL_dcov3D = nullptr);
-hipError_t launch_tile_scan(const SpfState&, int, int, int, uint32_t, bool, hipStream_t);
-uint32_t dense_threshold();
-hipError_t launch_bin_pairs(const SpfDims&, const SpfState&, uint64_t, int, int, uint32_t, hipStream_t);
-SortSwitches read_sort_switches();
-int plan_tile_sort(uint32_t, int, bool, const SortSwitches&, SortLaunch*);
-hipError_t launch_tile_sort(const SpfState&, const TileLists&, int, int, uint64_t, uint32_t, const uint2*, int,
-                            hipStream_t);
-hipError_t launch_render_fwd(const SpfDims&, const SpfInputs&, const SpfState&, const SpfOutputs&, uint64_t, int, int,
-                             bool, hipStream_t);
-hipError_t launch_render_bwd(const SpfDims&, const SpfInputs&, const SpfState&, const SpfGrads&, int, int, uint64_t, bool,
-                             hipStream_t);
-hipError_t launch_adapter_fwd(const float*, int64_t, int64_t, int, const float*, float, float*, float*, float*, float*,
-                              hipStream_t);
-hipError_t launch_adapter_bwd(const float*, int64_t, int64_t, int, const float*, float, const float*, const float*,
-                              const float*, const float*, int, float*, hipStream_t);
-int mse_partial_blocks();
-hipError_t launch_mse_fwd(const float*, const float*, int64_t, float, float*, float*, float, float*, hipStream_t);
-hipError_t launch_mse_scale(float*, int64_t, const float*, hipStream_t);
-hipError_t launch_mse_bwd(const float*, const float*, int64_t, float, const float*, float*, hipStream_t);
-int64_t reproj_slots(int, int, int, int, int*);
-hipError_t launch_reproj_fwd(const SpfReproj&, void*, float*, float*, hipStream_t);
-hipError_t launch_reproj_bwd(const SpfReproj&, const float*, const float*, float*, float*, float*, float*, hipStream_t);
-int64_t regr3d_scratch_words(int, int, int);
-hipError_t launch_regr3d_fwd(const SpfRegr3d&, void*, float*, float*, hipStream_t);
-hipError_t launch_regr3d_bwd(const SpfRegr3d&, const void*, const float*, const float*, float*, float*, hipStream_t);
-hipError_t launch_pose_compose_fwd(const float*, int64_t, int64_t, int, int, int, int, int, int, float*, hipStream_t);
-hipError_t launch_pose_compose_bwd(const float*, int64_t, int64_t, int, int, int, int, int, int, const float*, float*,
-                                   hipStream_t);
-int64_t depth_slots(int, int, int*);
-hipError_t launch_depth_fwd(const float*, int64_t, const float*, int, int, float*, hipStream_t);
-hipError_t launch_depth_bwd(const float*, int64_t, const float*, int, int, const float*, float*, float*, float*,
-                            hipStream_t);
-hipError_t launch_pose_error(const float*, const float*, int, float*, float*, hipStream_t);
-hipError_t launch_focal(const float*, int64_t, int64_t, int, int, int, const float*, int64_t, float, float, float, float,
-                        float, float, float, float*, float*, hipStream_t);
-int64_t ssim_slots(int, int, int, int, int);
-hipError_t launch_ssim_fwd(const SpfSsim&, float*, float*, float*, hipStream_t);
-hipError_t launch_ssim_bwd(const SpfSsim&, const float*, const float*, float*, float*, hipStream_t);
-hipError_t launch_psnr(const float*, const float*, int, int64_t, float*, hipStream_t);
-int64_t lpips_workspace_bytes(int, int, int, int);
-size_t lpips_pack_offset(int);
-hipError_t launch_lpips_fwd(const SpfLpips&, float*, float*, float*, hipStream_t);
-hipError_t launch_lpips_bwd(const SpfLpips&, float*, const float*, int, float*, float*, hipStream_t);
-hipError_t launch_lpips_conv(const float*, const float*, const float*, const float*, float*, int, int, int, int, int, int,
-                             hipStream_t);
-hipError_t launch_lpips_conv1(const SpfLpips&, int, float*, hipStream_t);
-hipError_t launch_lpips_conv1_bwd(const SpfLpips&, const float*, const float*, int, float*, int, float*, hipStream_t);
-hipError_t launch_lpips_pool(const float*, float*, int, int, int, int, hipStream_t);
-hipError_t launch_lpips_pool_bwd(const float*, const float*, float*, int, int, int, int, hipStream_t);
-hipError_t launch_lpips_head_single(const float*, const float*, const float*, int, int, int, float*, float*, hipStream_t);
-hipError_t launch_lpips_head_bwd(const float*, const float*, const float*, int, int, int, const float*, int, float, float*,
-                                 float*, hipStream_t);
-hipError_t launch_camera_fwd(const SpfCamera&, hipStream_t);
-hipError_t launch_camera_bwd(const SpfCamera&, const float*, float*, hipStream_t);
-hipError_t launch_camera_fwd_zero(const SpfCamera&, void*, uint64_t, hipStream_t);
-hipError_t launch_camera_bwd_reduce(const SpfCamera&, const float*, int, float*, hipStream_t);
-hipError_t launch_attn_forward(const SpfAttn&, const SpfAttnExt*, void*, float*, hipStream_t);
-hipError_t launch_attn_backward(const SpfAttn&, const SpfAttnGrads&, const SpfAttnExt*, const void*, const float*,
-                                const void*, hipStream_t);
-int64_t attn_ext_scratch_floats(int, int, int, int);
-hipError_t launch_attn16_forward(const SpfAttn&, void*, float*, hipStream_t);
-hipError_t launch_attn16_backward(const SpfAttn&, const SpfAttnGrads&, const void*, const float*, const void*, hipStream_t);
-hipError_t launch_attn_views_forward(const SpfAttn&, const SpfAttnViews&, void*, float*, hipStream_t);
-hipError_t launch_attn_views_backward(const SpfAttn&, const SpfAttnViews&, const SpfAttnGrads&, const void*, const float*,
-                                      const void*, hipStream_t);
-hipError_t launch_rope2d(void*, void*, const int64_t*, int, int, int, int, int64_t, int64_t, int64_t, int, int, float,
-                         float, hipStream_t);
-int64_t optim_chunks_of(int64_t);
-int64_t optim_scratch_bytes(int, int64_t);
-hipError_t launch_optim_step(const SpfOptim&, const SpfOptimHyper&, hipStream_t);
-int64_t block_partial_blocks(int64_t, int, int);
-hipError_t launch_block_norm_fwd(const SpfBlockNorm&, float*, float*, float*, hipStream_t);
-hipError_t launch_block_norm_bwd(const SpfBlockNorm&, const float*, const float*, const float*, float*, float*, float*,
-                                 float*, hipStream_t);
-hipError_t launch_block_gelu_fwd(const float*, const float*, int64_t, int, float*, hipStream_t);
-hipError_t launch_block_gelu_bwd(const float*, const float*, const float*, int64_t, int, float*, float*, float*,
-                                 hipStream_t);
-int dpt_max_grid();
-hipError_t launch_dpt_up2_fwd(const float*, const float*, int, int64_t, int, int, float*, hipStream_t);
-hipError_t launch_dpt_up2_bwd(const float*, const float*, int64_t, int, int, float*, float*, hipStream_t);
-hipError_t launch_dpt_add_relu_fwd(const float*, const float*, const float*, int64_t, float*, float*, hipStream_t);
-hipError_t launch_dpt_add_relu_bwd(const float*, const float*, const float*, int64_t, float*, hipStream_t);
-hipError_t launch_dpt_points(int, const float*, const float*, const float*, int64_t, int64_t, int, int, float, float, float,
-                             float, float*, float*, float*, hipStream_t);
-int tail_max_grid();
-hipError_t launch_tail_fwd(const SpfTail&, float*, float*, float*, float*, float*, float*, hipStream_t);
-hipError_t launch_tail_bwd(const SpfTail&, const SpfTailGrads&, const float*, const float*, const float*, const float*,
-                           const float*, const float*, int, hipStream_t);
-hipError_t launch_opacity_fwd(const float*, int64_t, int64_t, float, float*, hipStream_t);
-hipError_t launch_opacity_bwd(const float*, int64_t, int64_t, float, const float*, float*, hipStream_t);
-}  // namespace spf
+#include "launchers.h"
 
 namespace {
 
@@ -116,6 +19,13 @@ int fail(int code, const char* fmt, ...) {
     vsnprintf(g_err, sizeof g_err, fmt, ap);
     va_end(ap);
     return code;
+}
+
+// every pointer is a multiple of N bytes; a null pointer passes (whether it may be null is the caller's own check)
+template <unsigned N> bool aligned(std::initializer_list<const void*> ps) {
+    uintptr_t x = 0;
+    for (const void* p : ps) x |= reinterpret_cast<uintptr_t>(p);
+    return (x & (N - 1)) == 0;
 }
 
 #define SPF_HIP(expr)                                                                         \
@@ -504,7 +414,7 @@ int spf_raster_forward_project_cov3d(const SpfDims* d, const SpfInputs* in, cons
 int spf_decoder_prepare(const SpfCamera* cam, void* zero, uint64_t zero_bytes, void* stream_) {
     int rc = check_camera(cam, true);
     if (rc) return rc;
-    if (!zero || (reinterpret_cast<uintptr_t>(zero) & 15) || (zero_bytes & 15))
+    if (!zero || !aligned<16>({zero}) || (zero_bytes & 15))
         return fail(SPF_E_INVALID, "decoder_prepare: the buffer to clear must be 16-byte aligned and sized");
     SPF_HIP(spf::launch_camera_fwd_zero(*cam, zero, zero_bytes, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
@@ -515,8 +425,7 @@ int spf_camera_backward_partials(const SpfCamera* cam, const float* vpartial, in
     int rc = check_camera(cam, false);
     if (rc) return rc;
     if (!vpartial || !dL_dextrinsics || nblk < 1) return fail(SPF_E_INVALID, "camera_backward_partials: bad argument");
-    if (reinterpret_cast<uintptr_t>(vpartial) & 15)
-        return fail(SPF_E_INVALID, "camera_backward_partials: vpartial must be 16-byte aligned");
+    if (!aligned<16>({vpartial})) return fail(SPF_E_INVALID, "camera_backward_partials: vpartial must be 16-byte aligned");
     SPF_HIP(spf::launch_camera_bwd_reduce(*cam, vpartial, nblk, dL_dextrinsics, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
@@ -701,8 +610,7 @@ int spf_adapter_backward(const float* raw, int64_t raw_stride, int64_t N, int32_
     if (raw_stride < 7 + 3 * (int64_t)K) return fail(SPF_E_INVALID, "adapter: raw_stride %lld is below the %d channels of a row", (long long)raw_stride, 7 + 3 * K);
     if (split && K != 25) return fail(SPF_E_INVALID, "adapter: the band-split layout is the 16 + 9 split of K = 25 (got K = %d)", K);
     if (!split && dL_dharmonics_high) return fail(SPF_E_INVALID, "adapter: dL_dharmonics_high without split");
-    if (dL_drotations && (reinterpret_cast<uintptr_t>(dL_drotations) & 15))
-        return fail(SPF_E_INVALID, "adapter: dL_drotations must be 16-byte aligned");
+    if (!aligned<16>({dL_drotations})) return fail(SPF_E_INVALID, "adapter: dL_drotations must be 16-byte aligned");
     if (N == 0) return SPF_OK;
     SPF_HIP(spf::launch_adapter_bwd(raw, raw_stride, N, K, sh_mask, eps, dL_dscales, dL_drotations, dL_dharmonics,
                                     dL_dharmonics_high, split ? 1 : 0, dL_draw, static_cast<hipStream_t>(stream_)));
@@ -715,8 +623,7 @@ int spf_mse_forward(const float* prediction, const float* image, int64_t n, floa
                     float* loss, void* stream_) {
     if (!prediction || !image || !partial || !loss) return fail(SPF_E_INVALID, "mse: null pointer");
     if (n <= 0) return fail(SPF_E_INVALID, "mse: n must be positive (got %lld)", (long long)n);
-    if ((reinterpret_cast<uintptr_t>(prediction) | reinterpret_cast<uintptr_t>(image)) & 15)
-        return fail(SPF_E_INVALID, "mse: prediction / image must be 16-byte aligned");
+    if (!aligned<16>({prediction, image})) return fail(SPF_E_INVALID, "mse: prediction / image must be 16-byte aligned");
     SPF_HIP(spf::launch_mse_fwd(prediction, image, n, weight / (float)n, partial, loss, 0.f, nullptr,
                                 static_cast<hipStream_t>(stream_)));
     return SPF_OK;
@@ -726,9 +633,7 @@ int spf_mse_forward_grad(const float* prediction, const float* image, int64_t n,
                          float* loss, float* dL_dprediction_unit, void* stream_) {
     if (!prediction || !image || !partial || !loss || !dL_dprediction_unit) return fail(SPF_E_INVALID, "mse: null pointer");
     if (n <= 0) return fail(SPF_E_INVALID, "mse: n must be positive (got %lld)", (long long)n);
-    if ((reinterpret_cast<uintptr_t>(prediction) | reinterpret_cast<uintptr_t>(image) |
-         reinterpret_cast<uintptr_t>(dL_dprediction_unit)) & 15)
-        return fail(SPF_E_INVALID, "mse: tensors must be 16-byte aligned");
+    if (!aligned<16>({prediction, image, dL_dprediction_unit})) return fail(SPF_E_INVALID, "mse: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_mse_fwd(prediction, image, n, weight / (float)n, partial, loss, 2.0f * weight / (float)n,
                                 dL_dprediction_unit, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
@@ -737,7 +642,7 @@ int spf_mse_forward_grad(const float* prediction, const float* image, int64_t n,
 int spf_mse_scale_grad(float* dL_dprediction, int64_t n, const float* dL_dloss, void* stream_) {
     if (!dL_dprediction || !dL_dloss) return fail(SPF_E_INVALID, "mse: null pointer");
     if (n <= 0) return fail(SPF_E_INVALID, "mse: n must be positive (got %lld)", (long long)n);
-    if (reinterpret_cast<uintptr_t>(dL_dprediction) & 15) return fail(SPF_E_INVALID, "mse: tensors must be 16-byte aligned");
+    if (!aligned<16>({dL_dprediction})) return fail(SPF_E_INVALID, "mse: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_mse_scale(dL_dprediction, n, dL_dloss, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
@@ -746,9 +651,7 @@ int spf_mse_backward(const float* prediction, const float* image, int64_t n, flo
                      float* dL_dprediction, void* stream_) {
     if (!prediction || !image || !dL_dloss || !dL_dprediction) return fail(SPF_E_INVALID, "mse: null pointer");
     if (n <= 0) return fail(SPF_E_INVALID, "mse: n must be positive (got %lld)", (long long)n);
-    if ((reinterpret_cast<uintptr_t>(prediction) | reinterpret_cast<uintptr_t>(image) |
-         reinterpret_cast<uintptr_t>(dL_dprediction)) & 15)
-        return fail(SPF_E_INVALID, "mse: tensors must be 16-byte aligned");
+    if (!aligned<16>({prediction, image, dL_dprediction})) return fail(SPF_E_INVALID, "mse: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_mse_bwd(prediction, image, n, 2.0f * weight / (float)n, dL_dloss, dL_dprediction,
                                 static_cast<hipStream_t>(stream_)));
     return SPF_OK;
@@ -778,9 +681,7 @@ static int check_regr3d(const SpfRegr3d* a) {
     if (a->stride_gt1 < 0 || a->stride_gt2 < 0 || a->stride_pr1 < 0 || a->stride_pr2 < 0)
         return fail(SPF_E_INVALID, "regr3d: negative batch strides are not supported");
     if (a->has_dist_clip && a->dist_clip != a->dist_clip) return fail(SPF_E_INVALID, "regr3d: dist_clip is NaN");
-    if ((reinterpret_cast<uintptr_t>(a->gt_pts1) | reinterpret_cast<uintptr_t>(a->gt_pts2) |
-         reinterpret_cast<uintptr_t>(a->pr_pts1) | reinterpret_cast<uintptr_t>(a->pr_pts2) |
-         reinterpret_cast<uintptr_t>(a->conf1) | reinterpret_cast<uintptr_t>(a->conf2)) & 3)
+    if (!aligned<4>({a->gt_pts1, a->gt_pts2, a->pr_pts1, a->pr_pts2, a->conf1, a->conf2}))
         return fail(SPF_E_INVALID, "regr3d: tensors must be 4-byte aligned");
     return SPF_OK;
 }
@@ -788,9 +689,8 @@ static int check_regr3d(const SpfRegr3d* a) {
 int spf_regr3d_forward(const SpfRegr3d* args, void* scratch, float* stats, float* loss, void* stream_) {
     if (int rc = check_regr3d(args)) return rc;
     if (!scratch || !stats || !loss) return fail(SPF_E_INVALID, "regr3d: null pointer");
-    if (reinterpret_cast<uintptr_t>(scratch) & 15) return fail(SPF_E_INVALID, "regr3d: scratch must be 16-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(stats) | reinterpret_cast<uintptr_t>(loss)) & 3)
-        return fail(SPF_E_INVALID, "regr3d: stats and loss must be 4-byte aligned");
+    if (!aligned<16>({scratch})) return fail(SPF_E_INVALID, "regr3d: scratch must be 16-byte aligned");
+    if (!aligned<4>({stats, loss})) return fail(SPF_E_INVALID, "regr3d: stats and loss must be 4-byte aligned");
     SPF_HIP(spf::launch_regr3d_fwd(*args, scratch, stats, loss, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
@@ -800,18 +700,11 @@ int spf_regr3d_backward(const SpfRegr3d* args, const void* scratch, const float*
     if (int rc = check_regr3d(args)) return rc;
     if (!scratch || !stats || !dL_dloss) return fail(SPF_E_INVALID, "regr3d: null pointer");
     if (!d_pr1 && !d_pr2) return fail(SPF_E_INVALID, "regr3d: no gradient requested");
-    if (reinterpret_cast<uintptr_t>(scratch) & 15) return fail(SPF_E_INVALID, "regr3d: scratch must be 16-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d_pr1) | reinterpret_cast<uintptr_t>(d_pr2) | reinterpret_cast<uintptr_t>(stats) |
-         reinterpret_cast<uintptr_t>(dL_dloss)) & 3)
+    if (!aligned<16>({scratch})) return fail(SPF_E_INVALID, "regr3d: scratch must be 16-byte aligned");
+    if (!aligned<4>({d_pr1, d_pr2, stats, dL_dloss}))
         return fail(SPF_E_INVALID, "regr3d: gradients, stats and dL_dloss must be 4-byte aligned");
     SPF_HIP(spf::launch_regr3d_bwd(*args, scratch, stats, dL_dloss, d_pr1, d_pr2, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
-}
-
-static bool aligned4(std::initializer_list<const void*> ps) {
-    uintptr_t x = 0;
-    for (const void* p : ps) x |= reinterpret_cast<uintptr_t>(p);
-    return (x & 3) == 0;
 }
 
 static int check_pose_compose(const float* enc, int64_t stride_b, int64_t stride_v, int32_t b, int32_t v, int32_t cv,
@@ -831,7 +724,7 @@ int spf_pose_compose_forward(const float* enc, int64_t stride_b, int64_t stride_
                              void* stream_) {
     if (int rc = check_pose_compose(enc, stride_b, stride_v, b, v, cv, encoding)) return rc;
     if (!poses) return fail(SPF_E_INVALID, "pose_compose: poses is null");
-    if (!aligned4({enc, poses})) return fail(SPF_E_INVALID, "pose_compose: tensors must be 4-byte aligned");
+    if (!aligned<4>({enc, poses})) return fail(SPF_E_INVALID, "pose_compose: tensors must be 4-byte aligned");
     SPF_HIP(spf::launch_pose_compose_fwd(enc, stride_b, stride_v, b, v, cv, encoding, make_baseline_1 != 0,
                                          make_relative != 0, poses, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
@@ -842,7 +735,7 @@ int spf_pose_compose_backward(const float* enc, int64_t stride_b, int64_t stride
                               float* dL_denc, void* stream_) {
     if (int rc = check_pose_compose(enc, stride_b, stride_v, b, v, cv, encoding)) return rc;
     if (!dL_dposes || !dL_denc) return fail(SPF_E_INVALID, "pose_compose: null gradient pointer");
-    if (!aligned4({enc, dL_dposes, dL_denc})) return fail(SPF_E_INVALID, "pose_compose: tensors must be 4-byte aligned");
+    if (!aligned<4>({enc, dL_dposes, dL_denc})) return fail(SPF_E_INVALID, "pose_compose: tensors must be 4-byte aligned");
     SPF_HIP(spf::launch_pose_compose_bwd(enc, stride_b, stride_v, b, v, cv, encoding, make_baseline_1 != 0,
                                          make_relative != 0, dL_dposes, dL_denc, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
@@ -870,7 +763,7 @@ int spf_depth_project_forward(const float* pts, int64_t stride_img, const float*
                               float* depth, void* stream_) {
     if (int rc = check_depth(pts, stride_img, poses, N, n)) return rc;
     if (!depth) return fail(SPF_E_INVALID, "depth_project: depth is null");
-    if (!aligned4({pts, poses, depth})) return fail(SPF_E_INVALID, "depth_project: tensors must be 4-byte aligned");
+    if (!aligned<4>({pts, poses, depth})) return fail(SPF_E_INVALID, "depth_project: tensors must be 4-byte aligned");
     SPF_HIP(spf::launch_depth_fwd(pts, stride_img, poses, N, n, depth, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
@@ -883,10 +776,9 @@ int spf_depth_project_backward(const float* pts, int64_t stride_img, const float
     if (!dL_dpts && !dL_dposes) return fail(SPF_E_INVALID, "depth_project: no gradient requested");
     if ((dL_dposes != nullptr) != (gpartial != nullptr))
         return fail(SPF_E_INVALID, "depth_project: dL_dposes and gpartial go together");
-    if (!aligned4({pts, poses, dL_ddepth, dL_dpts, dL_dposes}))
+    if (!aligned<4>({pts, poses, dL_ddepth, dL_dpts, dL_dposes}))
         return fail(SPF_E_INVALID, "depth_project: tensors must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(gpartial) & 15)
-        return fail(SPF_E_INVALID, "depth_project: gpartial must be 16-byte aligned");
+    if (!aligned<16>({gpartial})) return fail(SPF_E_INVALID, "depth_project: gpartial must be 16-byte aligned");
     SPF_HIP(spf::launch_depth_bwd(pts, stride_img, poses, N, n, dL_ddepth, dL_dpts, gpartial, dL_dposes,
                                   static_cast<hipStream_t>(stream_)));
     return SPF_OK;
@@ -895,7 +787,7 @@ int spf_depth_project_backward(const float* pts, int64_t stride_img, const float
 int spf_pose_error(const float* pred, const float* gt, int32_t N, float* errors, float* means, void* stream_) {
     if (!pred || !gt || !errors || !means) return fail(SPF_E_INVALID, "pose_error: null pointer");
     if (N < 1) return fail(SPF_E_INVALID, "pose_error: N must be positive (got %d)", N);
-    if (!aligned4({pred, gt, errors, means})) return fail(SPF_E_INVALID, "pose_error: tensors must be 4-byte aligned");
+    if (!aligned<4>({pred, gt, errors, means})) return fail(SPF_E_INVALID, "pose_error: tensors must be 4-byte aligned");
     SPF_HIP(spf::launch_pose_error(pred, gt, N, errors, means, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
@@ -916,7 +808,7 @@ int spf_focal_estimate(const float* pts, int64_t stride_scene, int64_t stride_ro
     if (!focal_sizes_ok(B, H, W)) return fail(SPF_E_INVALID, "focal_estimate: %d x %d x %d points is too large", B, H, W);
     if (stride_scene < 0 || stride_row < 0) return fail(SPF_E_INVALID, "focal_estimate: negative strides are not supported");
     if (pp_stride != 0 && pp_stride != 2) return fail(SPF_E_INVALID, "focal_estimate: pp_stride must be 0 or 2");
-    if (!aligned4({pts, pp, focal, intrinsics})) return fail(SPF_E_INVALID, "focal_estimate: tensors must be 4-byte aligned");
+    if (!aligned<4>({pts, pp, focal, intrinsics})) return fail(SPF_E_INVALID, "focal_estimate: tensors must be 4-byte aligned");
     // focal_base as the reference forms it (a Python float), the clip bounds as torch.clip receives them
     const double base = (double)(H > W ? H : W) / (2.0 * tan(30.0 * 3.14159265358979323846 / 180.0));
     SPF_HIP(spf::launch_focal(pts, stride_scene, stride_row, B, H, W, pp, pp_stride, (float)base,
@@ -944,16 +836,14 @@ static int check_reproj(const SpfReproj* a) {
     if (a->stride_b < 0 || a->stride_v < 0)
         return fail(SPF_E_INVALID, "reproj: negative pts3d strides (%lld, %lld) are not supported",
                     (long long)a->stride_b, (long long)a->stride_v);
-    if ((reinterpret_cast<uintptr_t>(a->pts3d) | reinterpret_cast<uintptr_t>(a->poses) |
-         reinterpret_cast<uintptr_t>(a->intrinsics)) & 3)
-        return fail(SPF_E_INVALID, "reproj: tensors must be 4-byte aligned");
+    if (!aligned<4>({a->pts3d, a->poses, a->intrinsics})) return fail(SPF_E_INVALID, "reproj: tensors must be 4-byte aligned");
     return SPF_OK;
 }
 
 int spf_reproj_forward(const SpfReproj* args, void* partial, float* loss, float* scale, void* stream_) {
     if (int rc = check_reproj(args)) return rc;
     if (!partial || !loss || !scale) return fail(SPF_E_INVALID, "reproj: null pointer");
-    if (reinterpret_cast<uintptr_t>(partial) & 3) return fail(SPF_E_INVALID, "reproj: partial must be 4-byte aligned");
+    if (!aligned<4>({partial})) return fail(SPF_E_INVALID, "reproj: partial must be 4-byte aligned");
     SPF_HIP(spf::launch_reproj_fwd(*args, partial, loss, scale, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
@@ -966,10 +856,8 @@ int spf_reproj_backward(const SpfReproj* args, const float* scale, const float* 
     if (!dL_dpts3d && !cam) return fail(SPF_E_INVALID, "reproj: no gradient requested");
     if (cam != (gpartial != nullptr))
         return fail(SPF_E_INVALID, "reproj: gpartial is needed exactly when dL_dposes or dL_dintrinsics is given");
-    if (gpartial && (reinterpret_cast<uintptr_t>(gpartial) & 15))
-        return fail(SPF_E_INVALID, "reproj: gpartial must be 16-byte aligned");
-    if (dL_dpts3d && (reinterpret_cast<uintptr_t>(dL_dpts3d) & 3))
-        return fail(SPF_E_INVALID, "reproj: dL_dpts3d must be 4-byte aligned");
+    if (!aligned<16>({gpartial})) return fail(SPF_E_INVALID, "reproj: gpartial must be 16-byte aligned");
+    if (!aligned<4>({dL_dpts3d})) return fail(SPF_E_INVALID, "reproj: dL_dpts3d must be 4-byte aligned");
     SPF_HIP(spf::launch_reproj_bwd(*args, scale, dL_dloss, dL_dpts3d, gpartial, dL_dposes, dL_dintrinsics,
                                    static_cast<hipStream_t>(stream_)));
     return SPF_OK;
@@ -996,8 +884,7 @@ static int check_ssim(const SpfSsim* a) {
     if (const char* e = ssim_size_error(a->N, a->C, a->H, a->W, a->ws))
         return fail(SPF_E_INVALID, "%s (got N %d C %d H %d W %d ws %d)", e, a->N, a->C, a->H, a->W, a->ws);
     if (!a->X || !a->Y) return fail(SPF_E_INVALID, "ssim: null pointer");
-    if ((reinterpret_cast<uintptr_t>(a->X) | reinterpret_cast<uintptr_t>(a->Y)) & 3)
-        return fail(SPF_E_INVALID, "ssim: tensors must be 4-byte aligned");
+    if (!aligned<4>({a->X, a->Y})) return fail(SPF_E_INVALID, "ssim: tensors must be 4-byte aligned");
     return SPF_OK;
 }
 
@@ -1013,8 +900,7 @@ int spf_ssim_backward(const SpfSsim* args, const float* plane_mean, const float*
     if (int rc = check_ssim(args)) return rc;
     if (!plane_mean || !dL_dout) return fail(SPF_E_INVALID, "ssim: null pointer");
     if (!dL_dX && !dL_dY) return fail(SPF_E_INVALID, "ssim: no gradient requested");
-    if ((reinterpret_cast<uintptr_t>(dL_dX) | reinterpret_cast<uintptr_t>(dL_dY)) & 3)
-        return fail(SPF_E_INVALID, "ssim: tensors must be 4-byte aligned");
+    if (!aligned<4>({dL_dX, dL_dY})) return fail(SPF_E_INVALID, "ssim: tensors must be 4-byte aligned");
     SPF_HIP(spf::launch_ssim_bwd(*args, plane_mean, dL_dout, dL_dX, dL_dY, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
@@ -1061,7 +947,7 @@ int spf_rope2d_pair(void* tokens, void* tokens2, const int64_t* positions, int32
 
 // arguments of an attention call: 0, or the message of the first one that is wrong
 static bool attn_rows_aligned(const void* p, const int64_t* stride, int esize) {
-    if (reinterpret_cast<uintptr_t>(p) % 16 != 0) return false;
+    if (!aligned<16>({p})) return false;
     for (int i = 0; i < 3; ++i)
         if ((stride[i] * esize) % 16 != 0) return false;
     return true;
@@ -1085,7 +971,7 @@ static const char* attn_args_error(const SpfAttn* a) {
 static const char* attn_forward_error(const SpfAttn* a, const void* out, const float* lse) {
     if (const char* e = attn_args_error(a)) return e;
     if (!out || !lse) return "attention: out / lse is null";
-    if (reinterpret_cast<uintptr_t>(out) % 16 != 0) return "attention: rows of out must be 16-byte aligned";
+    if (!aligned<16>({out})) return "attention: rows of out must be 16-byte aligned";
     return nullptr;
 }
 // a backward call; ext: the extras with a mask or norm parameters, or null (its outputs are checked in their place)
@@ -1098,8 +984,7 @@ static const char* attn_backward_error(const SpfAttn* a, const SpfAttnGrads* g, 
     if (ext && ext->q_weight && (!ext->dq_weight || !ext->dq_bias || !ext->dk_weight || !ext->dk_bias || !ext->partials))
         return "attention: dq_weight / dq_bias / dk_weight / dk_bias / partials is null";
     const int es = a->dtype == 0 ? 4 : 2;
-    if (reinterpret_cast<uintptr_t>(out) % 16 != 0 || reinterpret_cast<uintptr_t>(dout) % 16 != 0)
-        return "attention: rows of out and dout must be 16-byte aligned";
+    if (!aligned<16>({out, dout})) return "attention: rows of out and dout must be 16-byte aligned";
     if (!attn_rows_aligned(g->dq, g->dq_stride, es) || !attn_rows_aligned(g->dk, g->dk_stride, es) ||
         !attn_rows_aligned(g->dv, g->dv_stride, es))
         return "attention: rows of dq, dk and dv must be 16-byte aligned";
@@ -1114,7 +999,7 @@ static const char* attn_ext_error(const SpfAttnExt* e) {
         if (e->mask_stride[3] != 1) return "attention: the mask's key stride must be 1";
         for (int i = 0; i < 3; ++i)
             if (e->mask_stride[i] < 0) return "attention: mask strides must not be negative";
-        if (e->mask_dtype == 0 && reinterpret_cast<uintptr_t>(e->mask) % 4 != 0) return "attention: a float32 mask must be 4-byte aligned";
+        if (e->mask_dtype == 0 && !aligned<4>({e->mask})) return "attention: a float32 mask must be 4-byte aligned";
     }
     const int given = (e->q_weight != nullptr) + (e->q_bias != nullptr) + (e->k_weight != nullptr) + (e->k_bias != nullptr);
     if (given != 0 && given != 4) return "attention: q_weight, q_bias, k_weight and k_bias must all be given or all be null";
@@ -1232,8 +1117,6 @@ int64_t spf_lpips_workspace_bytes(int32_t n_with_grad, int32_t n_total, int32_t 
     return spf::lpips_workspace_bytes(n_with_grad, n_total, h, w);
 }
 
-static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
-
 static int check_lpips(const SpfLpips* a, bool first_only) {
     if (!a) return fail(SPF_E_INVALID, "lpips: args is null");
     if (const char* e = lpips_size_error(a->N, a->H, a->W))
@@ -1242,18 +1125,17 @@ static int check_lpips(const SpfLpips* a, bool first_only) {
     const int64_t img = (int64_t)3 * a->H * a->W;
     if (a->stride0 < img || (!first_only && a->stride1 < img))
         return fail(SPF_E_INVALID, "lpips: image stride shorter than 3 H W");
-    if ((reinterpret_cast<uintptr_t>(a->in0) | reinterpret_cast<uintptr_t>(a->in1)) & 3)
-        return fail(SPF_E_INVALID, "lpips: images must be 4-byte aligned");
+    if (!aligned<4>({a->in0, a->in1})) return fail(SPF_E_INVALID, "lpips: images must be 4-byte aligned");
     if (!a->wfwd || !a->wbwd || !a->bias || !a->shift_scale || (!first_only && !a->lin))
         return fail(SPF_E_INVALID, "lpips: null weight pointer");
-    if (misaligned16(a->wfwd) || misaligned16(a->wbwd)) return fail(SPF_E_INVALID, "lpips: weight packs must be 16-byte aligned");
+    if (!aligned<16>({a->wfwd, a->wbwd})) return fail(SPF_E_INVALID, "lpips: weight packs must be 16-byte aligned");
     return SPF_OK;
 }
 
 int spf_lpips_forward(const SpfLpips* args, void* workspace, float* out, float* mean, void* stream_) {
     if (int rc = check_lpips(args, false)) return rc;
     if (!workspace || !out) return fail(SPF_E_INVALID, "lpips: null pointer");
-    if (misaligned16(workspace)) return fail(SPF_E_INVALID, "lpips: workspace must be 16-byte aligned");
+    if (!aligned<16>({workspace})) return fail(SPF_E_INVALID, "lpips: workspace must be 16-byte aligned");
     SPF_HIP(spf::launch_lpips_fwd(*args, static_cast<float*>(workspace), out, mean, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
@@ -1262,7 +1144,7 @@ int spf_lpips_backward(const SpfLpips* args, void* workspace, const float* dL_do
                        float* d_in0, float* d_in1, void* stream_) {
     if (int rc = check_lpips(args, false)) return rc;
     if (!workspace || !dL_dout) return fail(SPF_E_INVALID, "lpips: null pointer");
-    if (misaligned16(workspace)) return fail(SPF_E_INVALID, "lpips: workspace must be 16-byte aligned");
+    if (!aligned<16>({workspace})) return fail(SPF_E_INVALID, "lpips: workspace must be 16-byte aligned");
     if (!d_in0 && !d_in1) return fail(SPF_E_INVALID, "lpips: no gradient requested");
     SPF_HIP(spf::launch_lpips_bwd(*args, static_cast<float*>(workspace), dL_dout, upstream_is_mean ? 1 : 0, d_in0, d_in1,
                                   static_cast<hipStream_t>(stream_)));
@@ -1281,8 +1163,7 @@ int spf_lpips_conv3x3(const float* in, const float* mask, const float* wpack, co
     if (int rc = check_lpips_map("lpips conv3x3", n, h, w, cin, 16)) return rc;
     if (cout < 64 || cout % 64) return fail(SPF_E_INVALID, "lpips conv3x3: cout %d is not a multiple of 64", cout);
     if (!in || !wpack || !out) return fail(SPF_E_INVALID, "lpips conv3x3: null pointer");
-    if (misaligned16(in) || misaligned16(mask) || misaligned16(wpack) || misaligned16(out))
-        return fail(SPF_E_INVALID, "lpips conv3x3: tensors must be 16-byte aligned");
+    if (!aligned<16>({in, mask, wpack, out})) return fail(SPF_E_INVALID, "lpips conv3x3: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_lpips_conv(in, mask, wpack, bias, out, n, h, w, cin, cout, relu ? 1 : 0,
                                    static_cast<hipStream_t>(stream_)));
     return SPF_OK;
@@ -1290,7 +1171,7 @@ int spf_lpips_conv3x3(const float* in, const float* mask, const float* wpack, co
 
 int spf_lpips_conv1_forward(const SpfLpips* args, float* out, void* stream_) {
     if (int rc = check_lpips(args, true)) return rc;
-    if (!out || misaligned16(out)) return fail(SPF_E_INVALID, "lpips conv1: out is null or not 16-byte aligned");
+    if (!out || !aligned<16>({out})) return fail(SPF_E_INVALID, "lpips conv1: out is null or not 16-byte aligned");
     SPF_HIP(spf::launch_lpips_conv1(*args, args->N, out, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
@@ -1298,14 +1179,14 @@ int spf_lpips_conv1_forward(const SpfLpips* args, float* out, void* stream_) {
 int spf_lpips_conv1_backward(const SpfLpips* args, const float* g, const float* act, float* d_in0, void* stream_) {
     if (int rc = check_lpips(args, true)) return rc;
     if (!g || !act || !d_in0) return fail(SPF_E_INVALID, "lpips conv1 backward: null pointer");
-    if (misaligned16(g) || misaligned16(act)) return fail(SPF_E_INVALID, "lpips conv1 backward: tensors must be 16-byte aligned");
+    if (!aligned<16>({g, act})) return fail(SPF_E_INVALID, "lpips conv1 backward: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_lpips_conv1_bwd(*args, g, act, args->N, d_in0, args->N, nullptr, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
 
 int spf_lpips_pool_forward(const float* in, float* out, int32_t n, int32_t h, int32_t w, int32_t c, void* stream_) {
     if (int rc = check_lpips_map("lpips pool", n, h, w, c, 4)) return rc;
-    if (!in || !out || misaligned16(in) || misaligned16(out))
+    if (!in || !out || !aligned<16>({in, out}))
         return fail(SPF_E_INVALID, "lpips pool: null or not 16-byte aligned pointer");
     SPF_HIP(spf::launch_lpips_pool(in, out, n, h, w, c, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
@@ -1314,7 +1195,7 @@ int spf_lpips_pool_forward(const float* in, float* out, int32_t n, int32_t h, in
 int spf_lpips_pool_backward(const float* gp, const float* act, float* inout, int32_t n, int32_t h, int32_t w, int32_t c,
                             void* stream_) {
     if (int rc = check_lpips_map("lpips pool backward", n, h, w, c, 4)) return rc;
-    if (!gp || !act || !inout || misaligned16(gp) || misaligned16(act) || misaligned16(inout))
+    if (!gp || !act || !inout || !aligned<16>({gp, act, inout}))
         return fail(SPF_E_INVALID, "lpips pool backward: null or not 16-byte aligned pointer");
     SPF_HIP(spf::launch_lpips_pool_bwd(gp, act, inout, n, h, w, c, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
@@ -1365,7 +1246,7 @@ int64_t spf_optim_plan(const SpfOptimTensor* table, int32_t T, int32_t num_group
     for (int32_t t = 0; t < T; ++t) {
         const SpfOptimTensor& e = table[t];
         if (!e.param || !e.exp_avg || !e.exp_avg_sq) return fail(SPF_E_INVALID, "optim: tensor %d has a null pointer", t);
-        if (((uintptr_t)e.param | (uintptr_t)e.exp_avg | (uintptr_t)e.exp_avg_sq) & 3)
+        if (!aligned<4>({e.param, e.exp_avg, e.exp_avg_sq}))
             return fail(SPF_E_INVALID, "optim: tensor %d is not 4-byte aligned", t);
         if (e.numel <= 0) return fail(SPF_E_INVALID, "optim: tensor %d has numel %lld; it must be positive", t, (long long)e.numel);
         if (e.group < 0 || e.group >= num_groups)
@@ -1389,7 +1270,7 @@ int spf_optim_step(const SpfOptim* o, const SpfOptimHyper* hp, void* stream_) {
     if (o->chunks < o->T) return fail(SPF_E_INVALID, "optim: chunks = %lld is below T = %d", (long long)o->chunks, o->T);
     if (!o->chunk_start || !o->grads || !o->guard_order || !o->step || !o->scratch || !o->report)
         return fail(SPF_E_INVALID, "optim: null pointer");
-    if (((uintptr_t)o->scratch | (uintptr_t)o->report) & 15)
+    if (!aligned<16>({o->scratch, o->report}))
         return fail(SPF_E_INVALID, "optim: scratch and report must be 16-byte aligned");
     if (hp->num_groups < 1 || hp->num_groups > SPF_OPTIM_MAX_GROUPS)
         return fail(SPF_E_INVALID, "optim: %d parameter groups; 1 .. %d are supported", hp->num_groups, SPF_OPTIM_MAX_GROUPS);
@@ -1413,11 +1294,6 @@ static int block_sizes_fail(const char* what, int64_t rows, int32_t C) {
     return fail(SPF_E_INVALID, "%s: rows must be 1 .. 2^30 and C a multiple of 4 in 4 .. %d (got rows = %lld, C = %d)", what,
                 SPF_BLOCK_MAX_C, (long long)rows, C);
 }
-static bool block_aligned(std::initializer_list<const void*> ps) {
-    for (const void* p : ps)
-        if (reinterpret_cast<uintptr_t>(p) & 15) return false;
-    return true;
-}
 // one addressed operand of SpfBlockNorm: the group size and the two strides
 static bool block_rows_ok(int64_t inner, int64_t stride, int64_t outer_stride) {
     return inner >= 1 && inner <= ((int64_t)1 << 30) && stride >= 0 && outer_stride >= 0 && stride % 4 == 0 &&
@@ -1432,7 +1308,7 @@ static int block_norm_check(const char* what, const SpfBlockNorm* a, bool backwa
     if (!(a->eps >= 0.f)) return fail(SPF_E_INVALID, "%s: eps must be >= 0", what);
     if (!block_rows_ok(a->x_inner, a->x_stride, a->x_outer_stride) || (a->r && !block_rows_ok(a->r_inner, a->r_stride, a->r_outer_stride)))
         return fail(SPF_E_INVALID, "%s: group sizes must be >= 1 and strides non-negative multiples of 4 floats", what);
-    if (!block_aligned({a->x, a->r, a->gamma, a->weight, a->bias}))
+    if (!aligned<16>({a->x, a->r, a->gamma, a->weight, a->bias}))
         return fail(SPF_E_INVALID, "%s: tensors must be 16-byte aligned", what);
     return SPF_OK;
 }
@@ -1445,7 +1321,7 @@ int64_t spf_block_partial_blocks(int64_t rows, int32_t C, int32_t gelu) {
 int spf_block_add_norm_forward(const SpfBlockNorm* a, float* s, float* y, float* stats, void* stream_) {
     if (const int rc = block_norm_check("block_add_norm_forward", a, false)) return rc;
     if (!y || !stats || (a->r && !s)) return fail(SPF_E_INVALID, "block_add_norm_forward: null output pointer");
-    if (!block_aligned({s, y, stats})) return fail(SPF_E_INVALID, "block_add_norm_forward: tensors must be 16-byte aligned");
+    if (!aligned<16>({s, y, stats})) return fail(SPF_E_INVALID, "block_add_norm_forward: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_block_norm_fwd(*a, s, y, stats, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
@@ -1456,7 +1332,7 @@ int spf_block_add_norm_backward(const SpfBlockNorm* a, const float* dy, const fl
     if (!dy || !stats || !dx || !partials || !dparams) return fail(SPF_E_INVALID, "block_add_norm_backward: null pointer");
     if ((a->gamma != nullptr) != (dr != nullptr))
         return fail(SPF_E_INVALID, "block_add_norm_backward: dr is written with gamma only (without it dr is dx)");
-    if (!block_aligned({dy, ds, stats, dx, dr, partials, dparams}))
+    if (!aligned<16>({dy, ds, stats, dx, dr, partials, dparams}))
         return fail(SPF_E_INVALID, "block_add_norm_backward: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_block_norm_bwd(*a, dy, ds, stats, dx, dr, partials, dparams, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
@@ -1465,7 +1341,7 @@ int spf_block_add_norm_backward(const SpfBlockNorm* a, const float* dy, const fl
 int spf_block_bias_gelu_forward(const float* u, const float* bias, int64_t rows, int32_t C, float* h, void* stream_) {
     if (!block_sizes_ok(rows, C)) return block_sizes_fail("block_bias_gelu_forward", rows, C);
     if (!u || !h) return fail(SPF_E_INVALID, "block_bias_gelu_forward: null pointer");
-    if (!block_aligned({u, bias, h})) return fail(SPF_E_INVALID, "block_bias_gelu_forward: tensors must be 16-byte aligned");
+    if (!aligned<16>({u, bias, h})) return fail(SPF_E_INVALID, "block_bias_gelu_forward: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_block_gelu_fwd(u, bias, rows, C, h, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
@@ -1476,7 +1352,7 @@ int spf_block_bias_gelu_backward(const float* u, const float* bias, const float*
     if (!u || !dh || !du) return fail(SPF_E_INVALID, "block_bias_gelu_backward: null pointer");
     if (bias ? (!partials || !dbias) : (partials || dbias))
         return fail(SPF_E_INVALID, "block_bias_gelu_backward: partials and dbias are given with a bias and only then");
-    if (!block_aligned({u, bias, dh, du, partials, dbias}))
+    if (!aligned<16>({u, bias, dh, du, partials, dbias}))
         return fail(SPF_E_INVALID, "block_bias_gelu_backward: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_block_gelu_bwd(u, bias, dh, rows, C, du, partials, dbias, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
@@ -1502,7 +1378,7 @@ int spf_dpt_upsample2x_forward(const float* x, const float* skip, int32_t relu_s
     if (const int rc = dpt_up2_check("dpt_upsample2x_forward", planes, h, w)) return rc;
     if (!x || !out) return fail(SPF_E_INVALID, "dpt_upsample2x_forward: null pointer (x or out)");
     if (relu_skip && !skip) return fail(SPF_E_INVALID, "dpt_upsample2x_forward: relu_skip is set without skip");
-    if (!block_aligned({x, skip, out})) return fail(SPF_E_INVALID, "dpt_upsample2x_forward: tensors must be 16-byte aligned");
+    if (!aligned<16>({x, skip, out})) return fail(SPF_E_INVALID, "dpt_upsample2x_forward: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_dpt_up2_fwd(x, skip, relu_skip != 0, planes, h, w, out, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
@@ -1515,7 +1391,7 @@ int spf_dpt_upsample2x_backward(const float* dy, const float* skip, int64_t plan
     if ((skip != nullptr) != (dskip != nullptr))
         return fail(SPF_E_INVALID, "dpt_upsample2x_backward: skip and dskip are given with the ReLU flag and only then "
                     "(without it dskip is dy)");
-    if (!block_aligned({dy, skip, dx, dskip})) return fail(SPF_E_INVALID, "dpt_upsample2x_backward: tensors must be 16-byte aligned");
+    if (!aligned<16>({dy, skip, dx, dskip})) return fail(SPF_E_INVALID, "dpt_upsample2x_backward: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_dpt_up2_bwd(dy, skip, planes, h, w, dx, dskip, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
@@ -1532,7 +1408,7 @@ int spf_dpt_add_relu_forward(const float* a, const float* b, const float* c, int
     if (c && !b) return fail(SPF_E_INVALID, "dpt_add_relu_forward: c is given without b");
     if ((b != nullptr) != (s != nullptr))
         return fail(SPF_E_INVALID, "dpt_add_relu_forward: s is written with a second addend and only then (without one s is a)");
-    if (!block_aligned({a, b, c, s, y})) return fail(SPF_E_INVALID, "dpt_add_relu_forward: tensors must be 16-byte aligned");
+    if (!aligned<16>({a, b, c, s, y})) return fail(SPF_E_INVALID, "dpt_add_relu_forward: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_dpt_add_relu_fwd(a, b, c, n, s, y, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
@@ -1540,7 +1416,7 @@ int spf_dpt_add_relu_forward(const float* a, const float* b, const float* c, int
 int spf_dpt_add_relu_backward(const float* mask, const float* dy, const float* ds, int64_t n, float* g, void* stream_) {
     if (const int rc = dpt_count_check("dpt_add_relu_backward", n)) return rc;
     if (!mask || !dy || !g) return fail(SPF_E_INVALID, "dpt_add_relu_backward: null pointer (mask, dy or g)");
-    if (!block_aligned({mask, dy, ds, g})) return fail(SPF_E_INVALID, "dpt_add_relu_backward: tensors must be 16-byte aligned");
+    if (!aligned<16>({mask, dy, ds, g})) return fail(SPF_E_INVALID, "dpt_add_relu_backward: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_dpt_add_relu_bwd(mask, dy, ds, n, g, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
 }
@@ -1563,7 +1439,7 @@ int spf_dpt_points_forward(const SpfDptPoints* a, float* pts3d, float* conf, voi
     if (const int rc = dpt_points_check("dpt_points_forward", a)) return rc;
     if (!pts3d || (a->has_conf != 0) != (conf != nullptr))
         return fail(SPF_E_INVALID, "dpt_points_forward: null output pointer (pts3d; conf is given with has_conf and only then)");
-    if (!block_aligned({a->in, pts3d, conf})) return fail(SPF_E_INVALID, "dpt_points_forward: tensors must be 16-byte aligned");
+    if (!aligned<16>({a->in, pts3d, conf})) return fail(SPF_E_INVALID, "dpt_points_forward: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_dpt_points(1, a->in, nullptr, nullptr, a->B, a->HW, a->C, a->has_conf, a->depth_min, a->depth_max,
                                    a->conf_min, a->conf_max, pts3d, conf, nullptr, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
@@ -1573,7 +1449,7 @@ int spf_dpt_points_backward(const SpfDptPoints* a, const float* dpts3d, const fl
     if (const int rc = dpt_points_check("dpt_points_backward", a)) return rc;
     if (!dpts3d || !din || (a->has_conf != 0) != (dconf != nullptr))
         return fail(SPF_E_INVALID, "dpt_points_backward: null pointer (dpts3d, din; dconf is given with has_conf and only then)");
-    if (!block_aligned({a->in, dpts3d, dconf, din})) return fail(SPF_E_INVALID, "dpt_points_backward: tensors must be 16-byte aligned");
+    if (!aligned<16>({a->in, dpts3d, dconf, din})) return fail(SPF_E_INVALID, "dpt_points_backward: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_dpt_points(0, a->in, dpts3d, dconf, a->B, a->HW, a->C, a->has_conf, a->depth_min, a->depth_max,
                                    a->conf_min, a->conf_max, nullptr, nullptr, din, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
@@ -1597,7 +1473,7 @@ static int tail_check(const char* what, const SpfTail* a, bool need_pts) {
     if (!a->sh_mask) return fail(SPF_E_INVALID, "%s: null pointer (sh_mask)", what);
     for (int i = 0; i < a->v; ++i) {
         if (!a->raw[i] || (need_pts && !a->pts[i])) return fail(SPF_E_INVALID, "%s: null pointer (raw or pts of view %d)", what, i);
-        if (!block_aligned({a->raw[i], a->pts[i]})) return fail(SPF_E_INVALID, "%s: tensors must be 16-byte aligned (view %d)", what, i);
+        if (!aligned<16>({a->raw[i], a->pts[i]})) return fail(SPF_E_INVALID, "%s: tensors must be 16-byte aligned (view %d)", what, i);
     }
     return SPF_OK;
 }
@@ -1607,7 +1483,7 @@ int spf_tail_forward(const SpfTail* a, float* means, float* opacities, float* sc
     if (const int rc = tail_check("tail_forward", a, true)) return rc;
     if (!means || !opacities || !scales || !rotations || !harmonics) return fail(SPF_E_INVALID, "tail_forward: null output pointer");
     if (harmonics_high && a->K != 25) return fail(SPF_E_INVALID, "tail_forward: the band-split layout is the 16 + 9 split of K = 25 (got K = %d)", a->K);
-    if (!block_aligned({means, opacities, scales, rotations, harmonics, harmonics_high, a->sh_mask}))
+    if (!aligned<16>({means, opacities, scales, rotations, harmonics, harmonics_high, a->sh_mask}))
         return fail(SPF_E_INVALID, "tail_forward: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_tail_fwd(*a, means, opacities, scales, rotations, harmonics, harmonics_high, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
@@ -1622,9 +1498,9 @@ int spf_tail_backward(const SpfTail* a, const float* dL_dmeans, const float* dL_
     if (!split && dL_dharmonics_high) return fail(SPF_E_INVALID, "tail_backward: dL_dharmonics_high without split");
     for (int i = 0; i < a->v; ++i) {
         if (!g->d_raw[i] || !g->d_pts[i]) return fail(SPF_E_INVALID, "tail_backward: null pointer (d_raw or d_pts of view %d)", i);
-        if (!block_aligned({g->d_raw[i], g->d_pts[i]})) return fail(SPF_E_INVALID, "tail_backward: tensors must be 16-byte aligned (view %d)", i);
+        if (!aligned<16>({g->d_raw[i], g->d_pts[i]})) return fail(SPF_E_INVALID, "tail_backward: tensors must be 16-byte aligned (view %d)", i);
     }
-    if (!block_aligned({dL_dmeans, dL_dopacities, dL_dscales, dL_drotations, dL_dharmonics, dL_dharmonics_high, a->sh_mask}))
+    if (!aligned<16>({dL_dmeans, dL_dopacities, dL_dscales, dL_drotations, dL_dharmonics, dL_dharmonics_high, a->sh_mask}))
         return fail(SPF_E_INVALID, "tail_backward: tensors must be 16-byte aligned");
     SPF_HIP(spf::launch_tail_bwd(*a, *g, dL_dmeans, dL_dopacities, dL_dscales, dL_drotations, dL_dharmonics, dL_dharmonics_high,
                                  split ? 1 : 0, static_cast<hipStream_t>(stream_)));
@@ -1642,7 +1518,7 @@ static int opacity_check(const char* what, const float* logits, int64_t stride, 
 int spf_opacity_forward(const float* logits, int64_t stride, int64_t n, float exponent, float* opacities, void* stream_) {
     if (const int rc = opacity_check("opacity_forward", logits, stride, n, exponent)) return rc;
     if (!opacities) return fail(SPF_E_INVALID, "opacity_forward: null pointer (opacities)");
-    if (!aligned4({logits, opacities})) return fail(SPF_E_INVALID, "opacity_forward: tensors must be 4-byte aligned");
+    if (!aligned<4>({logits, opacities})) return fail(SPF_E_INVALID, "opacity_forward: tensors must be 4-byte aligned");
     if (n == 0) return SPF_OK;
     SPF_HIP(spf::launch_opacity_fwd(logits, stride, n, exponent, opacities, static_cast<hipStream_t>(stream_)));
     return SPF_OK;
@@ -1652,7 +1528,7 @@ int spf_opacity_backward(const float* logits, int64_t stride, int64_t n, float e
                          float* dL_dlogits, void* stream_) {
     if (const int rc = opacity_check("opacity_backward", logits, stride, n, exponent)) return rc;
     if (!dL_dopacities || !dL_dlogits) return fail(SPF_E_INVALID, "opacity_backward: null pointer (dL_dopacities or dL_dlogits)");
-    if (!aligned4({logits, dL_dopacities, dL_dlogits})) return fail(SPF_E_INVALID, "opacity_backward: tensors must be 4-byte aligned");
+    if (!aligned<4>({logits, dL_dopacities, dL_dlogits})) return fail(SPF_E_INVALID, "opacity_backward: tensors must be 4-byte aligned");
     if (n == 0) return SPF_OK;
     SPF_HIP(spf::launch_opacity_bwd(logits, stride, n, exponent, dL_dopacities, dL_dlogits, static_cast<hipStream_t>(stream_)));
     return SPF_OK;

@@ -43,6 +43,7 @@
 // (stage_commit, own_rows), everything of MASK, NORM and VIEWS, and the row-dot kernel, which attention16.hip launches
 // through launch_attn_delta.
 #include "attention_tiles.h"
+#include "launchers.h"
 
 namespace spf {
 

@@ -33,6 +33,7 @@
 // attention.hip's kernel behind launch_attn_delta.  This file owns the 16-bit LDS images (stage_commit, own_rows), the
 // operand fragments and the three matrix kernels.
 #include "attention_tiles.h"
+#include "launchers.h"
 
 namespace spf {
 

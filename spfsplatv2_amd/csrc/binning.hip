@@ -13,6 +13,7 @@
 #include <atomic>
 
 #include "spf_common.h"
+#include "launchers.h"
 
 namespace spf {
 

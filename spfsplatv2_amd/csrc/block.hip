@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "spf_common.h"
+#include "launchers.h"
 
 namespace spf {
 

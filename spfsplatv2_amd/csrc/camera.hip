@@ -6,6 +6,7 @@
 // (cuda_splatting.py:15-42), extrinsics.inverse() and the two transposes.  On MI355X those ~100 launches of
 // a few microseconds each cost more host time than the whole rasterizer costs device time.
 #include "point_slots.h"
+#include "launchers.h"
 
 namespace spf {
 

@@ -23,6 +23,7 @@
 #include <math.h>
 
 #include "spf_common.h"
+#include "launchers.h"
 
 namespace spf {
 

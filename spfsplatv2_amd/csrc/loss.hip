@@ -5,6 +5,7 @@
 // Here: one pass forward (read both images, deterministic two-level sum) and one pass backward
 // (grad = (2 * weight / N) * dL/dloss * (prediction - image), the upstream scalar read on the device: no sync).
 #include "point_slots.h"
+#include "launchers.h"
 
 namespace spf {
 

@@ -29,6 +29,7 @@
 //                               feature vector is all zero the 1 / ||a|| term is taken as 0 (autograd gives NaN there).
 // No atomics anywhere: results are run-to-run identical and an image's numbers do not depend on its batch.
 #include "point_slots.h"
+#include "launchers.h"
 
 namespace spf {
 

@@ -23,6 +23,7 @@
 #include <math.h>
 
 #include "point_slots.h"
+#include "launchers.h"
 
 namespace spf {
 

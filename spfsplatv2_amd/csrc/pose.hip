@@ -18,6 +18,7 @@
 //                             of them); per-point float32, the two running sums float64 in a fixed order
 #include "point_slots.h"
 #include "pose_math.h"
+#include "launchers.h"
 
 namespace spf {
 

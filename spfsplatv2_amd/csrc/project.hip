@@ -9,6 +9,7 @@
 #include <atomic>
 
 #include "spf_common.h"
+#include "launchers.h"
 
 namespace spf {
 

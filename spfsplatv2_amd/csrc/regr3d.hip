@@ -25,6 +25,7 @@
 // fixed order, and a slot's content depends on (row, chunk) only: results are run-to-run identical and do not depend
 // on the batch strides.
 #include "point_slots.h"
+#include "launchers.h"
 
 namespace spf {
 

@@ -26,6 +26,7 @@
 #include <stdlib.h>
 
 #include "spf_common.h"
+#include "launchers.h"
 
 namespace spf {
 

@@ -15,6 +15,7 @@
 // No atomics; a slot's content depends on the image and the chunk only, so a view's sums are formed in the same order
 // whether it comes alone or in a batch: the batched call equals the per-view loop bitwise.
 #include "point_slots.h"
+#include "launchers.h"
 
 namespace spf {
 

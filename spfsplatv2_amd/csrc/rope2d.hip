@@ -12,6 +12,7 @@
 // on the host with libm powf (exactly what the reference's CPU path evaluates,
 // curope/curope.cpp:35) and travel in the kernel-argument segment -- no device powf, no table in HBM.
 #include "rope_math.h"
+#include "launchers.h"
 
 namespace spf {
 

@@ -28,6 +28,7 @@
 // so the row pass reads and the column pass reads are both stride-1 across a wave: conflict-free (MI355X: 64 banks of
 // 4 bytes, ds_read_b32 serviced in two 32-lane groups).
 #include "point_slots.h"
+#include "launchers.h"
 
 namespace spf {
 

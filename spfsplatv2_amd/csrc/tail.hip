@@ -12,6 +12,7 @@
 // rotations; in backward their gradients) leave or arrive as flat coalesced accesses too.  64 x 83 floats = 21 KB per
 // block (K = 25): seven blocks per CU.  No atomics, nothing allocated, no host sync; every output byte is written once.
 #include "adapter_math.h"
+#include "launchers.h"
 
 namespace spf {
 

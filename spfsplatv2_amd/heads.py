@@ -43,7 +43,7 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .block import _call, _check_device, _check_float32
+from ._checks import check_device as _check_device, check_float32 as _check_float32
 
 MAX_SIDE = _lib.DPT_MAX_SIDE
 MAX_ELEMENTS = 2 ** 31 - 1
@@ -137,7 +137,7 @@ class _Upsample2x(torch.autograd.Function):
         x, skip = _dense(x), _dense(skip)
         B, C, h, w = x.shape
         out = torch.empty(B, C, 2 * h, 2 * w, dtype=x.dtype, device=x.device)
-        _call("spf_dpt_upsample2x_forward", x.device, x, skip, int(relu_skip), B * C, h, w, out)
+        _lib.launch("spf_dpt_upsample2x_forward", x.device, x, skip, int(relu_skip), B * C, h, w, out)
         ctx.save_for_backward(skip if relu_skip else None)       # the convolution output, never relu(skip)
         ctx.shape, ctx.has_skip, ctx.relu = x.shape, skip is not None, bool(relu_skip)
         return out
@@ -153,7 +153,7 @@ class _Upsample2x(torch.autograd.Function):
         if need_x or (need_skip and ctx.relu):
             dx = torch.empty(ctx.shape, dtype=dy.dtype, device=dy.device) if need_x else None
             dskip = torch.empty_like(dy) if ctx.relu else None
-            _call("spf_dpt_upsample2x_backward", dy.device, dy, skip, B * C, h, w, dx, dskip)
+            _lib.launch("spf_dpt_upsample2x_backward", dy.device, dy, skip, B * C, h, w, dx, dskip)
         if not ctx.relu:
             dskip = dy                                           # the same tensor, no copy
         return dx if need_x else None, dskip if need_skip else None, None
@@ -162,7 +162,7 @@ class _Upsample2x(torch.autograd.Function):
 def _add_relu_backward(y, dy, ds):
     dy, ds = _dense(dy), _dense(ds)
     g = torch.empty_like(y)
-    _call("spf_dpt_add_relu_backward", y.device, y, dy, ds, y.numel(), g)
+    _lib.launch("spf_dpt_add_relu_backward", y.device, y, dy, ds, y.numel(), g)
     return g
 
 
@@ -173,7 +173,7 @@ class _Relu(torch.autograd.Function):
     def forward(ctx, a):
         a = _dense(a)
         y = torch.empty_like(a)
-        _call("spf_dpt_add_relu_forward", a.device, a, None, None, a.numel(), None, y)
+        _lib.launch("spf_dpt_add_relu_forward", a.device, a, None, None, a.numel(), None, y)
         ctx.save_for_backward(y)                                 # (the convolution that reads y keeps it anyway)
         return y
 
@@ -191,7 +191,7 @@ class _AddRelu(torch.autograd.Function):
     def forward(ctx, a, b, c):
         a, b, c = _dense(a), _dense(b), _dense(c)
         s, y = torch.empty_like(a), torch.empty_like(a)
-        _call("spf_dpt_add_relu_forward", a.device, a, b, c, a.numel(), s, y)
+        _lib.launch("spf_dpt_add_relu_forward", a.device, a, b, c, a.numel(), s, y)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(y)
         ctx.three = c is not None
@@ -221,7 +221,7 @@ class _Points(torch.autograd.Function):
         B, _, H, W = out.shape
         pts = torch.empty(B, H, W, 3, dtype=out.dtype, device=out.device)
         cf = torch.empty(B, H, W, dtype=out.dtype, device=out.device) if conf is not None else None
-        _call("spf_dpt_points_forward", out.device, _Points._args(out, depth, conf), pts, cf)
+        _lib.launch("spf_dpt_points_forward", out.device, _Points._args(out, depth, conf), pts, cf)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(out)
         ctx.depth, ctx.conf = depth, conf
@@ -239,7 +239,7 @@ class _Points(torch.autograd.Function):
             dconf = _dense(dconf) if dconf is not None else torch.zeros(B, H, W, dtype=out.dtype, device=out.device)
         used = 4 if ctx.conf is not None else 3
         din = torch.empty_like(out) if C == used else torch.zeros_like(out)
-        _call("spf_dpt_points_backward", out.device, _Points._args(out, ctx.depth, ctx.conf), dpts, dconf, din)
+        _lib.launch("spf_dpt_points_backward", out.device, _Points._args(out, ctx.depth, ctx.conf), dpts, dconf, din)
         return din, None, None
 
 

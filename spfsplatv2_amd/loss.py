@@ -27,7 +27,6 @@ No CPU path: tensors must live on a HIP device.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from abc import ABC, abstractmethod
 from dataclasses import dataclass, fields
@@ -81,29 +80,20 @@ class _Mse(torch.autograd.Function):
     @staticmethod
     def forward(ctx, prediction: Tensor, image: Tensor, weight: float, grad_mode: bool = True):
         p, t = _kernel_operand(prediction), _kernel_operand(image)
-        lib = _lib.load()
         dev = p.device
         # per-call scratch for the block partials (a few KB from the caching allocator): two streams computing
         # losses at the same time never share it
-        partial = torch.empty(lib.spf_mse_partial_blocks(), dtype=torch.float32, device=dev)
+        partial = torch.empty(_lib.load().spf_mse_partial_blocks(), dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         # when a backward will come, the forward pass also writes the gradient for dL/dloss = 1 (what
         # `loss.backward()` passes): the backward is then one scalar look at the upstream gradient
         # (`grad_mode` = torch.is_grad_enabled() at the CALL SITE: needs_input_grad stays True under no_grad, and an
         #  evaluation loss on a tensor that requires grad must not pay a batch-sized allocation and write)
         unit = torch.empty_like(p) if (grad_mode and ctx.needs_input_grad[0]) else None
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            if unit is not None:
-                _lib.check(lib.spf_mse_forward_grad(C.c_void_p(p.data_ptr()), C.c_void_p(t.data_ptr()), p.numel(),
-                                                    float(weight), C.c_void_p(partial.data_ptr()),
-                                                    C.c_void_p(loss.data_ptr()), C.c_void_p(unit.data_ptr()), stream),
-                           "spf_mse_forward_grad")
-            else:
-                _lib.check(lib.spf_mse_forward(C.c_void_p(p.data_ptr()), C.c_void_p(t.data_ptr()), p.numel(),
-                                               float(weight), C.c_void_p(partial.data_ptr()),
-                                               C.c_void_p(loss.data_ptr()), stream),
-                           "spf_mse_forward")
+        if unit is not None:
+            _lib.launch("spf_mse_forward_grad", dev, p, t, p.numel(), float(weight), partial, loss, unit)
+        else:
+            _lib.launch("spf_mse_forward", dev, p, t, p.numel(), float(weight), partial, loss)
         ctx.save_for_backward(p, t)
         ctx.unit = unit
         ctx.weight = float(weight)
@@ -113,25 +103,18 @@ class _Mse(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         p, t = ctx.saved_tensors
-        lib = _lib.load()
-        dev = p.device
         g = g.to(torch.float32).contiguous()
         unit, ctx.unit = ctx.unit, None
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            if unit is not None:
-                # first backward through this node: the forward's unit gradient, scaled in place by dL/dloss (a no-op
-                # launch when that is 1).  The buffer is handed to autograd; a second backward (retain_graph) recomputes.
-                gp = unit
-                one = _ONES.get(g.device)
-                if not (one is not None and g.data_ptr() == one.data_ptr()):     # (unit_grad(): exactly 1, nothing to do)
-                    _lib.check(lib.spf_mse_scale_grad(C.c_void_p(gp.data_ptr()), gp.numel(), C.c_void_p(g.data_ptr()),
-                                                      stream), "spf_mse_scale_grad")
-            else:
-                gp = torch.empty_like(p)
-                _lib.check(lib.spf_mse_backward(C.c_void_p(p.data_ptr()), C.c_void_p(t.data_ptr()), p.numel(),
-                                                ctx.weight, C.c_void_p(g.data_ptr()), C.c_void_p(gp.data_ptr()), stream),
-                           "spf_mse_backward")
+        if unit is not None:
+            # first backward through this node: the forward's unit gradient, scaled in place by dL/dloss (a no-op
+            # launch when that is 1).  The buffer is handed to autograd; a second backward (retain_graph) recomputes.
+            gp = unit
+            one = _ONES.get(g.device)
+            if not (one is not None and g.data_ptr() == one.data_ptr()):     # (unit_grad(): exactly 1, nothing to do)
+                _lib.launch("spf_mse_scale_grad", p.device, gp, gp.numel(), g)
+        else:
+            gp = torch.empty_like(p)
+            _lib.launch("spf_mse_backward", p.device, p, t, p.numel(), ctx.weight, g, gp)
         gp = gp.view(ctx.shape)
         gi = -gp if ctx.needs_input_grad[1] else None
         return gp, gi, None, None
@@ -211,8 +194,8 @@ def reproj_lw(mode: str, global_step, total_iterations, circle_schedule: bool, s
 def _reproj_args(p5: Tensor, poses: Tensor, intr: Tensor, code: int, weight: float, lw: float, hard: float,
                  soft: float):
     b, v, h, w, _ = p5.shape
-    return _lib.SpfReproj(C.c_void_p(p5.data_ptr()), p5.stride(0), p5.stride(1), C.c_void_p(poses.data_ptr()),
-                          C.c_void_p(intr.data_ptr()), b, v, h, w, code, weight, lw, hard, soft)
+    return _lib.SpfReproj(_lib.ptr(p5), p5.stride(0), p5.stride(1), _lib.ptr(poses), _lib.ptr(intr), b, v, h, w, code,
+                          weight, lw, hard, soft)
 
 
 class _Reproj(torch.autograd.Function):
@@ -226,17 +209,13 @@ class _Reproj(torch.autograd.Function):
         b, v, h, w, _ = p5.shape
         po = poses.reshape(b, v, 4, 4).contiguous()
         ki = intrinsics.reshape(b, v, 3, 3).contiguous()
-        lib = _lib.load()
         dev = p5.device
         args = _reproj_args(p5, po, ki, code, weight, lw, hard, soft)
-        nslots = lib.spf_reproj_partial_blocks(b, v, h, w)
+        nslots = _lib.load().spf_reproj_partial_blocks(b, v, h, w)
         partial = torch.empty(2 * nslots, dtype=torch.float32, device=dev)
         loss = torch.empty((v,) if batched else (), dtype=torch.float32, device=dev)
         scale = torch.empty(v, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(lib.spf_reproj_forward(C.byref(args), C.c_void_p(partial.data_ptr()), C.c_void_p(loss.data_ptr()),
-                                              C.c_void_p(scale.data_ptr()), stream), "spf_reproj_forward")
+        _lib.launch("spf_reproj_forward", dev, args, partial, loss, scale)
         ctx.save_for_backward(p5, po, ki, scale)
         ctx.params = (code, weight, lw, hard, soft, nslots)
         ctx.shapes = (pts3d.shape, poses.shape, intrinsics.shape)
@@ -254,15 +233,8 @@ class _Reproj(torch.autograd.Function):
         dpose = torch.empty(b, v, 4, 4, dtype=torch.float32, device=dev) if need_pose else None
         dk = torch.empty(b, v, 3, 3, dtype=torch.float32, device=dev) if need_k else None
         gpartial = (torch.empty(24 * nslots, dtype=torch.float32, device=dev) if (need_pose or need_k) else None)
-
-        def ptr(t):
-            return C.c_void_p(t.data_ptr() if t is not None else None)
-        lib = _lib.load()
-        args = _reproj_args(p5, po, ki, code, weight, lw, hard, soft)
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(lib.spf_reproj_backward(C.byref(args), ptr(scale), ptr(g), ptr(dp), ptr(gpartial), ptr(dpose),
-                                               ptr(dk), stream), "spf_reproj_backward")
+        _lib.launch("spf_reproj_backward", dev, _reproj_args(p5, po, ki, code, weight, lw, hard, soft), scale, g, dp,
+                    gpartial, dpose, dk)
         sp, spose, sk = ctx.shapes
         return (dp.view(sp) if dp is not None else None, dpose.view(spose) if dpose is not None else None,
                 dk.view(sk) if dk is not None else None, None, None, None, None, None)
@@ -385,9 +357,7 @@ def _regr3d_rows(t: Tensor) -> Tensor:
 
 def _regr3d_args(gt1, gt2, pr1, pr2, c1, c2, dist_clip, disable_view1, normalize, gt_scale):
     b, h, w, _ = gt1.shape
-
-    def ptr(t):
-        return C.c_void_p(t.data_ptr() if t is not None else None)
+    ptr = _lib.ptr
     return _lib.SpfRegr3d(ptr(gt1), ptr(gt2), ptr(pr1), ptr(pr2), ptr(c1), ptr(c2), gt1.stride(0), gt2.stride(0),
                           pr1.stride(0), pr2.stride(0), b, h, w, int(dist_clip is not None),
                           float(dist_clip) if dist_clip is not None else 0.0, int(bool(disable_view1)),
@@ -402,20 +372,15 @@ class _Regr3D(torch.autograd.Function):
         c1, c2 = ((None, None) if dist_clip is not None else
                   tuple(c.to(torch.float32).contiguous() for c in (conf1, conf2)))
         b, h, w, _ = gt1.shape
-        lib = _lib.load()
         dev = gt1.device
         args = _regr3d_args(gt1, gt2, pr1, pr2, c1, c2, dist_clip, disable_view1, normalize, gt_scale)
-        nbytes = lib.spf_regr3d_scratch_bytes(b, h, w)
+        nbytes = _lib.load().spf_regr3d_scratch_bytes(b, h, w)
         if nbytes < 0:
             raise RuntimeError(f"regr3d_loss: {b} x {h} x {w} points is not a supported size")
         scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
         stats = torch.empty(8 * b, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(lib.spf_regr3d_forward(C.byref(args), C.c_void_p(scratch.data_ptr()),
-                                              C.c_void_p(stats.data_ptr()), C.c_void_p(loss.data_ptr()), stream),
-                       "spf_regr3d_forward")
+        _lib.launch("spf_regr3d_forward", dev, args, scratch, stats, loss)
         ctx.save_for_backward(gt1, gt2, pr1, pr2, c1, c2, scratch, stats)
         ctx.params = (dist_clip, disable_view1, normalize, gt_scale)
         ctx.mark_non_differentiable(stats)
@@ -429,15 +394,8 @@ class _Regr3D(torch.autograd.Function):
         g = grad.to(torch.float32).reshape(1).contiguous()
         d1 = torch.empty(pr1.shape, dtype=torch.float32, device=dev) if need1 else None
         d2 = torch.empty(pr2.shape, dtype=torch.float32, device=dev) if need2 else None
-
-        def ptr(t):
-            return C.c_void_p(t.data_ptr() if t is not None else None)
-        lib = _lib.load()
-        args = _regr3d_args(gt1, gt2, pr1, pr2, c1, c2, *ctx.params)
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(lib.spf_regr3d_backward(C.byref(args), ptr(scratch), ptr(stats), ptr(g), ptr(d1), ptr(d2),
-                                               stream), "spf_regr3d_backward")
+        _lib.launch("spf_regr3d_backward", dev, _regr3d_args(gt1, gt2, pr1, pr2, c1, c2, *ctx.params), scratch, stats, g,
+                    d1, d2)
         return None, None, d1, d2, None, None, None, None, None, None
 
 

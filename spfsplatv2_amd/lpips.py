@@ -30,7 +30,6 @@ the very kernels the whole-chain calls launch (the layout copy around them is te
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 import re
 from pathlib import Path
@@ -239,14 +238,6 @@ def resolve_weights(weights=None) -> LpipsWeights:
 
 
 # ---- plumbing --------------------------------------------------------------------------------------------------------
-def _ptr(t: Optional[Tensor]) -> C.c_void_p:
-    return C.c_void_p(t.data_ptr() if t is not None else None)
-
-
-def _stream(dev) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _need_device(name: str, **tensors: Tensor) -> None:
     for what, t in tensors.items():
         if not t.is_floating_point():
@@ -275,9 +266,10 @@ def _check_pair(name: str, in0: Tensor, in1: Tensor) -> None:
 
 def _args(x0: Tensor, x1: Optional[Tensor], dw: dict, normalize: bool, weight: float = 1.0) -> _lib.SpfLpips:
     n, _, h, w = x0.shape
-    return _lib.SpfLpips(_ptr(x0), _ptr(x1), x0.stride(0), x1.stride(0) if x1 is not None else 0, n, h, w,
-                         int(bool(normalize)), float(weight), 0, _ptr(dw["wfwd"]), _ptr(dw["wbwd"]), _ptr(dw["bias"]),
-                         _ptr(dw["lin"]), _ptr(dw["shift_scale"]))
+    ptr = _lib.ptr
+    return _lib.SpfLpips(ptr(x0), ptr(x1), x0.stride(0), x1.stride(0) if x1 is not None else 0, n, h, w,
+                         int(bool(normalize)), float(weight), 0, ptr(dw["wfwd"]), ptr(dw["wbwd"]), ptr(dw["bias"]),
+                         ptr(dw["lin"]), ptr(dw["shift_scale"]))
 
 
 def _nhwc(t: Tensor) -> Tensor:
@@ -300,21 +292,18 @@ class _Lpips(torch.autograd.Function):
     def forward(ctx, in0: Tensor, in1: Tensor, W: LpipsWeights, normalize: bool, mean_weight: Optional[float],
                 grad_mode: bool):
         x0, x1 = in0.contiguous(), in1.contiguous()
-        lib = _lib.load()
         dev = x0.device
         n, _, h, w = x0.shape
         need = [bool(grad_mode and ctx.needs_input_grad[i]) for i in (0, 1)]
-        nbytes = lib.spf_lpips_workspace_bytes(n * sum(need), 2 * n, h, w)
+        nbytes = _lib.load().spf_lpips_workspace_bytes(n * sum(need), 2 * n, h, w)
         if nbytes < 0:
             raise RuntimeError(f"lpips: unsupported sizes {tuple(x0.shape)}")
-        with torch.cuda.device(dev):
-            dw = W.on(dev)
-            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-            out = torch.empty(n, dtype=torch.float32, device=dev)
-            mean = torch.empty((), dtype=torch.float32, device=dev) if mean_weight is not None else None
-            args = _args(x0, x1, dw, normalize, 1.0 if mean_weight is None else mean_weight)
-            _lib.check(lib.spf_lpips_forward(C.byref(args), _ptr(ws), _ptr(out), _ptr(mean), _stream(dev)),
-                       "spf_lpips_forward")
+        dw = W.on(dev)
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        mean = torch.empty((), dtype=torch.float32, device=dev) if mean_weight is not None else None
+        args = _args(x0, x1, dw, normalize, 1.0 if mean_weight is None else mean_weight)
+        _lib.launch("spf_lpips_forward", dev, args, ws, out, mean)
         if any(need):
             ctx.save_for_backward(x0, x1)
             ctx.ws, ctx.dw, ctx.params = ws, dw, (normalize, mean_weight)
@@ -329,11 +318,8 @@ class _Lpips(torch.autograd.Function):
         need0, need1 = ctx.needs_input_grad[:2]
         d0 = torch.empty_like(x0, memory_format=torch.contiguous_format) if need0 else None
         d1 = torch.empty_like(x1, memory_format=torch.contiguous_format) if need1 else None
-        with torch.cuda.device(dev):
-            args = _args(x0, x1, ctx.dw, normalize, 1.0 if mean_weight is None else mean_weight)
-            _lib.check(_lib.load().spf_lpips_backward(C.byref(args), _ptr(ctx.ws), _ptr(g),
-                                                      int(mean_weight is not None), _ptr(d0), _ptr(d1), _stream(dev)),
-                       "spf_lpips_backward")
+        args = _args(x0, x1, ctx.dw, normalize, 1.0 if mean_weight is None else mean_weight)
+        _lib.launch("spf_lpips_backward", dev, args, ctx.ws, g, int(mean_weight is not None), d0, d1)
         return d0, d1, None, None, None, None
 
 
@@ -387,23 +373,20 @@ def conv3x3_forward(x: Tensor, layer: int, weights: LpipsWeights, relu: bool = T
     _need_device("conv3x3_forward", x=x)
     if x.dim() != 4 or x.shape[1] != CONV_CIN[l]:
         raise ValueError(f"conv3x3_forward: layer {layer} takes [N,{CONV_CIN[l]},H,W], got {tuple(x.shape)}")
-    lib, dev = _lib.load(), x.device
+    dev = x.device
     n, _, h, w = x.shape
-    with torch.cuda.device(dev):
-        dw = weights.on(dev)
-        out = torch.empty((n, h, w, CONV_COUT[l]), dtype=torch.float32, device=dev)
-        if l == 0:
-            if not relu:
-                raise NotImplementedError("conv3x3_forward: the first layer's kernel always applies its ReLU")
-            xi = x.to(torch.float32).contiguous()
-            _lib.check(lib.spf_lpips_conv1_forward(C.byref(_args(xi, None, dw, normalize)), _ptr(out), _stream(dev)),
-                       "spf_lpips_conv1_forward")
-        else:
-            xi = _nhwc(x)
-            wp = dw["wfwd"][PACK_OFFSET[l]:]
-            bias = dw["bias"][sum(CONV_COUT[:l]):]
-            _lib.check(lib.spf_lpips_conv3x3(_ptr(xi), None, _ptr(wp), _ptr(bias), _ptr(out), n, h, w, CONV_CIN[l],
-                                             CONV_COUT[l], int(bool(relu)), _stream(dev)), "spf_lpips_conv3x3")
+    dw = weights.on(dev)
+    out = torch.empty((n, h, w, CONV_COUT[l]), dtype=torch.float32, device=dev)
+    if l == 0:
+        if not relu:
+            raise NotImplementedError("conv3x3_forward: the first layer's kernel always applies its ReLU")
+        xi = x.to(torch.float32).contiguous()
+        _lib.launch("spf_lpips_conv1_forward", dev, _args(xi, None, dw, normalize), out)
+    else:
+        xi = _nhwc(x)
+        wp = dw["wfwd"][PACK_OFFSET[l]:]
+        bias = dw["bias"][sum(CONV_COUT[:l]):]
+        _lib.launch("spf_lpips_conv3x3", dev, xi, None, wp, bias, out, n, h, w, CONV_CIN[l], CONV_COUT[l], int(bool(relu)))
     return _nchw(out)
 
 
@@ -416,23 +399,20 @@ def conv3x3_backward_data(g: Tensor, layer: int, weights: LpipsWeights, act: Opt
     _need_device("conv3x3_backward_data", g=g, **({} if act is None else {"act": act}))
     if g.dim() != 4 or g.shape[1] != CONV_COUT[l] or (act is not None and act.shape != g.shape):
         raise ValueError(f"conv3x3_backward_data: layer {layer} takes [N,{CONV_COUT[l]},H,W] (and `act` alike)")
-    lib, dev = _lib.load(), g.device
+    dev = g.device
     n, _, h, w = g.shape
-    with torch.cuda.device(dev):
-        dw = weights.on(dev)
-        gi = _nhwc(g)
-        ai = _nhwc(act) if act is not None else None
-        if l == 0:
-            if ai is None:
-                ai = torch.ones_like(gi)
-            out = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
-            _lib.check(lib.spf_lpips_conv1_backward(C.byref(_args(out, None, dw, normalize)), _ptr(gi), _ptr(ai),
-                                                    _ptr(out), _stream(dev)), "spf_lpips_conv1_backward")
-            return out
-        out = torch.empty((n, h, w, CONV_CIN[l]), dtype=torch.float32, device=dev)
-        wp = dw["wbwd"][PACK_OFFSET[l]:]
-        _lib.check(lib.spf_lpips_conv3x3(_ptr(gi), _ptr(ai), _ptr(wp), None, _ptr(out), n, h, w, CONV_COUT[l],
-                                         CONV_CIN[l], 0, _stream(dev)), "spf_lpips_conv3x3")
+    dw = weights.on(dev)
+    gi = _nhwc(g)
+    ai = _nhwc(act) if act is not None else None
+    if l == 0:
+        if ai is None:
+            ai = torch.ones_like(gi)
+        out = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
+        _lib.launch("spf_lpips_conv1_backward", dev, _args(out, None, dw, normalize), gi, ai, out)
+        return out
+    out = torch.empty((n, h, w, CONV_CIN[l]), dtype=torch.float32, device=dev)
+    wp = dw["wbwd"][PACK_OFFSET[l]:]
+    _lib.launch("spf_lpips_conv3x3", dev, gi, ai, wp, None, out, n, h, w, CONV_COUT[l], CONV_CIN[l], 0)
     return _nchw(out)
 
 
@@ -442,12 +422,9 @@ def maxpool_forward(x: Tensor) -> Tensor:
     n, c, h, w = x.shape
     if c % 4 or h < 2 or w < 2:
         raise ValueError(f"maxpool_forward: needs C % 4 == 0 and sides >= 2, got {tuple(x.shape)}")
-    dev = x.device
-    with torch.cuda.device(dev):
-        xi = _nhwc(x)
-        out = torch.empty((n, h // 2, w // 2, c), dtype=torch.float32, device=dev)
-        _lib.check(_lib.load().spf_lpips_pool_forward(_ptr(xi), _ptr(out), n, h, w, c, _stream(dev)),
-                   "spf_lpips_pool_forward")
+    xi = _nhwc(x)
+    out = torch.empty((n, h // 2, w // 2, c), dtype=torch.float32, device=x.device)
+    _lib.launch("spf_lpips_pool_forward", x.device, xi, out, n, h, w, c)
     return _nchw(out)
 
 
@@ -457,12 +434,9 @@ def maxpool_backward(g: Tensor, x: Tensor) -> Tensor:
     n, c, h, w = x.shape
     if c % 4 or h < 2 or w < 2 or tuple(g.shape) != (n, c, h // 2, w // 2):
         raise ValueError(f"maxpool_backward: shapes {tuple(g.shape)} and {tuple(x.shape)} do not belong together")
-    dev = x.device
-    with torch.cuda.device(dev):
-        gi, xi = _nhwc(g), _nhwc(x)
-        out = torch.zeros((n, h, w, c), dtype=torch.float32, device=dev)
-        _lib.check(_lib.load().spf_lpips_pool_backward(_ptr(gi), _ptr(xi), _ptr(out), n, h, w, c, _stream(dev)),
-                   "spf_lpips_pool_backward")
+    gi, xi = _nhwc(g), _nhwc(x)
+    out = torch.zeros((n, h, w, c), dtype=torch.float32, device=x.device)
+    _lib.launch("spf_lpips_pool_backward", x.device, gi, xi, out, n, h, w, c)
     return _nchw(out)
 
 
@@ -477,12 +451,9 @@ def head_forward(a: Tensor, b: Tensor, lin: Tensor) -> Tensor:
     """One tap's term: the mean over the pixels of ``sum_c lin_c (a_c / (||a|| + 1e-10) - b_c / (||b|| + 1e-10))^2`` -> [N]."""
     ai, bi, li = _head_operands("head_forward", a, b, lin)
     n, c, h, w = a.shape
-    dev = a.device
-    with torch.cuda.device(dev):
-        partial = torch.empty(n * ((h * w + 63) // 64), dtype=torch.float32, device=dev)
-        out = torch.empty(n, dtype=torch.float32, device=dev)
-        _lib.check(_lib.load().spf_lpips_head_forward(_ptr(ai), _ptr(bi), _ptr(li), n, h * w, c, _ptr(partial), _ptr(out),
-                                                      _stream(dev)), "spf_lpips_head_forward")
+    partial = torch.empty(n * ((h * w + 63) // 64), dtype=torch.float32, device=a.device)
+    out = torch.empty(n, dtype=torch.float32, device=a.device)
+    _lib.launch("spf_lpips_head_forward", a.device, ai, bi, li, n, h * w, c, partial, out)
     return out
 
 
@@ -493,11 +464,8 @@ def head_backward(a: Tensor, b: Tensor, lin: Tensor, upstream: Tensor, need_a: b
     n, c, h, w = a.shape
     if upstream.numel() != n or not (need_a or need_b):
         raise ValueError("head_backward: upstream must have N entries, and one gradient must be asked for")
-    dev = a.device
-    with torch.cuda.device(dev):
-        up = upstream.to(torch.float32).reshape(-1).contiguous()
-        da = torch.empty_like(ai) if need_a else None
-        db = torch.empty_like(bi) if need_b else None
-        _lib.check(_lib.load().spf_lpips_head_backward(_ptr(ai), _ptr(bi), _ptr(li), n, h * w, c, _ptr(up), _ptr(da),
-                                                       _ptr(db), _stream(dev)), "spf_lpips_head_backward")
+    up = upstream.to(torch.float32).reshape(-1).contiguous()
+    da = torch.empty_like(ai) if need_a else None
+    db = torch.empty_like(bi) if need_b else None
+    _lib.launch("spf_lpips_head_backward", a.device, ai, bi, li, n, h * w, c, up, da, db)
     return (_nchw(da) if need_a else None), (_nchw(db) if need_b else None)

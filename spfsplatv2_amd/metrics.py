@@ -20,8 +20,6 @@ the caller: ``weights=`` or ``$SPF_LPIPS_WEIGHTS`` (lpips.py says how to make th
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 from torch import Tensor
 
@@ -61,13 +59,8 @@ def compute_psnr(ground_truth: Tensor, predicted: Tensor) -> Tensor:
     _check_pair("compute_psnr", ground_truth, predicted)
     _check_images("compute_psnr", ground_truth, predicted, 1)
     gt, pred = _operand(ground_truth), _operand(predicted)
-    lib = _lib.load()
-    dev = pred.device
-    out = torch.empty(pred.shape[0], dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.spf_psnr_forward(C.c_void_p(gt.data_ptr()), C.c_void_p(pred.data_ptr()), pred.shape[0],
-                                        pred[0].numel(), C.c_void_p(out.data_ptr()), stream), "spf_psnr_forward")
+    out = torch.empty(pred.shape[0], dtype=torch.float32, device=pred.device)
+    _lib.launch("spf_psnr_forward", pred.device, gt, pred, pred.shape[0], pred[0].numel(), out)
     return out.to(predicted.dtype)
 
 

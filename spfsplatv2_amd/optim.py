@@ -345,14 +345,11 @@ class GuardedAdamW(torch.optim.Optimizer):
                 raise RuntimeError(f"{_NAME}: the gradient of parameter {i} has shape {tuple(g.shape)}, not {tuple(p.shape)}")
             ptrs[i] = g.data_ptr()
         hp = self._hyper()
-        lib = _lib.load()
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev)
             slot = self._slot(len(ptrs))
             slot.array[:] = ptrs
             plan.grads.copy_(slot.pinned, non_blocking=True)
-            slot.event.record(stream)
+            slot.event.record(torch.cuda.current_stream(dev))
             slot.pending = True
-            _lib.check(lib.spf_optim_step(C.byref(plan.args), C.byref(hp), C.c_void_p(stream.cuda_stream)),
-                       "spf_optim_step")
+        _lib.launch("spf_optim_step", dev, plan.args, hp)
         return loss

@@ -40,7 +40,6 @@ Out of scope: ``get_pnp_pose*`` (cv2 RANSAC), ``update_pose`` / ``SE3_exp``, ``c
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import numpy as np
@@ -50,14 +49,6 @@ from torch import Tensor
 from . import _lib
 
 ENCODINGS = {"rot6d": 0, "absT_quaR_FoV": 1}
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr() if t is not None else None)
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _check(name: str, what: str, t) -> None:
@@ -83,13 +74,10 @@ class _ComposePose(torch.autograd.Function):
         b, v, _ = enc.shape
         if enc.stride(2) != 1:                       # a view's nine floats must be contiguous; b and v strides are free
             enc = enc.contiguous()
-        lib = _lib.load()
         dev = enc.device
         poses = torch.empty(b, v, 4, 4, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.spf_pose_compose_forward(_ptr(enc), enc.stride(0), enc.stride(1), b, v, context_views,
-                                                    encoding, int(baseline), int(relative), _ptr(poses), _stream(dev)),
-                       "spf_pose_compose_forward")
+        _lib.launch("spf_pose_compose_forward", dev, enc, enc.stride(0), enc.stride(1), b, v, context_views, encoding,
+                    int(baseline), int(relative), poses)
         ctx.save_for_backward(enc)
         ctx.params = (context_views, encoding, baseline, relative)
         return poses
@@ -98,15 +86,12 @@ class _ComposePose(torch.autograd.Function):
     def backward(ctx, grad: Tensor):
         (enc,) = ctx.saved_tensors
         b, v, _ = enc.shape
-        lib = _lib.load()
         dev = enc.device
         g = grad.to(torch.float32).contiguous()
         denc = torch.empty(b, v, 9, dtype=torch.float32, device=dev)
         context_views, encoding, baseline, relative = ctx.params
-        with torch.cuda.device(dev):
-            _lib.check(lib.spf_pose_compose_backward(_ptr(enc), enc.stride(0), enc.stride(1), b, v, context_views,
-                                                     encoding, int(baseline), int(relative), _ptr(g), _ptr(denc),
-                                                     _stream(dev)), "spf_pose_compose_backward")
+        _lib.launch("spf_pose_compose_backward", dev, enc, enc.stride(0), enc.stride(1), b, v, context_views, encoding,
+                    int(baseline), int(relative), g, denc)
         return denc, None, None, None, None
 
 
@@ -149,12 +134,9 @@ class _DepthProject(torch.autograd.Function):
         if pts.stride(2) != 1 or (n > 1 and pts.stride(1) != 3):       # an image's 3 n floats must be contiguous
             pts = pts.contiguous()
         poses = poses.contiguous()
-        lib = _lib.load()
         dev = pts.device
         depth = torch.empty(N, n, 1, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.spf_depth_project_forward(_ptr(pts), pts.stride(0), _ptr(poses), N, n, _ptr(depth),
-                                                     _stream(dev)), "spf_depth_project_forward")
+        _lib.launch("spf_depth_project_forward", dev, pts, pts.stride(0), poses, N, n, depth)
         ctx.save_for_backward(pts, poses)
         return depth
 
@@ -162,7 +144,6 @@ class _DepthProject(torch.autograd.Function):
     def backward(ctx, grad: Tensor):
         pts, poses = ctx.saved_tensors
         N, n, _ = pts.shape
-        lib = _lib.load()
         dev = pts.device
         g = grad.to(torch.float32).contiguous()
         need_pts, need_poses = ctx.needs_input_grad
@@ -170,11 +151,8 @@ class _DepthProject(torch.autograd.Function):
         dposes = gpartial = None
         if need_poses:
             dposes = torch.empty(N, 4, 4, dtype=torch.float32, device=dev)
-            gpartial = torch.empty(lib.spf_depth_project_partial_blocks(N, n), 4, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.spf_depth_project_backward(_ptr(pts), pts.stride(0), _ptr(poses), N, n, _ptr(g), _ptr(dpts),
-                                                      _ptr(gpartial), _ptr(dposes), _stream(dev)),
-                       "spf_depth_project_backward")
+            gpartial = torch.empty(_lib.load().spf_depth_project_partial_blocks(N, n), 4, dtype=torch.float32, device=dev)
+        _lib.launch("spf_depth_project_backward", dev, pts, pts.stride(0), poses, N, n, g, dpts, gpartial, dposes)
         return dpts, dposes
 
 
@@ -215,12 +193,10 @@ def _pose_error_launch(name: str, pred: Tensor, tgt: Tensor):
     p = pred.detach().to(torch.float32).reshape(-1, 4, 4).contiguous()
     t = tgt.detach().to(torch.float32).reshape(-1, 4, 4).contiguous()
     N = p.shape[0]
-    lib = _lib.load()
     dev = p.device
     errors = torch.empty(N, 3, dtype=torch.float32, device=dev)
     means = torch.empty(3, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.spf_pose_error(_ptr(p), _ptr(t), N, _ptr(errors), _ptr(means), _stream(dev)), "spf_pose_error")
+    _lib.launch("spf_pose_error", dev, p, t, N, errors, means)
     return errors, means
 
 
@@ -282,16 +258,13 @@ def _focal_launch(name: str, pts: Tensor, pp, min_focal: float, max_focal: float
                                f"{tuple(pp.shape)} on {pp.device}")
         pp = pp.detach().to(torch.float32).reshape(-1, 2).contiguous()
         pp_stride = 2 if pp.shape[0] == B and B > 1 else 0
-    lib = _lib.load()
-    if lib.spf_focal_scratch_bytes(B, H, W) < 0:
+    if _lib.load().spf_focal_scratch_bytes(B, H, W) < 0:
         raise RuntimeError(f"{name}: {B} x {H} x {W} points is not a supported size")
     focal = torch.empty(B, dtype=torch.float32, device=dev)
     K = torch.empty(B, 3, 3, dtype=torch.float32, device=dev) if intr is not None else None
     height, width = intr if intr is not None else (1, 1)
-    with torch.cuda.device(dev):
-        _lib.check(lib.spf_focal_estimate(_ptr(pts), pts.stride(0), pts.stride(1), B, H, W, _ptr(pp), pp_stride,
-                                          float(min_focal), float(max_focal), width / 2.0, height / 2.0, float(height),
-                                          float(width), None, _ptr(focal), _ptr(K), _stream(dev)), "spf_focal_estimate")
+    _lib.launch("spf_focal_estimate", dev, pts, pts.stride(0), pts.stride(1), B, H, W, pp, pp_stride, float(min_focal),
+                float(max_focal), width / 2.0, height / 2.0, float(height), float(width), None, focal, K)
     return focal, K
 
 

@@ -126,8 +126,7 @@ def last_forward_stats() -> dict:
     return {k: v for k, v in _last.items() if k != "counters"}
 
 
-def _ptr(t: Optional[Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
+_ptr = _lib.ptr
 
 
 def _f32c(t: Tensor, name: str, shape: tuple) -> Tensor:
@@ -281,8 +280,7 @@ def _check_sh(S, G, sh_degree, sh_band4, shs=None, sh_layout="gk3", shs_high=Non
     return shs, shs_high, sh_mask, K, layout, bool(sh_band4)
 
 
-def _stream_ptr(device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+_stream_ptr = _lib.stream_ptr
 
 
 def _on_device_of_first_arg(fn):

@@ -15,8 +15,6 @@ There is no CPU path here (the reference's CPU loop lives on as the test oracle 
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -58,7 +56,8 @@ def rope_2d(tokens: torch.Tensor, positions: torch.Tensor, base: float, fwd: flo
     """In-place RoPE-2D on ``tokens`` (B,N,H,D); ``fwd`` = +F0 forward, -F0 backward."""
     _check(tokens, positions)
     B, N, H, D = tokens.shape
-    _launch(tokens, positions, B, N, H, D, tokens.stride(0), tokens.stride(1), D, 1, base, fwd)
+    _lib.launch("spf_rope2d", tokens.device, tokens, positions, B, N, H, D, tokens.stride(0), tokens.stride(1), D, 1,
+                _DTYPES[tokens.dtype], float(base), float(fwd))
 
 
 def rope_2d_pair(q: torch.Tensor, k: torch.Tensor, positions: torch.Tensor, base: float, fwd: float) -> None:
@@ -71,20 +70,8 @@ def rope_2d_pair(q: torch.Tensor, k: torch.Tensor, positions: torch.Tensor, base
         return
     _check(q, positions)
     B, N, H, D = q.shape
-    lib = _lib.load()
-    with torch.cuda.device(q.device):
-        stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-        _lib.check(lib.spf_rope2d_pair(C.c_void_p(q.data_ptr()), C.c_void_p(k.data_ptr()),
-                                       C.c_void_p(positions.data_ptr()), B, N, H, D, q.stride(0), q.stride(1), D, 1,
-                                       _DTYPES[q.dtype], float(base), float(fwd), stream), "spf_rope2d_pair")
-
-
-def _launch(tokens, positions, B, N, H, D, sb, sn, sh, pos_div, base, fwd) -> None:
-    lib = _lib.load()
-    with torch.cuda.device(tokens.device):      # HIP launches go to the current device
-        stream = C.c_void_p(torch.cuda.current_stream(tokens.device).cuda_stream)
-        _lib.check(lib.spf_rope2d(C.c_void_p(tokens.data_ptr()), C.c_void_p(positions.data_ptr()), B, N, H, D, sb, sn,
-                                  sh, pos_div, _DTYPES[tokens.dtype], float(base), float(fwd), stream), "spf_rope2d")
+    _lib.launch("spf_rope2d_pair", q.device, q, k, positions, B, N, H, D, q.stride(0), q.stride(1), D, 1,
+                _DTYPES[q.dtype], float(base), float(fwd))
 
 
 def rope_2d_head_major(tokens: torch.Tensor, positions: torch.Tensor, base: float, fwd: float) -> None:
@@ -103,7 +90,8 @@ def rope_2d_head_major(tokens: torch.Tensor, positions: torch.Tensor, base: floa
     if tokens.dtype not in _DTYPES:
         raise RuntimeError(f"rope_2d: unsupported dtype {tokens.dtype}")
     positions = positions.to(torch.int64).contiguous()
-    _launch(tokens, positions, B * H, N, 1, D, N * D, D, D, H, base, fwd)
+    _lib.launch("spf_rope2d", tokens.device, tokens, positions, B * H, N, 1, D, N * D, D, D, H, _DTYPES[tokens.dtype],
+                float(base), float(fwd))
 
 
 class cuRoPE2D_func(torch.autograd.Function):

@@ -77,7 +77,7 @@ def _args(X: Tensor, Y: Tensor, win: Sequence[float], C1: float, C2: float, cov_
           nonnegative: bool) -> _lib.SpfSsim:
     n, c, h, w = X.shape
     arr = (C.c_float * _lib.SSIM_MAX_WIN)(*win)
-    return _lib.SpfSsim(C.c_void_p(X.data_ptr()), C.c_void_p(Y.data_ptr()), n, c, h, w, len(win), C1, C2, cov_norm,
+    return _lib.SpfSsim(_lib.ptr(X), _lib.ptr(Y), n, c, h, w, len(win), C1, C2, cov_norm,
                         int(bool(size_average)), int(bool(nonnegative)), arr)
 
 
@@ -94,11 +94,7 @@ def ssim_forward(X: Tensor, Y: Tensor, win: Sequence[float], C1: float, C2: floa
     plane_mean = torch.empty((n, c), dtype=torch.float32, device=dev)
     out = torch.empty(() if size_average else (n,), dtype=torch.float32, device=dev)
     args = _args(X, Y, win, C1, C2, cov_norm, size_average, nonnegative)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.spf_ssim_forward(C.byref(args), C.c_void_p(partial.data_ptr()),
-                                        C.c_void_p(plane_mean.data_ptr()), C.c_void_p(out.data_ptr()), stream),
-                   "spf_ssim_forward")
+    _lib.launch("spf_ssim_forward", dev, args, partial, plane_mean, out)
     return out, plane_mean
 
 
@@ -117,19 +113,11 @@ class _Ssim(torch.autograd.Function):
         x, y, plane_mean = ctx.saved_tensors
         win, C1, C2, cov_norm, size_average, nonnegative = ctx.params
         need_x, need_y = ctx.needs_input_grad[:2]
-        dev = x.device
         g = grad.to(torch.float32).contiguous()
         dx = torch.empty_like(x) if need_x else None
         dy = torch.empty_like(y) if need_y else None
-
-        def ptr(t):
-            return C.c_void_p(t.data_ptr() if t is not None else None)
-        lib = _lib.load()
-        args = _args(x, y, win, C1, C2, cov_norm, size_average, nonnegative)
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(lib.spf_ssim_backward(C.byref(args), ptr(plane_mean), ptr(g), ptr(dx), ptr(dy), stream),
-                       "spf_ssim_backward")
+        _lib.launch("spf_ssim_backward", x.device, _args(x, y, win, C1, C2, cov_norm, size_average, nonnegative),
+                    plane_mean, g, dx, dy)
         return dx, dy, None, None, None, None, None, None
 
 

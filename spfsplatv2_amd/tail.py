@@ -17,7 +17,6 @@ Not served: ``num_surfaces != 1``, 16-bit tensors, CPU tensors, ``sh_degree > 4`
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Sequence
 
 import torch
@@ -59,14 +58,6 @@ def _grad(g):
     return g if g.data_ptr() % 16 == 0 else g.clone()
 
 
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def sh_mask(sh_degree: int) -> Tensor:
     """gaussian_adapter.py:41-48: band l >= 1 is scaled by 0.1 * 0.25 ** l."""
     mask = torch.ones(((sh_degree + 1) ** 2,), dtype=torch.float32)
@@ -103,7 +94,6 @@ class _TailFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, v, exponent, eps, mask, split, *tensors):
         ctx.set_materialize_grads(False)
-        lib = _lib.load()
         pts = [_dense(t.detach()) for t in tensors[:v]]
         raw = [_dense(t.detach()) for t in tensors[v:]]
         b, c, h, w = raw[0].shape
@@ -113,10 +103,8 @@ class _TailFn(torch.autograd.Function):
         scales, rot = torch.empty((b, G, 3), **f32), torch.empty((b, G, 4), **f32)
         sh = torch.empty((b, G, 3, 16 if split else K), **f32)
         sh_hi = torch.empty((b, G, 3, 9), **f32) if split else None
-        args = _tail_args(raw, pts, mask, exponent, eps)
-        with torch.cuda.device(raw[0].device):
-            _lib.check(lib.spf_tail_forward(C.byref(args), _p(means), _p(opac), _p(scales), _p(rot), _p(sh), _p(sh_hi),
-                                            _stream(raw[0].device)), "spf_tail_forward")
+        _lib.launch("spf_tail_forward", raw[0].device, _tail_args(raw, pts, mask, exponent, eps), means, opac, scales, rot,
+                    sh, sh_hi)
         ctx.save_for_backward(mask, *raw)
         ctx.v, ctx.exponent, ctx.eps, ctx.split = v, float(exponent), float(eps), bool(split)
         return (means, opac, scales, rot, sh, sh_hi) if split else (means, opac, scales, rot, sh)
@@ -124,7 +112,6 @@ class _TailFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g_means, g_opac, g_scales, g_rot, g_sh, g_sh_hi=None):
-        lib = _lib.load()
         mask, *raw = ctx.saved_tensors
         b, c, h, w = raw[0].shape
         # (a decoder that evaluates to degree 3 hands back NO gradient for the band-4 plane -- None here -- and the kernel
@@ -135,10 +122,8 @@ class _TailFn(torch.autograd.Function):
         d_pts = [torch.empty((b, h, w, 3), dtype=torch.float32, device=t.device) for t in raw]
         for i in range(ctx.v):
             out.d_raw[i], out.d_pts[i] = d_raw[i].data_ptr(), d_pts[i].data_ptr()
-        args = _tail_args(raw, None, mask, ctx.exponent, ctx.eps)
-        with torch.cuda.device(raw[0].device):
-            _lib.check(lib.spf_tail_backward(C.byref(args), *(_p(g) for g in ups), 1 if ctx.split else 0, C.byref(out),
-                                             _stream(raw[0].device)), "spf_tail_backward")
+        _lib.launch("spf_tail_backward", raw[0].device, _tail_args(raw, None, mask, ctx.exponent, ctx.eps), *ups,
+                    1 if ctx.split else 0, out)
         return (None, None, None, None, None, *d_pts, *d_raw)
 
 
@@ -216,7 +201,6 @@ def map_pdf_to_opacity(pdf: Tensor, global_step: int, opacity_mapping) -> Tensor
 class _OpacityFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, exponent):
-        lib = _lib.load()
         x = logits.detach()
         # one element stride over the whole view (channel 0 of a dense channels-last tensor): read in place
         stride = _uniform_stride(x)
@@ -225,9 +209,7 @@ class _OpacityFn(torch.autograd.Function):
             dense_copies["bytes"] += x.numel() * x.element_size()
             x, stride = x.contiguous(), 1
         out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.spf_opacity_forward(_p(x), stride, x.numel(), exponent, _p(out), _stream(x.device)),
-                       "spf_opacity_forward")
+        _lib.launch("spf_opacity_forward", x.device, x, stride, x.numel(), exponent, out)
         ctx.save_for_backward(x)
         ctx.stride, ctx.exponent = stride, exponent
         return out
@@ -235,13 +217,10 @@ class _OpacityFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        lib = _lib.load()
         (x,) = ctx.saved_tensors
         g = g.contiguous().float()
         dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.spf_opacity_backward(_p(x), ctx.stride, x.numel(), ctx.exponent, _p(g), _p(dx),
-                                                _stream(x.device)), "spf_opacity_backward")
+        _lib.launch("spf_opacity_backward", x.device, x, ctx.stride, x.numel(), ctx.exponent, g, dx)
         return dx, None
 
 
