@@ -966,6 +966,74 @@ int spf_opacity_forward(const float* logits, int64_t stride, int64_t n, float ex
 int spf_opacity_backward(const float* logits, int64_t stride, int64_t n, float exponent, const float* dL_dopacities,
                          float* dL_dlogits, void* stream);
 
+/* ---- the pose heads between their GEMMs (spfsplatv2_amd/csrc/posehead.hip) ---------------------------------------------
+ * The MLP PoseHead (heads/pose_head.py) and VGGT's CameraHead (vggt/heads/camera_head.py): token pooling, the head's
+ * tail, embed + SiLU, the adaptive LayerNorm, attention over the views and activate_pose, forward and backward.  float32
+ * only; every pointer of the pool, modulate and attention calls is 16-byte aligned, the others 4-byte.  Nothing is
+ * allocated or synchronised; no atomics: every sum has one order, two runs agree bitwise.  Argument errors return
+ * SPF_E_INVALID (spf_last_error) before anything is launched. */
+#define SPF_POSEHEAD_MAX_S 32
+#define SPF_POSEHEAD_MAX_ROWS 65535
+enum { SPF_POSE_ACT_LINEAR = 0, SPF_POSE_ACT_INV_LOG = 1, SPF_POSE_ACT_EXP = 2, SPF_POSE_ACT_RELU = 3 };
+typedef struct SpfPosePool {
+    const float* src[2];          /* source s: [rows, L, C[s]] with unit channel stride; src[1] NULL: one source.  The
+                                   * backward reads no source: both may be NULL there */
+    int64_t inner[2], stride[2], outer_stride[2];   /* row i of source s starts at (i / inner) * outer_stride +
+                                                     * (i % inner) * stride (floats, multiples of 4; inner >= 1) */
+    int64_t tok_stride[2];        /* floats between two tokens of a row, a multiple of 4 */
+    int32_t C[2];                 /* multiples of 4, 4 .. 2^20; C[1] is ignored without a second source */
+    int64_t rows;                 /* 1 .. SPF_POSEHEAD_MAX_ROWS */
+    int32_t L;                    /* tokens per row, 1 .. 2^20; L = 1 copies */
+    int32_t reserved;
+} SpfPosePool;
+/* feat [rows, C[0] + C[1]] dense: the mean over the L tokens, source 0's channels first */
+int spf_posehead_pool_forward(const SpfPosePool* args, float* feat, void* stream);
+/* d_src0 [rows, L, C[0]], d_src1 [rows, L, C[1]] dense (d_src1 with a second source and only then; whether there is one
+ * is read from d_src1 here): d_feat / L at every token */
+int spf_posehead_pool_backward(const SpfPosePool* args, const float* d_feat, float* d_src0, float* d_src1, void* stream);
+typedef struct SpfPoseEncode {
+    int64_t rows;                 /* 1 .. 2^24 */
+    int64_t out_inner, out_stride, out_outer_stride;   /* pose row i starts at (i / out_inner) * out_outer_stride +
+                                                        * (i % out_inner) * out_stride: views 1.. of a [b, v, 9] tensor */
+    int32_t homogeneous;          /* t is [rows, 4] and out[6:9] = t[:3] / h, h = min(softplus(t[3], beta) +
+                                   * max_inv_scale, min_inv_scale); else t is [rows, 3], copied */
+    float beta, max_inv_scale, min_inv_scale;
+} SpfPoseEncode;
+/* rot [rows, 6] and t dense; out: the 9-float pose rows (rot, then the translation), addressed as above.  softplus is
+ * torch's: x where beta x > 20. */
+int spf_posehead_encode_forward(const SpfPoseEncode* args, const float* rot, const float* t, float* out, void* stream);
+/* d_out addressed as out was; d_rot [rows, 6], d_t [rows, 3 or 4] dense.  Nothing flows through a clamped h. */
+int spf_posehead_encode_backward(const SpfPoseEncode* args, const float* t, const float* d_out, float* d_rot, float* d_t,
+                                 void* stream);
+/* out [rows, C] = SiLU(p W^T + b): p [rows, 9] dense, or with `broadcast` ONE row of 9 floats used for every row;
+ * W [C, 9], b [C]; rows 1 .. SPF_POSEHEAD_MAX_ROWS, C 1 .. 2^20 */
+int spf_posehead_embed_silu_forward(const float* p, int32_t broadcast, const float* W, const float* b, int64_t rows,
+                                    int32_t C, float* out, void* stream);
+/* The pre-activation is recomputed.  dW [C, 9], db [C] (both always written: a thread per column sums down the rows);
+ * dp: NULL, or [rows, 9] -- with `broadcast` [9], summed over the rows too. */
+int spf_posehead_embed_silu_backward(const float* p, int32_t broadcast, const float* W, const float* b, const float* dout,
+                                     int64_t rows, int32_t C, float* dW, float* db, float* dp, void* stream);
+/* out [rows, C] = gate * (LN(x) * (1 + scale) + shift) + x with mod [rows, 3 C] = shift | scale | gate (the column
+ * thirds), LN without parameters, the biased variance from the centred values; C as SpfBlockNorm's, rows 1 .. 2^30 */
+int spf_posehead_modulate_forward(const float* x, const float* mod, int64_t rows, int32_t C, float eps, float* out,
+                                  void* stream);
+/* dx [rows, C] and dmod [rows, 3 C] in mod's layout (every element written); the row statistics are recomputed */
+int spf_posehead_modulate_backward(const float* x, const float* mod, const float* dout, int64_t rows, int32_t C, float eps,
+                                   float* dx, float* dmod, void* stream);
+/* out [B, S, H D] = softmax(q k^T / sqrt(D)) v per (batch item, head) of the packed qkv [B, S, 3, H, D]; D is 64 or 128,
+ * 1 <= S <= SPF_POSEHEAD_MAX_S, B H < 2^31 / 3.  No rotation, no mask, no q / k norm. */
+int spf_posehead_attn_forward(const float* qkv, int32_t B, int32_t S, int32_t H, int32_t D, float* out, void* stream);
+/* dqkv [B, S, 3, H, D], every element written; the probabilities are recomputed */
+int spf_posehead_attn_backward(const float* qkv, const float* dout, int32_t B, int32_t S, int32_t H, int32_t D,
+                               float* dqkv, void* stream);
+/* pred [rows, 9] = prev + delta (prev NULL: delta), out [rows, 9] = the SPF_POSE_ACT_* of columns 0:3 (trans_act),
+ * 3:7 (quat_act), 7:9 (fl_act) of pred; rows 1 .. 2^24 */
+int spf_posehead_activate_forward(const float* prev, const float* delta, int64_t rows, int32_t trans_act, int32_t quat_act,
+                                  int32_t fl_act, float* pred, float* out, void* stream);
+/* d_delta = d_pred + d_out * act'(pred); d_pred or d_out may be NULL (zero), not both */
+int spf_posehead_activate_backward(const float* pred, const float* d_pred, const float* d_out, int64_t rows,
+                                   int32_t trans_act, int32_t quat_act, int32_t fl_act, float* d_delta, void* stream);
+
 /* Per-stage device timing with HIP events recorded on the launch stream around every kernel
  * stage.  spf_stage_timing_enable(mask) clears the log and starts recording the stages whose bit
  * (1 << SPF_STAGE_x) is set in `mask` (0 = off, -1 = all) (up to

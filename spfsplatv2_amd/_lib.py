@@ -163,6 +163,22 @@ class SpfTailGrads(C.Structure):
     _fields_ = [("d_raw", C.c_void_p * TAIL_MAX_VIEWS), ("d_pts", C.c_void_p * TAIL_MAX_VIEWS)]
 
 
+POSEHEAD_MAX_S = 32
+POSEHEAD_MAX_ROWS = 65535
+POSE_ACTS = {"linear": 0, "inv_log": 1, "exp": 2, "relu": 3}
+
+
+class SpfPosePool(C.Structure):
+    _fields_ = [("src", C.c_void_p * 2), ("inner", C.c_int64 * 2), ("stride", C.c_int64 * 2),
+                ("outer_stride", C.c_int64 * 2), ("tok_stride", C.c_int64 * 2), ("C", C.c_int32 * 2), ("rows", C.c_int64),
+                ("L", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SpfPoseEncode(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("out_inner", C.c_int64), ("out_stride", C.c_int64), ("out_outer_stride", C.c_int64),
+                ("homogeneous", C.c_int32), ("beta", C.c_float), ("max_inv_scale", C.c_float), ("min_inv_scale", C.c_float)]
+
+
 # Every symbol include/spfsplat_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "spf_abi_version": (C.c_int, []),
@@ -291,6 +307,27 @@ SYMBOLS = {
                                     C.c_void_p, C.c_int32, C.POINTER(SpfTailGrads), C.c_void_p]),
     "spf_opacity_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "spf_opacity_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_posehead_pool_forward": (C.c_int, [C.POINTER(SpfPosePool), C.c_void_p, C.c_void_p]),
+    "spf_posehead_pool_backward": (C.c_int, [C.POINTER(SpfPosePool), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_posehead_encode_forward": (C.c_int, [C.POINTER(SpfPoseEncode), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_posehead_encode_backward": (C.c_int, [C.POINTER(SpfPoseEncode), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
+    "spf_posehead_embed_silu_forward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                                  C.c_void_p, C.c_void_p]),
+    "spf_posehead_embed_silu_backward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_posehead_modulate_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p,
+                                                C.c_void_p]),
+    "spf_posehead_modulate_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_posehead_attn_forward": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                            C.c_void_p]),
+    "spf_posehead_attn_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_void_p]),
+    "spf_posehead_activate_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_posehead_activate_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                                 C.c_int32, C.c_void_p, C.c_void_p]),
     "spf_stage_timing_enable": (C.c_int, [C.c_int32]),
     "spf_stage_timing_sample_every": (C.c_int, [C.c_int32]),
     "spf_stage_times_ms": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_int32)]),

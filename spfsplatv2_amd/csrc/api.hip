@@ -1534,6 +1534,165 @@ int spf_opacity_backward(const float* logits, int64_t stride, int64_t n, float e
     return SPF_OK;
 }
 
+// ---- the pose heads (posehead.hip) ---------------------------------------------------------------------------------------
+static bool pose_rows_ok(int64_t inner, int64_t stride, int64_t outer_stride, int64_t unit) {
+    return inner >= 1 && stride >= 0 && outer_stride >= 0 && stride % unit == 0 && outer_stride % unit == 0;
+}
+
+static int pose_pool_check(const char* what, const SpfPosePool* a, int sources) {
+    if (!a) return fail(SPF_E_INVALID, "%s: args is null", what);
+    if (a->rows < 1 || a->rows > SPF_POSEHEAD_MAX_ROWS || a->L < 1 || a->L > (1 << 20))
+        return fail(SPF_E_INVALID, "%s: rows must be 1 .. %d and L 1 .. 2^20 (got %lld, %d)", what, SPF_POSEHEAD_MAX_ROWS,
+                    (long long)a->rows, a->L);
+    for (int s = 0; s < sources; ++s) {
+        if (a->C[s] < 4 || a->C[s] > (1 << 20) || a->C[s] % 4 != 0)
+            return fail(SPF_E_INVALID, "%s: the width of source %d must be a multiple of 4 in 4 .. 2^20 (got %d)", what, s, a->C[s]);
+    }
+    return SPF_OK;
+}
+
+int spf_posehead_pool_forward(const SpfPosePool* a, float* feat, void* stream_) {
+    const int sources = a && a->src[1] ? 2 : 1;
+    if (const int rc = pose_pool_check("posehead_pool_forward", a, sources)) return rc;
+    if (!a->src[0] || !feat) return fail(SPF_E_INVALID, "posehead_pool_forward: null pointer (src[0] or feat)");
+    for (int s = 0; s < sources; ++s)
+        if (!pose_rows_ok(a->inner[s], a->stride[s], a->outer_stride[s], 4) || a->tok_stride[s] < 0 || a->tok_stride[s] % 4 != 0)
+            return fail(SPF_E_INVALID, "posehead_pool_forward: inner must be >= 1 and every stride a non-negative multiple of 4 floats (source %d)", s);
+    if (!aligned<16>({a->src[0], a->src[1], feat})) return fail(SPF_E_INVALID, "posehead_pool_forward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_posehead_pool_fwd(*a, feat, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_posehead_pool_backward(const SpfPosePool* a, const float* d_feat, float* d_src0, float* d_src1, void* stream_) {
+    if (const int rc = pose_pool_check("posehead_pool_backward", a, d_src1 ? 2 : 1)) return rc;
+    if (!d_feat || !d_src0) return fail(SPF_E_INVALID, "posehead_pool_backward: null pointer (d_feat or d_src0)");
+    if (!aligned<16>({d_feat, d_src0, d_src1})) return fail(SPF_E_INVALID, "posehead_pool_backward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_posehead_pool_bwd(*a, d_feat, d_src0, d_src1, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+static int pose_encode_check(const char* what, const SpfPoseEncode* a) {
+    if (!a) return fail(SPF_E_INVALID, "%s: args is null", what);
+    if (a->rows < 1 || a->rows > (1 << 24)) return fail(SPF_E_INVALID, "%s: rows must be 1 .. 2^24 (got %lld)", what, (long long)a->rows);
+    if (!pose_rows_ok(a->out_inner, a->out_stride, a->out_outer_stride, 1))
+        return fail(SPF_E_INVALID, "%s: out_inner must be >= 1 and the strides non-negative", what);
+    if (a->homogeneous && (!(a->beta > 0.f) || !(a->max_inv_scale > 0.f) || !(a->min_inv_scale >= a->max_inv_scale) || !(a->min_inv_scale < 3.0e38f) || !(a->beta < 3.0e38f)))
+        return fail(SPF_E_INVALID, "%s: beta and max_inv_scale must be positive and finite, min_inv_scale finite and not below max_inv_scale", what);
+    return SPF_OK;
+}
+
+int spf_posehead_encode_forward(const SpfPoseEncode* a, const float* rot, const float* t, float* out, void* stream_) {
+    if (const int rc = pose_encode_check("posehead_encode_forward", a)) return rc;
+    if (!rot || !t || !out) return fail(SPF_E_INVALID, "posehead_encode_forward: null pointer (rot, t or out)");
+    if (!aligned<4>({rot, t, out})) return fail(SPF_E_INVALID, "posehead_encode_forward: tensors must be 4-byte aligned");
+    SPF_HIP(spf::launch_posehead_encode_fwd(*a, rot, t, out, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_posehead_encode_backward(const SpfPoseEncode* a, const float* t, const float* d_out, float* d_rot, float* d_t,
+                                 void* stream_) {
+    if (const int rc = pose_encode_check("posehead_encode_backward", a)) return rc;
+    if ((a->homogeneous && !t) || !d_out || !d_rot || !d_t) return fail(SPF_E_INVALID, "posehead_encode_backward: null pointer (t, d_out, d_rot or d_t)");
+    if (!aligned<4>({t, d_out, d_rot, d_t})) return fail(SPF_E_INVALID, "posehead_encode_backward: tensors must be 4-byte aligned");
+    SPF_HIP(spf::launch_posehead_encode_bwd(*a, t, d_out, d_rot, d_t, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+static int pose_embed_check(const char* what, int64_t rows, int32_t C) {
+    if (rows < 1 || rows > SPF_POSEHEAD_MAX_ROWS || C < 1 || C > (1 << 20))
+        return fail(SPF_E_INVALID, "%s: rows must be 1 .. %d and C 1 .. 2^20 (got %lld, %d)", what, SPF_POSEHEAD_MAX_ROWS, (long long)rows, C);
+    return SPF_OK;
+}
+
+int spf_posehead_embed_silu_forward(const float* p, int32_t broadcast, const float* W, const float* b, int64_t rows,
+                                    int32_t C, float* out, void* stream_) {
+    if (const int rc = pose_embed_check("posehead_embed_silu_forward", rows, C)) return rc;
+    if (!p || !W || !b || !out) return fail(SPF_E_INVALID, "posehead_embed_silu_forward: null pointer (p, W, b or out)");
+    if (!aligned<4>({p, W, b, out})) return fail(SPF_E_INVALID, "posehead_embed_silu_forward: tensors must be 4-byte aligned");
+    SPF_HIP(spf::launch_posehead_embed_fwd(p, broadcast != 0, W, b, rows, C, out, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_posehead_embed_silu_backward(const float* p, int32_t broadcast, const float* W, const float* b, const float* dout,
+                                     int64_t rows, int32_t C, float* dW, float* db, float* dp, void* stream_) {
+    if (const int rc = pose_embed_check("posehead_embed_silu_backward", rows, C)) return rc;
+    if (!p || !W || !b || !dout || !dW || !db) return fail(SPF_E_INVALID, "posehead_embed_silu_backward: null pointer (p, W, b, dout, dW or db)");
+    if (!aligned<4>({p, W, b, dout, dW, db, dp})) return fail(SPF_E_INVALID, "posehead_embed_silu_backward: tensors must be 4-byte aligned");
+    SPF_HIP(spf::launch_posehead_embed_bwd(p, broadcast != 0, W, b, dout, rows, C, dW, db, dp, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_posehead_modulate_forward(const float* x, const float* mod, int64_t rows, int32_t C, float eps, float* out,
+                                  void* stream_) {
+    if (!block_sizes_ok(rows, C)) return block_sizes_fail("posehead_modulate_forward", rows, C);
+    if (!(eps >= 0.f) || !(eps < 3.0e38f)) return fail(SPF_E_INVALID, "posehead_modulate_forward: eps must be finite and not negative");
+    if (!x || !mod || !out) return fail(SPF_E_INVALID, "posehead_modulate_forward: null pointer (x, mod or out)");
+    if (!aligned<16>({x, mod, out})) return fail(SPF_E_INVALID, "posehead_modulate_forward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_posehead_modulate_fwd(x, mod, rows, C, eps, out, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_posehead_modulate_backward(const float* x, const float* mod, const float* dout, int64_t rows, int32_t C, float eps,
+                                   float* dx, float* dmod, void* stream_) {
+    if (!block_sizes_ok(rows, C)) return block_sizes_fail("posehead_modulate_backward", rows, C);
+    if (!(eps >= 0.f) || !(eps < 3.0e38f)) return fail(SPF_E_INVALID, "posehead_modulate_backward: eps must be finite and not negative");
+    if (!x || !mod || !dout || !dx || !dmod) return fail(SPF_E_INVALID, "posehead_modulate_backward: null pointer");
+    if (!aligned<16>({x, mod, dout, dx, dmod})) return fail(SPF_E_INVALID, "posehead_modulate_backward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_posehead_modulate_bwd(x, mod, dout, rows, C, eps, dx, dmod, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+static int pose_attn_check(const char* what, int32_t B, int32_t S, int32_t H, int32_t D) {
+    if (D != 64 && D != 128) return fail(SPF_E_INVALID, "%s: the head dim must be 64 or 128 (got %d)", what, D);
+    if (S < 1 || S > SPF_POSEHEAD_MAX_S) return fail(SPF_E_INVALID, "%s: S must be 1 .. %d (got %d)", what, SPF_POSEHEAD_MAX_S, S);
+    if (B < 1 || H < 1 || (int64_t)B * H > ((int64_t)1 << 31) / 3 - 1)
+        return fail(SPF_E_INVALID, "%s: B and H must be positive and B H below 2^31 / 3 (got %d, %d)", what, B, H);
+    return SPF_OK;
+}
+
+int spf_posehead_attn_forward(const float* qkv, int32_t B, int32_t S, int32_t H, int32_t D, float* out, void* stream_) {
+    if (const int rc = pose_attn_check("posehead_attn_forward", B, S, H, D)) return rc;
+    if (!qkv || !out) return fail(SPF_E_INVALID, "posehead_attn_forward: null pointer (qkv or out)");
+    if (!aligned<16>({qkv, out})) return fail(SPF_E_INVALID, "posehead_attn_forward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_posehead_attn_fwd(qkv, B, S, H, D, out, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_posehead_attn_backward(const float* qkv, const float* dout, int32_t B, int32_t S, int32_t H, int32_t D, float* dqkv,
+                               void* stream_) {
+    if (const int rc = pose_attn_check("posehead_attn_backward", B, S, H, D)) return rc;
+    if (!qkv || !dout || !dqkv) return fail(SPF_E_INVALID, "posehead_attn_backward: null pointer (qkv, dout or dqkv)");
+    if (!aligned<16>({qkv, dout, dqkv})) return fail(SPF_E_INVALID, "posehead_attn_backward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_posehead_attn_bwd(qkv, dout, B, S, H, D, dqkv, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+static int pose_act_check(const char* what, int64_t rows, int32_t trans_act, int32_t quat_act, int32_t fl_act) {
+    if (rows < 1 || rows > (1 << 24)) return fail(SPF_E_INVALID, "%s: rows must be 1 .. 2^24 (got %lld)", what, (long long)rows);
+    for (const int32_t act : {trans_act, quat_act, fl_act})
+        if (act < SPF_POSE_ACT_LINEAR || act > SPF_POSE_ACT_RELU)
+            return fail(SPF_E_INVALID, "%s: unknown activation %d (SPF_POSE_ACT_*)", what, act);
+    return SPF_OK;
+}
+
+int spf_posehead_activate_forward(const float* prev, const float* delta, int64_t rows, int32_t trans_act, int32_t quat_act,
+                                  int32_t fl_act, float* pred, float* out, void* stream_) {
+    if (const int rc = pose_act_check("posehead_activate_forward", rows, trans_act, quat_act, fl_act)) return rc;
+    if (!delta || !pred || !out) return fail(SPF_E_INVALID, "posehead_activate_forward: null pointer (delta, pred or out)");
+    if (!aligned<4>({prev, delta, pred, out})) return fail(SPF_E_INVALID, "posehead_activate_forward: tensors must be 4-byte aligned");
+    SPF_HIP(spf::launch_posehead_activate_fwd(prev, delta, rows, trans_act, quat_act, fl_act, pred, out, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_posehead_activate_backward(const float* pred, const float* d_pred, const float* d_out, int64_t rows,
+                                   int32_t trans_act, int32_t quat_act, int32_t fl_act, float* d_delta, void* stream_) {
+    if (const int rc = pose_act_check("posehead_activate_backward", rows, trans_act, quat_act, fl_act)) return rc;
+    if (!pred || !d_delta || (!d_pred && !d_out)) return fail(SPF_E_INVALID, "posehead_activate_backward: null pointer (pred, d_delta, or both gradients)");
+    if (!aligned<4>({pred, d_pred, d_out, d_delta})) return fail(SPF_E_INVALID, "posehead_activate_backward: tensors must be 4-byte aligned");
+    SPF_HIP(spf::launch_posehead_activate_bwd(pred, d_pred, d_out, rows, trans_act, quat_act, fl_act, d_delta, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
 int spf_stage_timing_enable(int32_t mask) {
     g_timing = (uint32_t)mask;
     if (g_timing)

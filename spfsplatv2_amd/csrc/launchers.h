@@ -120,4 +120,24 @@ hipError_t launch_tail_bwd(const SpfTail& a, const SpfTailGrads& out, const floa
 hipError_t launch_opacity_fwd(const float* x, int64_t stride, int64_t n, float e, float* y, hipStream_t stream);
 hipError_t launch_opacity_bwd(const float* x, int64_t stride, int64_t n, float e, const float* dy, float* dx,
                               hipStream_t stream);
+hipError_t launch_posehead_pool_fwd(const SpfPosePool& a, float* feat, hipStream_t st);
+hipError_t launch_posehead_pool_bwd(const SpfPosePool& a, const float* d_feat, float* d0, float* d1, hipStream_t st);
+hipError_t launch_posehead_encode_fwd(const SpfPoseEncode& a, const float* rot, const float* t, float* out, hipStream_t st);
+hipError_t launch_posehead_encode_bwd(const SpfPoseEncode& a, const float* t, const float* d_out, float* d_rot, float* d_t,
+                                      hipStream_t st);
+hipError_t launch_posehead_embed_fwd(const float* p, int bcast, const float* W, const float* b, int64_t rows, int C,
+                                     float* out, hipStream_t st);
+hipError_t launch_posehead_embed_bwd(const float* p, int bcast, const float* W, const float* b, const float* dout,
+                                     int64_t rows, int C, float* dW, float* db, float* dp, hipStream_t st);
+hipError_t launch_posehead_modulate_fwd(const float* x, const float* mod, int64_t rows, int C, float eps, float* out,
+                                        hipStream_t st);
+hipError_t launch_posehead_modulate_bwd(const float* x, const float* mod, const float* dout, int64_t rows, int C, float eps,
+                                        float* dx, float* dmod, hipStream_t st);
+hipError_t launch_posehead_attn_fwd(const float* qkv, int B, int S, int H, int D, float* out, hipStream_t st);
+hipError_t launch_posehead_attn_bwd(const float* qkv, const float* dout, int B, int S, int H, int D, float* dqkv,
+                                    hipStream_t st);
+hipError_t launch_posehead_activate_fwd(const float* prev, const float* delta, int64_t rows, int trans_act, int quat_act,
+                                        int fl_act, float* pred, float* out, hipStream_t st);
+hipError_t launch_posehead_activate_bwd(const float* pred, const float* d_pred, const float* d_out, int64_t rows,
+                                        int trans_act, int quat_act, int fl_act, float* d_delta, hipStream_t st);
 }  // namespace spf
