@@ -284,11 +284,33 @@ __device__ __forceinline__ void fwd_rows_tile(float4* s_p0, float2* s_p1, float4
 #define SPF_SCATTER4 1
 #endif
 __device__ __forceinline__ void scatter_box(uint32_t (*s_pm)[kBlock], int i, float gx, float gy, float r2, int X0, int Y0,
-                                            int xl, int yl, int bw, int bh) {
+                                            int xl, int yl, int bw, int bh, bool straight) {
     uint32_t* __restrict__ wp = s_pm[i >> 5] + yl * kTile + xl;
     const uint32_t bit = 1u << (i & 31);
     const float dx0 = (float)(X0 + xl) - gx;
     float dy = (float)(Y0 + yl) - gy;
+    // Straight line for a wave all of whose boxes fit 4 x 4 (`straight` is the same in every lane; lanes that are off
+    // do not vote): sixteen test-and-OR pairs under one lane predicate per row and per column -- no loop counters, no
+    // `k < left`, no back-edges.  The offsets are formed exactly as the loops below form them (dy by repeated + 1.f,
+    // dx0 + (float)k), so the candidate words are the same bit for bit.  Per slot: v_fma, v_cmp, four scalar
+    // instructions and the ds_or.  C2: forward 31.2 -> 30.1 M, backward 49.8 -> 47.5 M vector instructions per launch,
+    // step 0.353 -> 0.348 ms (DESIGN_EXPERIMENTS.md; footprints x 10, where every wave falls through to the loops, pay
+    // 0.2 % for the vote).
+    if (straight && lane_ballot(bw > 4 || bh > 4) == 0) {
+#pragma unroll
+        for (int y = 0; y < 4; ++y) {
+            const bool row = y < bh;
+            const float dy2 = dy * dy;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float d = dx0 + (float)k;
+                const bool in = !(fmaf(d, d, dy2) > r2);
+                if ((int)row & (int)(k < bw) & (int)in) atomicOr(&wp[y * kTile + k], bit);
+            }
+            dy += 1.f;
+        }
+        return;
+    }
 #if SPF_SCATTER4
     // Rows outside, FOUR columns per trip inside: a pixel-aligned footprint is 2 - 4 pixels wide, so the column loop of
     // the plain form ran once or twice per row and paid two branches and half a dozen scalar instructions per pixel for
@@ -348,8 +370,9 @@ __global__ __launch_bounds__(kBlock, STAGE == 256 ? 8 : 4) void spf_render_fwd_l
     const uint32_t* __restrict__ tile_flags, const uint32_t* __restrict__ counters, uint64_t capacity,
     const float* __restrict__ bg_all, float* __restrict__ image, float* __restrict__ depth_out,
     float* __restrict__ alpha_out, float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, int G, int H, int W,
-    int T, int tiles_x, int RT, uint32_t dense_thr_arg) {
+    int T, int tiles_x, int RT, uint32_t dense_thr_arg, int straight_arg) {
     const uint32_t dense_thr = dense_thr_arg;
+    const bool straight = straight_arg != 0;
     __shared__ float4 s_p0[STAGE];   // x, y | A', C'   (conic pre-scaled, see lists_power2)
     __shared__ float2 s_p1[STAGE];   // B', opacity   (8 bytes: with a float4 here the block is 20,752 bytes of LDS -- 7 per CU instead of 8)
     __shared__ float4 s_p2z[STAGE + 1];   // r, g | b, depth; record 0 is all zeros (see `next` below), entry i is record i + 1
@@ -420,7 +443,7 @@ __global__ __launch_bounds__(kBlock, STAGE == 256 ? 8 : 4) void spf_render_fwd_l
                 s_p2[e] = make_float4(ec[q].x, ec[q].y, ec[q].z, eb[q].z);
             }
             const TileBox tb = clipped_box(ea[q].x, ea[q].y, eb[q].w, X0, Y0);      // (no entry: r2 = -1 -> empty box)
-            scatter_box(s_pm, e, ea[q].x, ea[q].y, eb[q].w, X0, Y0, tb.xl, tb.yl, tb.bw, tb.bh);
+            scatter_box(s_pm, e, ea[q].x, ea[q].y, eb[q].w, X0, Y0, tb.xl, tb.yl, tb.bw, tb.bh, straight);
         }
         __syncthreads();
         if (!wave_done) {
@@ -723,8 +746,9 @@ __global__ __launch_bounds__(kBlock, BPC) void spf_render_bwd_lists_kernel(
     const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dimage, const float* __restrict__ dL_ddepth,
     const float* __restrict__ dL_dalpha, const uint2* __restrict__ pinfo,
     float* __restrict__ gpair, int G, int H, int W, int T, int tiles_x, int RT, uint32_t dense_thr_arg,
-    const uint32_t* __restrict__ counters, uint64_t capacity) {
+    const uint32_t* __restrict__ counters, uint64_t capacity, int straight_arg) {
     (void)capacity;
+    const bool straight = straight_arg != 0;
     if (counters[2] != 0u) return;           // failed plan: nothing was rendered; the projection backward poisons the gradients
     const uint32_t dense_thr = dense_thr_arg;
     __shared__ float4 s_p0[kRoundL];                 // x, y | A', C'   (as in the forward)
@@ -854,7 +878,7 @@ __global__ __launch_bounds__(kBlock, BPC) void spf_render_bwd_lists_kernel(
 #pragma unroll
         for (int k = 0; k < kPool / kBlock; ++k) s_pool[k * kBlock + tid] = make_float2(0.f, 0.f);
         // ---- phase A (the candidate words were cleared before the prefix-sum barrier above) ----
-        if (acc) scatter_box(s_pm, tid, a.x, a.y, b.w, X0, Y0, xl, yl, bw, bh);
+        if (acc) scatter_box(s_pm, tid, a.x, a.y, b.w, X0, Y0, xl, yl, bw, bh, straight);
         __syncthreads();
         const int cnt = (int)(s_wacc[0] + s_wacc[1] + s_wacc[2] + s_wacc[3]);   // >= 1: one entry needs <= 256 slots
         // ---- phase B: ascending bits = descending list position ----
@@ -1012,6 +1036,10 @@ __global__ __launch_bounds__(kBlock, BPC) void spf_render_bwd_lists_kernel(
 }
 
 // ---- launchers ------------------------------------------------------------------------------------
+static int scatter_straight() {                          // SPF_SCATTER_STRAIGHT=0 pins scatter_box's loops (A/B runs, tests; read per call)
+    const char* const e = getenv("SPF_SCATTER_STRAIGHT");
+    return e ? atoi(e) != 0 : 1;
+}
 uint32_t dense_threshold_fwd();
 uint32_t dense_threshold() {                       // (read per call: the tests flip it)
     const char* const e = getenv("SPF_DENSE_AREA");
@@ -1041,14 +1069,15 @@ hipError_t launch_render_fwd(const SpfDims& d, const SpfInputs& in, const SpfSta
     const int grid = (RT + 7) / 8 * 8;
     const char* const fe = getenv("SPF_FWD_STAGE");           // ("256" / "512" pins the instantiation: experiments, tests)
     const int stage = fe ? atoi(fe) : (RT <= kFwdLongRoundsMaxTiles ? 512 : 256);
+    const int straight = scatter_straight();
     if (stage == 512)
         spf_render_fwd_lists_kernel<512><<<grid, kBlock, 0, stream>>>(
             st.rec, st.pairs, tlo, st.tile_flags, st.counters, capacity, in.bg, out.image, out.depth,
-            out.alpha, st.final_T, st.n_contrib, d.G, d.H, d.W, T, tiles_x, RT, dense_threshold_fwd());
+            out.alpha, st.final_T, st.n_contrib, d.G, d.H, d.W, T, tiles_x, RT, dense_threshold_fwd(), straight);
     else
         spf_render_fwd_lists_kernel<256><<<grid, kBlock, 0, stream>>>(
             st.rec, st.pairs, tlo, st.tile_flags, st.counters, capacity, in.bg, out.image, out.depth,
-            out.alpha, st.final_T, st.n_contrib, d.G, d.H, d.W, T, tiles_x, RT, dense_threshold_fwd());
+            out.alpha, st.final_T, st.n_contrib, d.G, d.H, d.W, T, tiles_x, RT, dense_threshold_fwd(), straight);
     return hipGetLastError();
 }
 
@@ -1065,7 +1094,7 @@ static void launch_render_bwd_t(const SpfDims& d, const SpfInputs& in, const Spf
 #define SPF_BWD_LISTS(RL, PL, BPC)                                                                                      \
     spf_render_bwd_lists_kernel<DG, RL, PL, BPC><<<grid, kBlock, 0, stream>>>(                                            \
         st.rec, st.pairs, tlo, st.tile_flags, in.bg, st.final_T, st.n_contrib, g.dL_dimage, g.dL_ddepth, g.dL_dalpha,     \
-        pinfo, g.gpair, d.G, d.H, d.W, T, tiles_x, RT, dense_threshold(), st.counters, capacity)
+        pinfo, g.gpair, d.G, d.H, d.W, T, tiles_x, RT, dense_threshold(), st.counters, capacity, scatter_straight())
     if (shape == 256) SPF_BWD_LISTS(256, 2560, 3);
     else if (shape == 224) SPF_BWD_LISTS(224, 1792, 4);
     else SPF_BWD_LISTS(192, 1536, 5);
