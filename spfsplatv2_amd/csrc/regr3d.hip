@@ -148,10 +148,11 @@ __global__ __launch_bounds__(kBlock) void spf_regr3d_hist_kernel(SpfRegr3d a, in
     }
 }
 
-// torch's lerp (aten/src/ATen/native/Lerp.h) in float32
+// torch's lerp (aten/src/ATen/native/Lerp.h) in float32: the difference and 1 - w are rounded, the multiply-add is ONE
+// fused operation, as torch's kernels form it (torch.quantile on the CPU gives these bits; tests/test_regr3d_exact.py)
 __device__ __forceinline__ float regr_lerp(float lo, float hi, float w) {
     const float d = __fsub_rn(hi, lo);
-    return w < 0.5f ? __fadd_rn(lo, __fmul_rn(w, d)) : __fsub_rn(hi, __fmul_rn(d, __fsub_rn(1.f, w)));
+    return w < 0.5f ? __fmaf_rn(w, d, lo) : __fmaf_rn(-d, __fsub_rn(1.f, w), hi);
 }
 
 // One block per row, wave t = rank t.

@@ -18,7 +18,10 @@ reference) decides the same masks whenever the order statistics either side of e
 than float32 rounding moves them: rank_gaps() reports those gaps, clip_gap() the distance of the nearest norm to
 dist_clip, and the exact gates of the tests (n_valid, zero gradients at invalid points) use only inputs where they are
 >= 1e-5 relative.  Gradients come from autograd in float64, which follows torch's rules by construction: zero at
-|x| = 0 (vector_norm), nothing for invalid points, and both the direct term and the path through nf_pr."""
+|x| = 0 (vector_norm), nothing for invalid points, and both the direct term and the path through nf_pr.
+
+The EXACT SIDE at the end of the file needs no such margin: for ground truth on the coordinate axes float64 and float32
+form the same norms, and thresholds, masks and counts are restated in float32, bit for bit (see there)."""
 from __future__ import annotations
 
 import math
@@ -95,9 +98,13 @@ def decided(case: dict, tol: float = 1e-5) -> bool:
 
 
 def regr3d_ref(gt_pts1, gt_pts2, pr_pts1, pr_pts2, conf1=None, conf2=None, *, dist_clip=None, disable_view1=False,
-               norm_mode="avg_dis", gt_scale=False) -> dict:
+               norm_mode="avg_dis", gt_scale=False, valid_override=None) -> dict:
     """Everything the tests compare, in float64: loss, grad (pr1, pr2), valid [2,B,H,W], n_valid [2,B], q [2,B,2],
-    nf_pr [B], nf_gt [B], and the normalised prediction / target a, b ([2,B,H,W,3]) for the gradient tolerance."""
+    nf_pr [B], nf_gt [B], and the normalised prediction / target a, b ([2,B,H,W,3]) for the gradient tolerance.
+
+    `valid_override` (two bool [B,H,W], the float32-exact masks of exact_truth()) replaces the masks by rank: the loss
+    and the gradients are then taken over it.  Under it a ground-truth point outside the mask is read as (0, 0, 0): an
+    invalid point contributes nothing, and 0 * inf or 0 * NaN must not say otherwise (nan_point, inf_point)."""
     if norm_mode and norm_mode != "avg_dis":
         raise NotImplementedError(norm_mode)
     gts = [gt_pts1.detach().double(), gt_pts2.detach().double()]
@@ -112,6 +119,10 @@ def regr3d_ref(gt_pts1, gt_pts2, pr_pts1, pr_pts2, conf1=None, conf2=None, *, di
         else:
             valid.append(rank_mask(dis) & (c.double() >= CONF_MIN))
             qs.append(thresholds(dis))
+    if valid_override is not None:
+        valid = [torch.as_tensor(m, dtype=torch.bool) for m in valid_override]
+        assert all(m.shape == g.shape[:3] for m, g in zip(valid, gts))
+        gts = [torch.where(m[..., None], g, torch.zeros_like(g)) for m, g in zip(valid, gts)]
     n_valid = torch.stack([m.flatten(1).sum(1) for m in valid])                      # [2,B]
     cnt = n_valid.sum(0).double()
     den = torch.where(cnt > 0, cnt, torch.full_like(cnt, NF_MIN))
@@ -177,10 +188,10 @@ def first_decided_case(B: int, H: int, W: int, start: int = 0, tries: int = 64, 
     raise AssertionError(f"no decided input among seeds {start} .. {start + tries - 1} at {(B, H, W)}")
 
 
-def run_ref(case: dict) -> dict:
+def run_ref(case: dict, valid_override=None) -> dict:
     return regr3d_ref(case["gt_pts1"], case["gt_pts2"], case["pr_pts1"], case["pr_pts2"], case["conf1"], case["conf2"],
                       dist_clip=case["dist_clip"], disable_view1=case["disable_view1"], norm_mode=case["norm_mode"],
-                      gt_scale=case["gt_scale"])
+                      gt_scale=case["gt_scale"], valid_override=valid_override)
 
 
 def grad_tolerance(ref: dict, c: float) -> torch.Tensor:
@@ -194,3 +205,216 @@ def grad_tolerance(ref: dict, c: float) -> torch.Tensor:
     m = want.abs().amax(-1, keepdim=True)
     big = want.abs().flatten(2).amax(2).view(2, -1, 1, 1, 1)
     return ((1e-4 + cancel[..., None]) * m + 1e-6 * big).expand_as(want)
+
+
+# ---- the exact side ------------------------------------------------------------------------------------------------
+# For a ground-truth point on a coordinate axis the kernel's norm chain sqrtf(fmaf(z, z, fmaf(y, y, x * x))) is |c| bit
+# for bit, c the one non-zero coordinate: x * x or the fmaf that meets c forms fl32(c^2), every other step adds an exact
+# 0, and a correctly rounded square root takes fl(c^2) back to |c| away from overflow and underflow (build.py passes no
+# fast-math flag).  The float64 norm of such a point is |c| as well, so on an input that passes is_exact() the oracle and
+# the product see THE SAME norms: ties, thresholds and masks have one truth, in float32, and decided() is not needed.
+# That truth is restated here on the host, in numpy float32, from the contract:
+#     keys: the norms' bit patterns without the sign; NaN orders above +inf (the product's documented deviation from
+#         torch.quantile, which returns NaN for a row that holds one);
+#     rank r = float32(q) * float32(n - 1), weight w = r - floor r, q = aten's lerp of s[floor r], s[ceil r]:
+#         w < 0.5 ? lo + w (hi - lo) : hi - (hi - lo) (1 - w), each multiply-add fused as torch's kernels fuse it;
+#     valid = (dis >= q_lo) & (dis <= q_hi) & (conf >= 3), or dis <= dist_clip.
+# Where the float32 lerp rounds q_lo onto s[floor r_lo] (neighbouring patterns), the floor statistic is valid although
+# rank_mask() drops it: the float32 thresholds are the contract, not the ranks.
+#
+# MUTANTS restate one line each the wrong way; tests/test_regr3d_exact.py asserts that every one of them moves n_valid
+# or the bits of q on a named case of tests/regr3d_cases.py (nf_per_view: the norm factors), except alias_last, which
+# must move nothing.
+MUTANTS = ("lo_strict", "hi_strict", "conf_strict", "clip_strict", "rank_n", "ceil_is_floor", "weight_zero",
+           "lerp_one_sided", "alias_last", "alias_none_low", "nan_low", "nan_poisons", "nf_per_view")
+RADIX_MUTANTS = ("alias_last", "alias_none_low")        # these live in the radix restatement of the select
+RADIX_PASSES = ((31, 20, 2048), (20, 9, 2048), (9, 0, 512))   # (shift of the prefix, shift of the digit, bins)
+_F4, _F8 = np.float32, np.float64
+
+
+def norm32(gt: torch.Tensor) -> np.ndarray:
+    """The kernel's norm chain on the host, float32 [...] of gt [...,3] (float32).  fmaf is formed in float64 -- the
+    product of two float32 is exact there -- and rounded to float32: one rounding wherever the float64 sum is exact,
+    which it is when the addend is 0 (every point on an axis)."""
+    p = gt.detach().cpu().numpy()
+    assert p.dtype == _F4 and p.shape[-1] == 3
+    x, y, z = p[..., 0], p[..., 1], p[..., 2]
+    with np.errstate(all="ignore"):
+        t = x * x
+        t = (y.astype(_F8) * y.astype(_F8) + t.astype(_F8)).astype(_F4)
+        t = (z.astype(_F8) * z.astype(_F8) + t.astype(_F8)).astype(_F4)
+        return np.sqrt(t)
+
+
+def is_exact(gt: torch.Tensor) -> bool:
+    """True when the float64 norm of every point of gt, rounded to float32, is norm32's (NaN equal to NaN): float64
+    and float32 then order, tie and threshold the row alike."""
+    return bool(np.array_equal(_norms(gt).float().numpy(), norm32(gt), equal_nan=True))
+
+
+def keys32(dis32: np.ndarray) -> np.ndarray:
+    return np.ascontiguousarray(dis32, dtype=_F4).view(np.uint32) & np.uint32(0x7FFFFFFF)
+
+
+def ranks32(n: int, mut: str | None = None):
+    """((floor, ceil, weight) of r_lo, the same of r_hi) with the weight as a float32."""
+    m = _F4(n if mut == "rank_n" else n - 1)
+    out = []
+    for q in (Q_LO, Q_HI):
+        r = _F4(q) * m
+        lo = np.floor(r)
+        hi = lo if mut == "ceil_is_floor" else np.ceil(r)
+        out.append((min(int(lo), n - 1), min(int(hi), n - 1), _F4(r - lo)))
+    return tuple(out)
+
+
+def fma32(a, b, c) -> np.ndarray:
+    """fmaf(a, b, c) on float32 arrays, exactly: a b is exact in float64, the float64 sum rounds once more than a fused
+    operation does, and that shows only where the sum lands on the midpoint of two float32 -- there the part the float64
+    sum lost (TwoSum) says which way the one true rounding goes."""
+    a, b, c = (np.asarray(t, dtype=_F4).astype(_F8) for t in (a, b, c))
+    with np.errstate(all="ignore"):
+        p = a * b
+        t = p + c
+        bb = t - p
+        e = (p - (t - bb)) + (c - bb)
+        r = t.astype(_F4)
+        away = np.nextafter(r, np.where(t > r.astype(_F8), _F4(np.inf), _F4(-np.inf)).astype(_F4))
+        tie = np.isfinite(t) & np.isfinite(away) & (r.astype(_F8) != t) & ((r.astype(_F8) + away.astype(_F8)) / 2 == t) & (e != 0)
+        up = np.maximum(r, away)
+        return np.where(tie, np.where(e > 0, up, np.minimum(r, away)), r).astype(_F4)
+
+
+def lerp32(lo: np.ndarray, hi: np.ndarray, w, mut: str | None = None) -> np.ndarray:
+    """aten's lerp (Lerp.h) in float32: w < 0.5 ? lo + w (hi - lo) : hi - (hi - lo) (1 - w), the difference and 1 - w
+    rounded, the multiply-add FUSED -- torch's kernels form it as one fmadd (the vectorised CPU path spells it out;
+    the scalar and device paths get it from the compilers' default contraction)."""
+    lo, hi, w = lo.astype(_F4), hi.astype(_F4), _F4(w)
+    if mut == "weight_zero":
+        return lo
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = hi - lo
+        out = fma32(w, d, lo) if (w < _F4(0.5) or mut == "lerp_one_sided") else fma32(-d, _F4(1.0) - w, hi)
+    assert out.dtype == _F4
+    return out
+
+
+def radix_select32(keys: np.ndarray, wants, mut: str | None = None) -> list:
+    """The product's select on one row of keys, restated: three passes over digits of 11, 11 and 9 bits; in each pass a
+    rank whose prefix an EARLIER rank has reads that rank's counts (`alias`), and only the first rank of a prefix owns a
+    histogram.  Returns the keys at the four wanted ranks.
+
+    alias_last: a rank names the nearest earlier rank with its prefix, not the first, and takes what that one reads.
+        Equal prefixes are transitive, so the chain ends at the first: a no-op (in the kernel a rank that does not own
+        its prefix has an empty histogram, so the pick has to name the first directly; it does).
+    alias_none_low: the ceiling of r_lo, where it shares the floor's prefix, carries on with the floor's rank inside it."""
+    keys = keys.astype(np.int64)
+    prefix, want = [0, 0, 0, 0], [int(w) for w in wants]
+    for p, (pshift, dshift, bins) in enumerate(RADIX_PASSES):
+        alias = []
+        for t in range(4):
+            same = [s for s in range(t) if prefix[s] == prefix[t]]
+            alias.append(t if not same else (same[-1] if mut == "alias_last" else same[0]))
+        hist = {}
+        for t in range(4):
+            if alias[t] == t:
+                sel = keys if p == 0 else keys[(keys >> pshift) == prefix[t]]
+                hist[t] = np.bincount((sel >> dshift) & (bins - 1), minlength=bins)
+        if mut == "alias_none_low" and p > 0 and alias[1] == 0:
+            want[1] = want[0]
+        new_prefix, new_want = [], []
+        for t in range(4):
+            s = t
+            while alias[s] != s:
+                s = alias[s]
+            cum = np.cumsum(hist[s])
+            digit = int(np.searchsorted(cum, want[t], side="right"))
+            assert digit < bins, "the row's counts add up to more than the rank"
+            new_want.append(want[t] - (int(cum[digit - 1]) if digit else 0))
+            new_prefix.append((prefix[t] << (pshift - dshift)) | digit)
+        prefix, want = new_prefix, new_want
+    assert want == [0, 0, 0, 0] or len(set(keys.tolist())) < len(keys)     # what is left is a rank inside a tie
+    return prefix
+
+
+def order_stats32(dis32: np.ndarray, mut: str | None = None, radix: bool = False):
+    """(lo, hi, w) for q_lo and for q_hi of the rows dis32 [R, n]: the float32 order statistics at floor / ceil of the
+    two ranks.  By a sort of the keys, or row by row through radix_select32."""
+    R, n = dis32.shape
+    k = keys32(dis32).astype(np.int64)
+    nan = k > 0x7F800000
+    (l0, l1, lw), (h0, h1, hw) = ranks32(n, mut)
+    if radix:
+        assert mut != "nan_low"
+        picks = np.array([radix_select32(row, (l0, l1, h0, h1), mut) for row in k], dtype=np.int64).reshape(R, 4)
+    else:
+        s = np.sort(np.where(nan, -1, k) if mut == "nan_low" else k, axis=1)
+        picks = s[:, [l0, l1, h0, h1]]
+        picks = np.where(picks < 0, 0x7FC00000, picks)
+    val = picks.astype(np.uint32).view(_F4)
+    return (val[:, 0], val[:, 1], lw), (val[:, 2], val[:, 3], hw), nan.any(axis=1)
+
+
+def thresholds32(dis32: np.ndarray, mut: str | None = None, radix: bool = False) -> np.ndarray:
+    """[R, 2] float32: (q_lo, q_hi) of every row of dis32 [R, n], NaN keys ordered last."""
+    lo, hi, has_nan = order_stats32(np.asarray(dis32), mut, radix)
+    q = np.stack([lerp32(*lo, mut), lerp32(*hi, mut)], axis=1)
+    if mut == "nan_poisons":
+        q[has_nan] = np.nan
+    return q
+
+
+def valid32(dis32: np.ndarray, conf32, q32: np.ndarray, mut: str | None = None) -> np.ndarray:
+    """(dis >= q_lo) & (dis <= q_hi) & (conf >= 3) in float32 for rows dis32 [R, n], q32 [R, 2]; conf32 None: the
+    thresholds are (0, dist_clip) and only dis <= dist_clip is asked."""
+    dis32, q32 = np.asarray(dis32, dtype=_F4), np.asarray(q32, dtype=_F4)
+    with np.errstate(invalid="ignore"):
+        hi = dis32 < q32[:, 1:2] if mut in ("hi_strict", "clip_strict") else dis32 <= q32[:, 1:2]
+        if conf32 is None:
+            return hi
+        lo = dis32 > q32[:, 0:1] if mut == "lo_strict" else dis32 >= q32[:, 0:1]
+        conf32 = np.asarray(conf32, dtype=_F4)
+        return lo & hi & (conf32 > _F4(CONF_MIN) if mut == "conf_strict" else conf32 >= _F4(CONF_MIN))
+
+
+def exact_truth(case: dict, mut: str | None = None, radix: bool = False) -> dict:
+    """The float32-exact q [2,B,2] (numpy float32), valid [2,B,H,W] (torch bool) and n_valid [2,B] (torch int64) of a
+    case whose ground truth passes is_exact()."""
+    qs, valid = [], []
+    for v in (1, 2):
+        gt = case[f"gt_pts{v}"]
+        B, H, W, _ = gt.shape
+        dis = norm32(gt).reshape(B, H * W)
+        if case["dist_clip"] is not None:
+            q = np.tile(np.array([0.0, case["dist_clip"]], dtype=_F4), (B, 1))
+            m = valid32(dis, None, q, mut)
+        else:
+            q = thresholds32(dis, mut, radix)
+            m = valid32(dis, case[f"conf{v}"].numpy().reshape(B, H * W), q, mut)
+        qs.append(q)
+        valid.append(torch.from_numpy(m.reshape(B, H, W)))
+    valid = torch.stack(valid)
+    return {"q": np.stack(qs), "valid": valid, "n_valid": valid.flatten(2).sum(2)}
+
+
+def select_patterns(keys: np.ndarray, n: int):
+    """For one row's keys: which of the four selected ranks (floor, ceil of r_lo; floor, ceil of r_hi) share a prefix
+    after pass 0 (key >> 20), after pass 1 (key >> 9) and at the end (the whole key), each as the kernel's alias
+    pattern -- entry t is the first rank s <= t with an equal prefix.  The last digit separates what pass 1 left
+    together where the third pattern differs from the second."""
+    assert keys.shape == (n,)
+    s = np.sort(keys.astype(np.int64))
+    (l0, l1, _), (h0, h1, _) = ranks32(n)
+    k = s[[l0, l1, h0, h1]]
+    return tuple(tuple(next(a for a in range(t + 1) if k[a] >> sh == k[t] >> sh) for t in range(4)) for sh in (20, 9, 0))
+
+
+def norm_factors64(pts, valid, per_view: bool = False) -> torch.Tensor:
+    """nf of the contract in float64 for two point maps [B,H,W,3] under two masks [B,H,W]: [B] jointly over the views;
+    per_view (the mutant nf_per_view): [2,B], each view over its own valid points."""
+    tot = torch.stack([torch.where(m, torch.linalg.vector_norm(p.double(), dim=-1), torch.zeros(())).flatten(1).sum(1)
+                       for p, m in zip(pts, valid)])
+    cnt = torch.stack([m.flatten(1).sum(1) for m in valid]).double()
+    if not per_view:
+        tot, cnt = tot.sum(0), cnt.sum(0)
+    return (tot / torch.where(cnt > 0, cnt, torch.full_like(cnt, NF_MIN))).clamp(min=NF_MIN)

@@ -175,8 +175,10 @@ def _hold_depth(case, got, yard, truth):
     hold(case + "/d_poses", got[2], yard[2], truth[2], GRAD)
 
 
-@pytest.mark.parametrize("shape", [(2, 768), (2, 1026), (3, 1551), (1, 65536)])
+@pytest.mark.parametrize("shape", [(2, 768), (2, 1026), (3, 1551), (1, 65536), (2049, 5)])
 def test_depth_matches_the_oracle_and_a_strided_misaligned_view(hip_lib, shape):
+    """(2049, 5): one slot per image, 2,049 slots on a grid capped at 2,048 (point_slots.h), so block 0 of the forward
+    and of the backward takes a second trip of its slot loop."""
     N, n = shape
     gen = torch.Generator().manual_seed(N * 7 + n)
     pts, poses, G = _depth_inputs(gen, N, n)
