@@ -1034,6 +1034,60 @@ int spf_posehead_activate_forward(const float* prev, const float* delta, int64_t
 int spf_posehead_activate_backward(const float* pred, const float* d_pred, const float* d_out, int64_t rows,
                                    int32_t trans_act, int32_t quat_act, int32_t fl_act, float* d_delta, void* stream);
 
+/* ---- the encoder front (spfsplatv2_amd/csrc/front.hip) ------------------------------------------------------------------
+ * Image -> tokens: the patch embedding (`nn.Conv2d(C_in, C, P, P)`, `flatten(2).transpose(1, 2)`) as an implicit GEMM on
+ * the float32 matrix instruction, the token rows around the patch rows, and the gradients to every parameter.  float32
+ * only; nothing is allocated or synchronised; no atomics: every sum has one order, two runs agree bitwise.  Argument
+ * errors return SPF_E_INVALID (spf_last_error) before anything is launched. */
+#define SPF_FRONT_MAX_TOKENS 16
+typedef struct SpfFront {
+    const float* image;           /* [B, C_in, gh P, gw P]: unit stride along a row; the base 16-byte aligned for P = 16,
+                                   * 8-byte aligned for P = 14 */
+    const float* affine;          /* NULL, or [2, C_in]: channel c is read as image * affine[c] + affine[C_in + c] */
+    int64_t stride_b, stride_c, stride_y;   /* floats between images, channels and rows: multiples of 4 (P = 16) or 2 */
+    int32_t B, C_in;              /* B gh gw < 2^31; 1 <= C_in <= 32 */
+    int32_t gh, gw;               /* the patch grid */
+    int32_t P;                    /* 14 or 16 */
+    int32_t C;                    /* embed_dim, a multiple of 4 */
+    int32_t before, after;        /* token rows in front of / behind the patch rows of an image of `out` / `dY` */
+} SpfFront;
+typedef struct SpfFrontTokens {
+    const float* tok[SPF_FRONT_MAX_TOKENS];     /* the tensors in front (n_before of them), then those behind: [1, rows, C]
+                                                 * or [S, rows, C], dense, 16-byte aligned.  In the backward call: the
+                                                 * DESTINATION of a broadcast tensor's gradient, NULL where none is wanted */
+    int32_t rows[SPF_FRONT_MAX_TOKENS];         /* >= 1 */
+    int32_t per_image[SPF_FRONT_MAX_TOKENS];    /* 1: [S, rows, C]; 0: broadcast over the sequences */
+    int32_t n_before, n_after;                  /* tensors */
+    int32_t before, after;                      /* rows: the sums of `rows` */
+    const float* pos_first;                     /* NULL, or [C]: added to row 0 (which must be an extra row) */
+} SpfFrontTokens;
+enum { SPF_FRONT_TILE_ROWS = 0, SPF_FRONT_TILE_COLS = 1, SPF_FRONT_CHUNK_ROWS = 2, SPF_FRONT_CHUNKS = 3 };
+/* host only: the rows (patches) and columns (channels) of a block's tile, and for M patch rows the height of a chunk of
+ * the weight gradient and the number of chunks; -1 for another `what` */
+int64_t spf_front_geometry(int32_t what, int64_t M);
+/* host only: floats of the backward's workspace (with_dweight: the chunks' partials of dW; then one [gh gw, C] sum), or
+ * -1 */
+int64_t spf_front_workspace_floats(const SpfFront* args, int32_t with_dweight);
+/* out [B, before + gh gw + after, C] dense: row before + n of image b = bias + weight . patch n (+ pos_table[n]).
+ * weight [C, C_in P P] dense (`proj.weight` in place); bias [C] or NULL; pos_table [gh gw, C] or NULL.  Only the patch
+ * rows are written. */
+int spf_front_embed_forward(const SpfFront* args, const float* weight, const float* bias, const float* pos_table, float* out,
+                            void* stream);
+/* out [S, before + N + after, C] dense.  The extra rows from `tokens`; with `body` (N rows per sequence, row i of all S N
+ * at (i / inner) * outer_stride + (i % inner) * stride floats, multiples of 4) the body's rows too, else they are left
+ * alone.  N >= 0, C a multiple of 4. */
+int spf_front_assemble(const SpfFrontTokens* tokens, const float* body, int64_t inner, int64_t stride, int64_t outer_stride,
+                       int64_t S, int32_t N, int32_t C, float* out, void* stream);
+/* dY: sequence s, row r at s * dy_stride_s + r * dy_stride_r (multiples of 4), unit stride along C.  Writes, for every
+ * broadcast tensor with a destination, the sum over s (ascending) of its rows; d_pos_first [C] (or NULL) likewise from
+ * row 0. */
+int spf_front_tokens_backward(const SpfFrontTokens* tokens, const float* dY, int64_t dy_stride_s, int64_t dy_stride_r,
+                              int64_t S, int32_t N, int32_t C, float* d_pos_first, void* stream);
+/* dweight [C, C_in P P], dbias [C], dpos_table [gh gw, C]: each NULL or written whole.  dY is read at its placed rows
+ * (image b, row before + n).  workspace: spf_front_workspace_floats(args, dweight != NULL) floats, 16-byte aligned. */
+int spf_front_embed_backward(const SpfFront* args, const float* dY, int64_t dy_stride_b, int64_t dy_stride_r,
+                             float* workspace, float* dweight, float* dbias, float* dpos_table, void* stream);
+
 /* Per-stage device timing with HIP events recorded on the launch stream around every kernel
  * stage.  spf_stage_timing_enable(mask) clears the log and starts recording the stages whose bit
  * (1 << SPF_STAGE_x) is set in `mask` (0 = off, -1 = all) (up to

@@ -179,6 +179,22 @@ class SpfPoseEncode(C.Structure):
                 ("homogeneous", C.c_int32), ("beta", C.c_float), ("max_inv_scale", C.c_float), ("min_inv_scale", C.c_float)]
 
 
+FRONT_MAX_TOKENS = 16
+FRONT_TILE_ROWS, FRONT_TILE_COLS, FRONT_CHUNK_ROWS, FRONT_CHUNKS = range(4)
+
+
+class SpfFront(C.Structure):
+    _fields_ = [("image", C.c_void_p), ("affine", C.c_void_p), ("stride_b", C.c_int64), ("stride_c", C.c_int64),
+                ("stride_y", C.c_int64), ("B", C.c_int32), ("C_in", C.c_int32), ("gh", C.c_int32), ("gw", C.c_int32),
+                ("P", C.c_int32), ("C", C.c_int32), ("before", C.c_int32), ("after", C.c_int32)]
+
+
+class SpfFrontTokens(C.Structure):
+    _fields_ = [("tok", C.c_void_p * FRONT_MAX_TOKENS), ("rows", C.c_int32 * FRONT_MAX_TOKENS),
+                ("per_image", C.c_int32 * FRONT_MAX_TOKENS), ("n_before", C.c_int32), ("n_after", C.c_int32),
+                ("before", C.c_int32), ("after", C.c_int32), ("pos_first", C.c_void_p)]
+
+
 # Every symbol include/spfsplat_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "spf_abi_version": (C.c_int, []),
@@ -328,6 +344,15 @@ SYMBOLS = {
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_posehead_activate_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                                  C.c_int32, C.c_void_p, C.c_void_p]),
+    "spf_front_geometry": (C.c_int64, [C.c_int32, C.c_int64]),
+    "spf_front_workspace_floats": (C.c_int64, [C.POINTER(SpfFront), C.c_int32]),
+    "spf_front_embed_forward": (C.c_int, [C.POINTER(SpfFront), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_front_assemble": (C.c_int, [C.POINTER(SpfFrontTokens), C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                     C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "spf_front_tokens_backward": (C.c_int, [C.POINTER(SpfFrontTokens), C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                            C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "spf_front_embed_backward": (C.c_int, [C.POINTER(SpfFront), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_stage_timing_enable": (C.c_int, [C.c_int32]),
     "spf_stage_timing_sample_every": (C.c_int, [C.c_int32]),
     "spf_stage_times_ms": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_int32)]),

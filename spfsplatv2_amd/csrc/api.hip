@@ -1455,6 +1455,104 @@ int spf_dpt_points_backward(const SpfDptPoints* a, const float* dpts3d, const fl
     return SPF_OK;
 }
 
+// ---- the encoder front (front.hip) -------------------------------------------------------------------------------------
+int64_t spf_front_geometry(int32_t what, int64_t M) { return spf::front_geometry(what, M < 0 ? 0 : M); }
+
+static int front_check(const char* what, const SpfFront* a) {
+    if (!a) return fail(SPF_E_INVALID, "%s: args is null", what);
+    if (a->P != 14 && a->P != 16) return fail(SPF_E_INVALID, "%s: the patch size must be 14 or 16 (got %d)", what, a->P);
+    if (a->B < 1 || a->gh < 1 || a->gw < 1 || (int64_t)a->B * a->gh * a->gw > 0x7fffffffLL || (int64_t)a->gw * a->P > 0x7fffffffLL ||
+        (int64_t)a->gh * a->gw > 0x7fffffffLL)
+        return fail(SPF_E_INVALID, "%s: B, gh, gw must be positive and B gh gw < 2^31 (got %d, %d, %d)", what, a->B, a->gh, a->gw);
+    if (a->C_in < 1 || a->C_in > 32) return fail(SPF_E_INVALID, "%s: C_in must be 1 .. 32 (got %d)", what, a->C_in);
+    if (a->C < 4 || a->C % 4 != 0) return fail(SPF_E_INVALID, "%s: C must be a positive multiple of 4 (got %d)", what, a->C);
+    if (a->before < 0 || a->after < 0 || (int64_t)a->before + a->after + (int64_t)a->gh * a->gw > 0x7fffffffLL)
+        return fail(SPF_E_INVALID, "%s: before and after must be >= 0 and the rows of an image < 2^31", what);
+    if (!a->image) return fail(SPF_E_INVALID, "%s: null pointer (image)", what);
+    const int v = a->P == 16 ? 4 : 2;
+    if ((reinterpret_cast<uintptr_t>(a->image) & (4 * v - 1)) != 0 || a->stride_b % v || a->stride_c % v || a->stride_y % v ||
+        a->stride_b < 0 || a->stride_c < 0 || a->stride_y < (int64_t)a->gw * a->P)
+        return fail(SPF_E_INVALID, "%s: the image must be %d-byte aligned with strides that are multiples of %d floats and rows "
+                    "that do not overlap", what, 4 * v, v);
+    if (!aligned<16>({a->affine})) return fail(SPF_E_INVALID, "%s: affine must be 16-byte aligned", what);
+    return SPF_OK;
+}
+
+int64_t spf_front_workspace_floats(const SpfFront* a, int32_t with_dweight) {
+    if (front_check("front_workspace_floats", a)) return -1;
+    return spf::front_workspace_floats(*a, with_dweight != 0);
+}
+
+int spf_front_embed_forward(const SpfFront* a, const float* weight, const float* bias, const float* pos_table, float* out,
+                            void* stream_) {
+    if (const int rc = front_check("front_embed_forward", a)) return rc;
+    if (!weight || !out) return fail(SPF_E_INVALID, "front_embed_forward: null pointer (weight or out)");
+    if (!aligned<16>({weight, bias, pos_table, out})) return fail(SPF_E_INVALID, "front_embed_forward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_front_embed_fwd(*a, weight, bias, pos_table, out, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+static int front_tokens_check(const char* what, const SpfFrontTokens* t, int64_t S, int32_t N, int32_t C, bool sources) {
+    if (!t) return fail(SPF_E_INVALID, "%s: tokens is null", what);
+    if (S < 1 || N < 0 || C < 4 || C % 4 != 0 || S > 0x7fffffffLL)
+        return fail(SPF_E_INVALID, "%s: S must be 1 .. 2^31 - 1, N >= 0, C a positive multiple of 4 (got %lld, %d, %d)", what, (long long)S, N, C);
+    if (t->n_before < 0 || t->n_after < 0 || t->n_before + t->n_after > SPF_FRONT_MAX_TOKENS)
+        return fail(SPF_E_INVALID, "%s: at most %d token tensors (got %d + %d)", what, SPF_FRONT_MAX_TOKENS, t->n_before, t->n_after);
+    int64_t before = 0, after = 0;
+    for (int g = 0; g < t->n_before + t->n_after; ++g) {
+        if (t->rows[g] < 1) return fail(SPF_E_INVALID, "%s: token tensor %d has %d rows", what, g, t->rows[g]);
+        if (sources && !t->tok[g]) return fail(SPF_E_INVALID, "%s: null pointer (token tensor %d)", what, g);
+        if (!aligned<16>({t->tok[g]})) return fail(SPF_E_INVALID, "%s: token tensor %d must be 16-byte aligned", what, g);
+        (g < t->n_before ? before : after) += t->rows[g];
+    }
+    if (before != t->before || after != t->after)
+        return fail(SPF_E_INVALID, "%s: before / after (%d / %d) are not the sums of the tensors' rows (%lld / %lld)", what,
+                    t->before, t->after, (long long)before, (long long)after);
+    if (before + after + N > 0x7fffffffLL || S * (before + after + N) > 0x7fffffffLL)
+        return fail(SPF_E_INVALID, "%s: S (before + N + after) must stay below 2^31", what);
+    if (t->pos_first && t->before < 1) return fail(SPF_E_INVALID, "%s: pos_first without a row in front", what);
+    if (!aligned<16>({t->pos_first})) return fail(SPF_E_INVALID, "%s: pos_first must be 16-byte aligned", what);
+    return SPF_OK;
+}
+
+int spf_front_assemble(const SpfFrontTokens* t, const float* body, int64_t inner, int64_t stride, int64_t outer_stride,
+                       int64_t S, int32_t N, int32_t C, float* out, void* stream_) {
+    if (const int rc = front_tokens_check("front_assemble", t, S, N, C, true)) return rc;
+    if (!out) return fail(SPF_E_INVALID, "front_assemble: null pointer (out)");
+    if (body && (inner < 1 || stride < 0 || outer_stride < 0 || stride % 4 || outer_stride % 4))
+        return fail(SPF_E_INVALID, "front_assemble: the body's rows need inner >= 1 and strides that are multiples of 4 floats");
+    if (!aligned<16>({body, out})) return fail(SPF_E_INVALID, "front_assemble: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_front_assemble(*t, body, inner, stride, outer_stride, S, N, C, out, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+static int front_dy_check(const char* what, const float* dY, int64_t ss, int64_t sr, int32_t C) {
+    if (!dY) return fail(SPF_E_INVALID, "%s: null pointer (dY)", what);
+    if (!aligned<16>({dY}) || ss < 0 || sr < C || ss % 4 || sr % 4)
+        return fail(SPF_E_INVALID, "%s: dY must be 16-byte aligned with strides that are multiples of 4 floats, rows apart", what);
+    return SPF_OK;
+}
+
+int spf_front_tokens_backward(const SpfFrontTokens* t, const float* dY, int64_t dy_stride_s, int64_t dy_stride_r, int64_t S,
+                              int32_t N, int32_t C, float* d_pos_first, void* stream_) {
+    if (const int rc = front_tokens_check("front_tokens_backward", t, S, N, C, false)) return rc;
+    if (const int rc = front_dy_check("front_tokens_backward", dY, dy_stride_s, dy_stride_r, C)) return rc;
+    if (d_pos_first && t->before < 1) return fail(SPF_E_INVALID, "front_tokens_backward: d_pos_first without a row in front");
+    if (!aligned<16>({d_pos_first})) return fail(SPF_E_INVALID, "front_tokens_backward: d_pos_first must be 16-byte aligned");
+    SPF_HIP(spf::launch_front_tokens_bwd(*t, dY, dy_stride_s, dy_stride_r, S, N, C, d_pos_first, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
+int spf_front_embed_backward(const SpfFront* a, const float* dY, int64_t dy_stride_b, int64_t dy_stride_r, float* workspace,
+                             float* dweight, float* dbias, float* dpos_table, void* stream_) {
+    if (const int rc = front_check("front_embed_backward", a)) return rc;
+    if (const int rc = front_dy_check("front_embed_backward", dY, dy_stride_b, dy_stride_r, a->C)) return rc;
+    if (!workspace) return fail(SPF_E_INVALID, "front_embed_backward: null pointer (workspace)");
+    if (!aligned<16>({workspace, dweight, dbias, dpos_table})) return fail(SPF_E_INVALID, "front_embed_backward: tensors must be 16-byte aligned");
+    SPF_HIP(spf::launch_front_embed_bwd(*a, dY, dy_stride_b, dy_stride_r, workspace, dweight, dbias, dpos_table, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
 // ---- the encoder tail (tail.hip) ---------------------------------------------------------------------------------------
 int32_t spf_tail_max_grid(void) { return spf::tail_max_grid(); }
 

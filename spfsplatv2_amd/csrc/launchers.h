@@ -140,4 +140,14 @@ hipError_t launch_posehead_activate_fwd(const float* prev, const float* delta, i
                                         int fl_act, float* pred, float* out, hipStream_t st);
 hipError_t launch_posehead_activate_bwd(const float* pred, const float* d_pred, const float* d_out, int64_t rows,
                                         int trans_act, int quat_act, int fl_act, float* d_delta, hipStream_t st);
+int64_t front_geometry(int what, int64_t M);
+int64_t front_workspace_floats(const SpfFront& a, bool with_dweight);
+hipError_t launch_front_embed_fwd(const SpfFront& a, const float* weight, const float* bias, const float* pos, float* out,
+                                  hipStream_t st);
+hipError_t launch_front_assemble(const SpfFrontTokens& t, const float* body, int64_t inner, int64_t stride,
+                                 int64_t outer_stride, int64_t S, int N, int C, float* out, hipStream_t st);
+hipError_t launch_front_tokens_bwd(const SpfFrontTokens& t, const float* dy, int64_t dy_ss, int64_t dy_sr, int64_t S, int N,
+                                   int C, float* d_pos_first, hipStream_t st);
+hipError_t launch_front_embed_bwd(const SpfFront& a, const float* dy, int64_t dy_sb, int64_t dy_sr, float* ws, float* dweight,
+                                  float* dbias, float* dpos, hipStream_t st);
 }  // namespace spf
