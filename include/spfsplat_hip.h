@@ -1088,6 +1088,31 @@ int spf_front_tokens_backward(const SpfFrontTokens* tokens, const float* dY, int
 int spf_front_embed_backward(const SpfFront* args, const float* dY, int64_t dy_stride_b, int64_t dy_stride_r,
                              float* workspace, float* dweight, float* dbias, float* dpos_table, void* stream);
 
+/* ---- PnP pose from point maps (csrc/pnp.hip): P3P RANSAC and Gauss-Newton refinement, all b v views of a
+ * call in four launches.  Pixel (row i, column j) of view (bi, vi) is the image point (x, y) = (j, i); its three
+ * contiguous floats are at pts3d + bi pts_stride[0] + vi pts_stride[1] + i pts_stride[2] + j pts_stride[3] (floats), its
+ * opacity likewise through opa_stride.  K: [b v, 3, 3] dense, normalised (row 0 is multiplied by w, row 1 by h). */
+typedef struct SpfPnp {
+    const float* pts3d;
+    const float* opacity;
+    const float* K;
+    int64_t pts_stride[4];
+    int64_t opa_stride[4];
+    int32_t b, v, h, w;
+    int32_t iterations;          /* a multiple of 64 in 64..1024 */
+    int32_t refine_steps;        /* 0..64 */
+    uint32_t seed;
+    float opacity_threshold;     /* candidates: opacity > threshold, finite coordinates */
+    float reprojection_error;    /* pixels */
+    int32_t reserved;
+} SpfPnp;
+/* host only: bytes of the workspace for `views` views of h x w pixels, or -1 for sizes spf_pnp_solve refuses */
+int64_t spf_pnp_workspace_bytes(int32_t views, int32_t h, int32_t w, int32_t iterations);
+/* poses [b v, 4, 4]: camera -> world, or the identity for a view that fails.  info [4, b v] int32: final inliers,
+ * candidates n, winning hypothesis (-1 on failure), success.  ranks: NULL, or [b v, iterations, 4] int32, the sample
+ * ranks of every hypothesis (-1: not drawn).  workspace: 16-byte aligned, needs no clearing. */
+int spf_pnp_solve(const SpfPnp* args, void* workspace, float* poses, int32_t* info, int32_t* ranks, void* stream);
+
 /* Per-stage device timing with HIP events recorded on the launch stream around every kernel
  * stage.  spf_stage_timing_enable(mask) clears the log and starts recording the stages whose bit
  * (1 << SPF_STAGE_x) is set in `mask` (0 = off, -1 = all) (up to

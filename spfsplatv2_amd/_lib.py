@@ -195,6 +195,13 @@ class SpfFrontTokens(C.Structure):
                 ("before", C.c_int32), ("after", C.c_int32), ("pos_first", C.c_void_p)]
 
 
+class SpfPnp(C.Structure):
+    _fields_ = [("pts3d", C.c_void_p), ("opacity", C.c_void_p), ("K", C.c_void_p), ("pts_stride", C.c_int64 * 4),
+                ("opa_stride", C.c_int64 * 4), ("b", C.c_int32), ("v", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("iterations", C.c_int32), ("refine_steps", C.c_int32), ("seed", C.c_uint32),
+                ("opacity_threshold", C.c_float), ("reprojection_error", C.c_float), ("reserved", C.c_int32)]
+
+
 # Every symbol include/spfsplat_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "spf_abi_version": (C.c_int, []),
@@ -353,6 +360,8 @@ SYMBOLS = {
                                             C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "spf_front_embed_backward": (C.c_int, [C.POINTER(SpfFront), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spf_pnp_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "spf_pnp_solve": (C.c_int, [C.POINTER(SpfPnp), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spf_stage_timing_enable": (C.c_int, [C.c_int32]),
     "spf_stage_timing_sample_every": (C.c_int, [C.c_int32]),
     "spf_stage_times_ms": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_int32)]),

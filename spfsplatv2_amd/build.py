@@ -18,7 +18,7 @@ CSRC = PKG / "csrc"
 OUT_DIR = PKG / os.environ.get("SPF_LIB_DIR", "_C")      # SPF_LIB_DIR=_C_xyz: a variant build next to the regular one
 LIB = OUT_DIR / "libspfsplat_hip.so"
 SOURCES = ["api.hip", "adapter.hip", "camera.hip", "project.hip", "binning.hip", "render.hip", "rope2d.hip", "loss.hip", "reproj.hip", "regr3d.hip", "pose.hip", "ssim.hip", "lpips.hip", "attention.hip", "attention16.hip", "optim.hip", "block.hip", "dpt.hip", "tail.hip",
-           "posehead.hip", "front.hip"]
+           "posehead.hip", "front.hip", "pnp.hip"]
 HEADERS = [CSRC / "spf_common.h", PKG.parent / "include" / "spfsplat_hip.h", CSRC / "pose_math.h", CSRC / "rope_math.h",
            CSRC / "attention_tiles.h", CSRC / "point_slots.h", CSRC / "adapter_math.h", CSRC / "launchers.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",

@@ -1553,6 +1553,37 @@ int spf_front_embed_backward(const SpfFront* a, const float* dY, int64_t dy_stri
     return SPF_OK;
 }
 
+// ---- PnP pose from point maps (pnp.hip) --------------------------------------------------------------------------------
+// h w < 2^24 keeps every pixel index and count in 32 bits with room to spare; b v is the y extent of the score grid
+static bool pnp_sizes_ok(int64_t views, int32_t h, int32_t w, int32_t iterations) {
+    return views >= 1 && views <= 65535 && h >= 1 && w >= 1 && (int64_t)h * w < ((int64_t)1 << 24) && iterations >= 64 &&
+           iterations <= 1024 && iterations % 64 == 0;
+}
+
+int64_t spf_pnp_workspace_bytes(int32_t views, int32_t h, int32_t w, int32_t iterations) {
+    return pnp_sizes_ok(views, h, w, iterations) ? spf::pnp_workspace_bytes(views, h, w, iterations) : -1;
+}
+
+int spf_pnp_solve(const SpfPnp* a, void* workspace, float* poses, int32_t* info, int32_t* ranks, void* stream_) {
+    if (!a) return fail(SPF_E_INVALID, "pnp_solve: args is null");
+    if (a->b < 1 || a->v < 1) return fail(SPF_E_INVALID, "pnp_solve: b and v must be positive (got %d %d)", a->b, a->v);
+    if (a->iterations < 64 || a->iterations > 1024 || a->iterations % 64 != 0)
+        return fail(SPF_E_INVALID, "pnp_solve: iterations must be a multiple of 64 in 64..1024 (got %d)", a->iterations);
+    if (!pnp_sizes_ok((int64_t)a->b * a->v, a->h, a->w, a->iterations))
+        return fail(SPF_E_INVALID, "pnp_solve: %d x %d views of %d x %d pixels is not a supported size", a->b, a->v, a->h, a->w);
+    if (a->refine_steps < 0 || a->refine_steps > 64)
+        return fail(SPF_E_INVALID, "pnp_solve: refine_steps must be in 0..64 (got %d)", a->refine_steps);
+    if (!(a->reprojection_error > 0.f) || !isfinite(a->reprojection_error) || isnan(a->opacity_threshold))
+        return fail(SPF_E_INVALID, "pnp_solve: reprojection_error must be positive and finite, opacity_threshold a number");
+    if (!a->pts3d || !a->opacity || !a->K || !workspace || !poses || !info) return fail(SPF_E_INVALID, "pnp_solve: null pointer");
+    for (int i = 0; i < 4; ++i)
+        if (a->pts_stride[i] < 0 || a->opa_stride[i] < 0) return fail(SPF_E_INVALID, "pnp_solve: negative strides are not supported");
+    if (!aligned<4>({a->pts3d, a->opacity, a->K, poses, info, ranks})) return fail(SPF_E_INVALID, "pnp_solve: tensors must be 4-byte aligned");
+    if (!aligned<16>({workspace})) return fail(SPF_E_INVALID, "pnp_solve: workspace must be 16-byte aligned");
+    SPF_HIP(spf::launch_pnp_solve(*a, workspace, poses, info, ranks, static_cast<hipStream_t>(stream_)));
+    return SPF_OK;
+}
+
 // ---- the encoder tail (tail.hip) ---------------------------------------------------------------------------------------
 int32_t spf_tail_max_grid(void) { return spf::tail_max_grid(); }
 

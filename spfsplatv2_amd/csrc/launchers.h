@@ -150,4 +150,6 @@ hipError_t launch_front_tokens_bwd(const SpfFrontTokens& t, const float* dy, int
                                    int C, float* d_pos_first, hipStream_t st);
 hipError_t launch_front_embed_bwd(const SpfFront& a, const float* dy, int64_t dy_sb, int64_t dy_sr, float* ws, float* dweight,
                                   float* dbias, float* dpos, hipStream_t st);
+int64_t pnp_workspace_bytes(int views, int h, int w, int iters);
+hipError_t launch_pnp_solve(const SpfPnp& a, void* workspace, float* poses, int32_t* info, int32_t* ranks, hipStream_t stream);
 }  // namespace spf

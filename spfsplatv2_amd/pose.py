@@ -35,7 +35,10 @@ What the reference really does, mirrored here:
 * pose errors are evaluated in float64 and rounded at the store; the reference's float32 ``acos`` loses up to 0.03
   degrees near 0 and 180.
 
-Out of scope: ``get_pnp_pose*`` (cv2 RANSAC), ``update_pose`` / ``SE3_exp``, ``camera_normalization``, and the trivial
+``get_pnp_pose`` and ``get_pnp_pose_batch`` (misc/cam_utils.py:162-253, cv2 RANSAC in the reference) are served by
+``pnp.py``: P3P RANSAC and refinement on the device.
+
+Out of scope: ``update_pose`` / ``SE3_exp``, ``camera_normalization``, and the trivial
 ``convert_focal_to_intrinsics`` / ``normalize_intrinsics`` helpers; ``focal_mode="median"`` raises.
 """
 from __future__ import annotations
