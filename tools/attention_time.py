@@ -25,13 +25,13 @@ Prints one JSON line and writes it to --out.
 from __future__ import annotations
 
 import argparse
-import json
-import statistics
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
+
+import steptime  # noqa: E402
 
 # name: (kind, B, H, Nq, Nk, dtype)
 SHAPES = {
@@ -51,7 +51,6 @@ SHAPES16 = {
 }
 VARIANTS = ("eager", "fused")
 VARIANTS16 = ("eager", "fused", "matrix16", "fused_repeat")
-CACHE_BYTES = 256 << 20
 
 
 def positions(B, N, gen):
@@ -166,50 +165,21 @@ def errors(kind, H, s, results, rows=2):
 def run(name, warmup, iters, shapes=SHAPES, variants=VARIANTS):
     import torch
     kind, B, H, Nq, Nk, dt = shapes[name]
-    dtype = getattr(torch, dt)
     dev = torch.device("cuda")
     gen = torch.Generator().manual_seed(0)
-    one = make_set(kind, B, H, Nq, Nk, dtype, gen, dev)
-    set_bytes = sum(t.numel() * t.element_size() for t in one.values())
-    nsets = max(2, -(-2 * CACHE_BYTES // set_bytes))
-    sets = [one] + [make_set(kind, B, H, Nq, Nk, dtype, gen, dev) for _ in range(nsets - 1)]
-    res = {"shape": name, "kind": kind, "B": B, "H": H, "Nq": Nq, "Nk": Nk, "dtype": dt, "input_sets": nsets,
-           "input_set_bytes": set_bytes, "variants": {}}
-    results = {}
-    times = {var: [] for var in variants}
-    for var in variants:
-        for i in range(warmup):
-            step(var, kind, H, sets[i % nsets], *prepare(kind, sets[i % nsets]))
-    torch.cuda.synchronize()
-    for i in range(iters):                              # the variants alternate, on rotating buffers
-        for vi, var in enumerate(variants):
-            s = sets[(len(variants) * i + vi) % nsets]
-            prepared = prepare(kind, s)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            step(var, kind, H, s, *prepared)
-            del prepared
-            e1.record()
-            e1.synchronize()
-            times[var].append(e0.elapsed_time(e1))
-    for var in variants:
-        prepared = prepare(kind, sets[0])
-        torch.cuda.synchronize()
-        torch.cuda.reset_peak_memory_stats()
-        before = torch.cuda.memory_allocated()
-        results[var] = step(var, kind, H, sets[0], *prepared)
-        del prepared
-        torch.cuda.synchronize()
-        res["variants"][var] = {"ms_median": statistics.median(times[var]), "ms_min": min(times[var]),
-                                "bytes_allocated_peak": torch.cuda.max_memory_allocated() - before,
-                                "iters": iters, "warmup": warmup}
+    sets, set_bytes = steptime.input_sets(lambda: make_set(kind, B, H, Nq, Nk, getattr(torch, dt), gen, dev))
+    res = {"shape": name, "kind": kind, "B": B, "H": H, "Nq": Nq, "Nk": Nk, "dtype": dt, "input_sets": len(sets),
+           "input_set_bytes": set_bytes}
+    steps = {var: (lambda s, leaves, bufs, var=var: step(var, kind, H, s, leaves, bufs)) for var in variants}
+    res["variants"], results = steptime.alternate(variants, steps, sets, warmup, iters, prepare=lambda s: prepare(kind, s))
     res["err_vs_float64"] = errors(kind, H, sets[0], results)
     ms = {var: res["variants"][var]["ms_median"] for var in variants}
     res["speedup_fused_over_eager"] = ms["eager"] / ms["fused"]
     if "matrix16" in ms:
-        res["fused_spread_ms"] = abs(ms["fused"] - ms["fused_repeat"])
-        res["matrix16_gain_over_fused_ms"] = min(ms["fused"], ms["fused_repeat"]) - ms["matrix16"]
-        res["speedup_matrix16_over_fused"] = min(ms["fused"], ms["fused_repeat"]) / ms["matrix16"]
+        spread = steptime.spread_summary(ms["fused"], ms["matrix16"], ms["fused_repeat"])
+        res["fused_spread_ms"] = spread["spread_ms"]
+        res["matrix16_gain_over_fused_ms"] = spread["gain_ms"]
+        res["speedup_matrix16_over_fused"] = spread["speedup"]
         res["speedup_matrix16_over_eager"] = ms["eager"] / ms["matrix16"]
     return res
 
@@ -225,20 +195,11 @@ def main():
     shapes, variants = (SHAPES16, VARIANTS16) if args.matrix16 else (SHAPES, VARIANTS)
     if args.out is None:
         args.out = str(ROOT / "profiles" / ("attention16_time.json" if args.matrix16 else "attention_time.json"))
-    if args.iters < 100 or args.warmup < 20:
-        raise SystemExit("attention_time.py: the median is taken over at least 100 steps after at least 20 warm-ups")
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("attention_time.py needs a GPU")
+    steptime.require_counts("attention_time", args, 100, 20)
+    res = steptime.require_gpu("attention_time")
     names = list(shapes) if args.shapes == "all" else args.shapes.split(",")
-    res = {"tool": "attention_time", "device": torch.cuda.get_device_name(0), "results": []}
-    for n in names:
-        res["results"].append(run(n, args.warmup, args.iters, shapes, variants))
-        print(json.dumps(res["results"][-1]), file=sys.stderr, flush=True)
-    line = json.dumps(res)
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(args.out).write_text(line + "\n")
-    print(line)
+    res["results"] = [steptime.note(run(n, args.warmup, args.iters, shapes, variants)) for n in names]
+    steptime.emit(res, args.out)
 
 
 if __name__ == "__main__":

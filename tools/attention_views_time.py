@@ -25,13 +25,13 @@ step above what was allocated before it.  Prints one JSON line and writes it to 
 from __future__ import annotations
 
 import argparse
-import json
-import statistics
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
+
+import steptime  # noqa: E402
 
 # name: (b, v, num_target)
 SHAPES = {
@@ -88,20 +88,6 @@ def make_set(level, b, v, vs, gen, dev):
     return s
 
 
-def set_bytes(s):
-    import torch
-
-    def walk(o):
-        if isinstance(o, torch.Tensor):
-            return o.numel() * o.element_size()
-        if isinstance(o, dict):
-            return sum(walk(x) for x in o.values())
-        if isinstance(o, (list, tuple)):
-            return sum(walk(x) for x in o)
-        return 0
-    return walk(s)
-
-
 def make_plan(vs, dev):
     """The gather path's index tensors, on the device (made once, outside every timed region)."""
     import torch
@@ -153,42 +139,18 @@ def run(name, level, warmup, iters):
     gen = torch.Generator().manual_seed(0)
     mod = spf.CrossAttention(C_, rope=spf.cuRoPE2D(100.0, 1.0), num_heads=H, qkv_bias=True).to(dev)
     plan = make_plan(vs, dev)
-    one = make_set(level, b, v, vs, gen, dev)
-    nbytes = set_bytes(one)
-    nsets = max(2, -(-ROTATE_BYTES // nbytes) + 1)
-    sets = [one] + [make_set(level, b, v, vs, gen, dev) for _ in range(nsets - 1)]
+    # (one set more than the shared rule asks: the recorded input_sets of this tool count it)
+    sets, nbytes = steptime.input_sets(lambda: make_set(level, b, v, vs, gen, dev), cache_bytes=ROTATE_BYTES // 2, extra=1)
     variants = ("gather", "views", "gather2")
     res = {"shape": name, "level": level, "b": b, "v": v, "num_target": nt, "Vq": v - 1, "Vk": v, "l": L, "C": C_,
-           "heads": H, "dtype": "float32", "calls_of_the_gather_path": len(groups_of(vs.allow)), "input_sets": nsets,
-           "input_set_bytes": nbytes, "variants": {}}
-    times = {var: [] for var in variants}
-    for var in variants[:2]:
-        for i in range(warmup):
-            step(level, var.rstrip("2"), mod, vs, sets[i % nsets], plan)
-    torch.cuda.synchronize()
-    for i in range(iters):                                  # the variants alternate, on rotating input sets
-        for j, var in enumerate(variants):
-            s = sets[(3 * i + j) % nsets]
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            step(level, var.rstrip("2"), mod, vs, s, plan)
-            e1.record()
-            e1.synchronize()
-            times[var].append(e0.elapsed_time(e1))
-    for var in variants:
-        torch.cuda.synchronize()
-        torch.cuda.reset_peak_memory_stats()
-        before = torch.cuda.memory_allocated()
-        step(level, var.rstrip("2"), mod, vs, sets[0], plan)
-        torch.cuda.synchronize()
-        res["variants"][var] = {"ms_median": statistics.median(times[var]), "ms_min": min(times[var]),
-                                "bytes_allocated_peak": torch.cuda.max_memory_allocated() - before,
-                                "iters": iters, "warmup": warmup}
+           "heads": H, "dtype": "float32", "calls_of_the_gather_path": len(groups_of(vs.allow)), "input_sets": len(sets),
+           "input_set_bytes": nbytes}
+    steps = {var: (lambda s, var=var: step(level, var.rstrip("2"), mod, vs, s, plan)) for var in variants}
+    res["variants"], _ = steptime.alternate(variants, steps, sets, warmup, iters, warm=variants[:2])
     ms = {var: res["variants"][var]["ms_median"] for var in variants}
-    res["spread_of_the_gather_path_ms"] = abs(ms["gather"] - ms["gather2"])
-    res["gain_ms"] = min(ms["gather"], ms["gather2"]) - ms["views"]
-    res["speedup_views_over_gather"] = min(ms["gather"], ms["gather2"]) / ms["views"]
-    res["faster_by_more_than_the_spread"] = res["gain_ms"] > res["spread_of_the_gather_path_ms"]
+    spread = steptime.spread_summary(ms["gather"], ms["views"], ms["gather2"])
+    res.update(spread_of_the_gather_path_ms=spread["spread_ms"], gain_ms=spread["gain_ms"],
+               speedup_views_over_gather=spread["speedup"], faster_by_more_than_the_spread=spread["faster_beyond_spread"])
     return res
 
 
@@ -200,23 +162,13 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "attention_views_time.json"))
     args = ap.parse_args()
-    if args.iters < 100 or args.warmup < 20:
-        raise SystemExit("attention_views_time.py: the median is taken over at least 100 steps after at least 20 warm-ups")
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("attention_views_time.py needs a GPU")
+    steptime.require_counts("attention_views_time", args, 100, 20)
+    res = steptime.require_gpu("attention_views_time")
     names = list(SHAPES) if args.shapes == "all" else args.shapes.split(",")
-    res = {"tool": "attention_views_time", "device": torch.cuda.get_device_name(0), "results": []}
-    for n in names:
-        for level in args.levels.split(","):
-            res["results"].append(run(n, level, args.warmup, args.iters))
-            print(json.dumps(res["results"][-1]), file=sys.stderr, flush=True)
-            torch.cuda.empty_cache()
-    line = json.dumps(res)
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(args.out).write_text(line + "\n")
-    print(line)
+    res["results"] = [steptime.note(run(n, level, args.warmup, args.iters)) for n in names for level in args.levels.split(",")]
+    steptime.emit(res, args.out)
 
 
 if __name__ == "__main__":
     main()
+

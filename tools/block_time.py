@@ -15,20 +15,19 @@ A step is the module's forward and the backward of a given upstream gradient to 
 Times: device events around each step, median over --iters (>= 100) after --warmup (>= 20); the tokens rotate over enough
 buffer sets to exceed the 256 MB last-level cache twice, so every step reads cold tokens.  Bytes: the peak of torch's
 allocator during one step above what was allocated before it.  Host syncs: the synchronising calls torch reports during
-one step (torch.cuda.set_sync_debug_mode("warn")).  Prints one JSON line and writes it to --out.
+one step (steptime.count_syncs).  Prints one JSON line and writes it to --out.
 """
 from __future__ import annotations
 
 import argparse
-import json
-import statistics
 import sys
-import warnings
 from functools import partial
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
+
+import steptime  # noqa: E402
 
 # name: (kind, dim, heads, batch, tokens, memory tokens)
 SHAPES = {
@@ -37,7 +36,6 @@ SHAPES = {
     "vggt_1024x16_4x786": ("vggt", 1024, 16, 4, 786, 0),
 }
 VARIANTS = ("baseline", "fused", "baseline_repeat")
-CACHE_BYTES = 256 << 20
 EPS = 1e-6
 
 
@@ -138,54 +136,17 @@ def run(name, warmup, iters):
     mods = {True: build(kind, dim, heads, True).to(dev)}
     mods[False] = build(kind, dim, heads, False).to(dev)
     mods[False].load_state_dict(mods[True].state_dict())                # same names, same weights
-    one = make_set(kind, dim, B, N, M, gen, dev)
-    set_bytes = sum(t.numel() * t.element_size() for t in one.values())
-    nsets = max(2, -(-2 * CACHE_BYTES // set_bytes))
-    sets = [one] + [make_set(kind, dim, B, N, M, gen, dev) for _ in range(nsets - 1)]
-    res = {"shape": name, "kind": kind, "dim": dim, "heads": heads, "B": B, "N": N, "M": M, "input_sets": nsets,
-           "input_set_bytes": set_bytes, "parameters": sum(p.numel() for p in mods[True].parameters()), "variants": {}}
-    times = {var: [] for var in VARIANTS}
-    for var in VARIANTS[:2]:
-        for i in range(warmup):
-            step(kind, var == "fused", mods[var == "fused"], sets[i % nsets])
-    torch.cuda.synchronize()
-    for i in range(iters):                                              # the variants alternate, on rotating buffers
-        for vi, var in enumerate(VARIANTS):
-            s = sets[(len(VARIANTS) * i + vi) % nsets]
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            step(kind, var == "fused", mods[var == "fused"], s)
-            e1.record()
-            e1.synchronize()
-            times[var].append(e0.elapsed_time(e1))
-    results = {}
-    for var in VARIANTS:
-        fused = var == "fused"
-        torch.cuda.synchronize()
-        torch.cuda.reset_peak_memory_stats()
-        before = torch.cuda.memory_allocated()
-        results[var] = step(kind, fused, mods[fused], sets[0])
-        torch.cuda.synchronize()
-        peak = torch.cuda.max_memory_allocated() - before
-        with warnings.catch_warnings(record=True) as caught:
-            warnings.simplefilter("always")
-            torch.cuda.set_sync_debug_mode("warn")
-            try:
-                step(kind, fused, mods[fused], sets[0])
-            finally:
-                torch.cuda.set_sync_debug_mode("default")
-        torch.cuda.synchronize()
-        res["variants"][var] = {"ms_median": statistics.median(times[var]), "ms_min": min(times[var]),
-                                "bytes_allocated_peak": peak,
-                                "host_syncs": sum("synchroniz" in str(w.message).lower() for w in caught),
-                                "iters": iters, "warmup": warmup}
+    sets, set_bytes = steptime.input_sets(lambda: make_set(kind, dim, B, N, M, gen, dev))
+    res = {"shape": name, "kind": kind, "dim": dim, "heads": heads, "B": B, "N": N, "M": M, "input_sets": len(sets),
+           "input_set_bytes": set_bytes, "parameters": sum(p.numel() for p in mods[True].parameters())}
+    steps = {var: (lambda s, fused=var == "fused": step(kind, fused, mods[fused], s)) for var in VARIANTS}
+    res["variants"], results = steptime.alternate(VARIANTS, steps, sets, warmup, iters, warm=VARIANTS[:2], syncs=True)
     # the two paths compute one function: the largest relative difference over the output and every gradient
     (o0, g0), (o1, g1) = results["baseline"], results["fused"]
-    res["max_rel_diff_fused_vs_baseline"] = max(float((a - b).abs().max() / b.abs().max()) for a, b in zip((o1, *g1), (o0, *g0)))
+    res["max_rel_diff_fused_vs_baseline"] = steptime.max_rel_diff((o1, *g1), (o0, *g0))
     ms = {var: res["variants"][var]["ms_median"] for var in VARIANTS}
-    res["baseline_spread_ms"] = abs(ms["baseline"] - ms["baseline_repeat"])
-    res["gain_ms"] = min(ms["baseline"], ms["baseline_repeat"]) - ms["fused"]
-    res["speedup_fused_over_baseline"] = min(ms["baseline"], ms["baseline_repeat"]) / ms["fused"]
+    spread = steptime.spread_summary(ms["baseline"], ms["fused"], ms["baseline_repeat"])
+    res.update(baseline_spread_ms=spread["spread_ms"], gain_ms=spread["gain_ms"], speedup_fused_over_baseline=spread["speedup"])
     return res
 
 
@@ -196,20 +157,11 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "block_time.json"))
     args = ap.parse_args()
-    if args.iters < 100 or args.warmup < 20:
-        raise SystemExit("block_time.py: the median is taken over at least 100 steps after at least 20 warm-ups")
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("block_time.py needs a GPU")
+    steptime.require_counts("block_time", args, 100, 20)
+    res = steptime.require_gpu("block_time")
     names = list(SHAPES) if args.shapes == "all" else args.shapes.split(",")
-    res = {"tool": "block_time", "device": torch.cuda.get_device_name(0), "results": []}
-    for n in names:
-        res["results"].append(run(n, args.warmup, args.iters))
-        print(json.dumps(res["results"][-1]), file=sys.stderr, flush=True)
-    line = json.dumps(res)
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(args.out).write_text(line + "\n")
-    print(line)
+    res["results"] = [steptime.note(run(n, args.warmup, args.iters)) for n in names]
+    steptime.emit(res, args.out)
 
 
 if __name__ == "__main__":

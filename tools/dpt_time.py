@@ -26,13 +26,13 @@ from __future__ import annotations
 
 import argparse
 import copy
-import json
-import statistics
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
+
+import steptime  # noqa: E402
 
 SHAPES = {"pts_256_256x256": "pts", "gs_256_256x256": "gs"}
 VARIANTS = ("baseline", "fused", "baseline_repeat")
@@ -150,54 +150,34 @@ def run(name, B, warmup, iters):
         shape = forward(kind, fused, sets[0]).shape
     dout = torch.randn(shape, generator=gen).to(dev)
     res = {"shape": name, "kind": kind, "B": B, "image": IMAGE, "feature_dim": 256, "output": list(shape),
-           "parameters": sum(p.numel() for p in fused.parameters()), "variants": {}}
-    times = {var: [] for var in VARIANTS}
-    for var in VARIANTS[:2]:
-        for i in range(warmup):
-            step(kind, mods[var], sets[i % 2], dout)
-        torch.cuda.synchronize()
-        print(f"{name}: {var} warm", file=sys.stderr, flush=True)
-    for i in range(iters):                                              # the variants alternate, on rotating inputs
-        for vi, var in enumerate(VARIANTS):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            step(kind, mods[var], sets[(len(VARIANTS) * i + vi) % 2], dout)
-            e1.record()
-            e1.synchronize()
-            times[var].append(e0.elapsed_time(e1))
-        if i % 5 == 4:
-            print(f"{name}: {i + 1} rounds", file=sys.stderr, flush=True)
-    results = {}
-    for var in VARIANTS:
-        torch.cuda.synchronize()
-        torch.cuda.reset_peak_memory_stats()
-        before = torch.cuda.memory_allocated()
-        held = []
-        copies = dict(heads.dense_copies)
-        results[var] = step(kind, mods[var], sets[0], dout, lambda: held.append(torch.cuda.memory_allocated() - before))
-        torch.cuda.synchronize()
-        peak = torch.cuda.max_memory_allocated() - before
-        copies = {k: heads.dense_copies[k] - v for k, v in copies.items()}     # operands the fused calls had to copy
-        res["variants"][var] = {"ms_median": statistics.median(times[var]), "ms_min": min(times[var]),
-                                "bytes_allocated_peak": peak, "bytes_held_after_forward": held[0],
-                                "dense_copies": copies["calls"], "dense_copy_bytes": copies["bytes"], "iters": iters,
-                                "warmup": warmup}
-        results[var] = [t.detach().clone() for t in (results[var][0], *results[var][1])]
+           "parameters": sum(p.numel() for p in fused.parameters())}
+    copied = {}                                     # per variant, the operands its latest step had to copy
+
+    def counted(var):
+        def run_step(s, between=None):
+            before = dict(heads.dense_copies)
+            out, grads = step(kind, mods[var], s, dout, between)
+            copied[var] = {k: heads.dense_copies[k] - v for k, v in before.items()}
+            return [out.detach(), *grads]
+        return run_step
+    res["variants"], results = steptime.alternate(VARIANTS, {var: counted(var) for var in VARIANTS}, sets, warmup, iters,
+                                                  warm=VARIANTS[:2], held=True, label=name)
+    for var, rec in res["variants"].items():        # (the bytes step is a variant's last)
+        rec.update(dense_copies=copied[var]["calls"], dense_copy_bytes=copied[var]["bytes"])
     # the two paths compute one function: the largest relative difference over the output and every gradient, next to
     # the same figure between the two runs of the eager path (what the convolutions' own backward leaves undetermined)
     names = ["out"] + [f"d_tokens[{h}]" for h in (0, 6, 9, 12)] + (["d_img"] if kind == "gs" else [])
     names += ["d_" + n for n, _ in fused.named_parameters() if "refinenet4.resConfUnit1" not in n]
 
     def diffs(a, b):
-        return {n: float((x - y).abs().max() / y.abs().max()) for n, x, y in zip(names, results[a], results[b])}
+        return {n: steptime.rel_diff(x, y) for n, x, y in zip(names, results[a], results[b])}
     for key, d in (("fused_vs_baseline", diffs("fused", "baseline")), ("baseline_repeat_vs_baseline", diffs("baseline_repeat", "baseline"))):
         res["max_rel_diff_" + key] = max(d.values())
         res["rel_diff_out_" + key] = d["out"]
         res["largest_rel_diffs_" + key] = dict(sorted(d.items(), key=lambda kv: -kv[1])[:4])
     ms = {var: res["variants"][var]["ms_median"] for var in VARIANTS}
-    res["baseline_spread_ms"] = abs(ms["baseline"] - ms["baseline_repeat"])
-    res["gain_ms"] = min(ms["baseline"], ms["baseline_repeat"]) - ms["fused"]
-    res["speedup_fused_over_baseline"] = min(ms["baseline"], ms["baseline_repeat"]) / ms["fused"]
+    spread = steptime.spread_summary(ms["baseline"], ms["fused"], ms["baseline_repeat"])
+    res.update(baseline_spread_ms=spread["spread_ms"], gain_ms=spread["gain_ms"], speedup_fused_over_baseline=spread["speedup"])
     res["bytes_held_saved"] = res["variants"]["baseline"]["bytes_held_after_forward"] - res["variants"]["fused"]["bytes_held_after_forward"]
     res["bytes_peak_saved"] = res["variants"]["baseline"]["bytes_allocated_peak"] - res["variants"]["fused"]["bytes_allocated_peak"]
     return res
@@ -211,20 +191,11 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "dpt_time.json"))
     args = ap.parse_args()
-    if args.iters < 10 or args.warmup < 3:
-        raise SystemExit("dpt_time.py: the median is taken over at least 10 steps after at least 3 warm-ups")
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("dpt_time.py needs a GPU")
+    steptime.require_counts("dpt_time", args, 10, 3)
+    res = steptime.require_gpu("dpt_time")
     names = list(SHAPES) if args.shapes == "all" else args.shapes.split(",")
-    res = {"tool": "dpt_time", "device": torch.cuda.get_device_name(0), "results": []}
-    for n in names:
-        res["results"].append(run(n, args.batch, args.warmup, args.iters))
-        print(json.dumps(res["results"][-1]), file=sys.stderr, flush=True)
-    line = json.dumps(res)
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(args.out).write_text(line + "\n")
-    print(line)
+    res["results"] = [steptime.note(run(n, args.batch, args.warmup, args.iters)) for n in names]
+    steptime.emit(res, args.out)
 
 
 if __name__ == "__main__":

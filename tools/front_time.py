@@ -18,22 +18,20 @@ A step is the forward and the backward of a given upstream gradient to every par
 Times: device events around each step, median over --iters after --warmup; the inputs and upstream gradients rotate over
 enough sets to exceed twice the 256 MB last-level cache (cold buffers).  Bytes: the peak of torch's allocator during one
 step above what was allocated before it, and what is still allocated between the forward and the backward.  Host syncs:
-the synchronising calls torch reports during one step (torch.cuda.set_sync_debug_mode("warn")).  Prints one JSON line
+the synchronising calls torch reports during one step (steptime.count_syncs).  Prints one JSON line
 and writes it to --out.
 """
 from __future__ import annotations
 
 import argparse
-import json
-import statistics
 import sys
-import warnings
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
-CACHE_BYTES = 256 << 20
+import steptime  # noqa: E402
+
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 # name: (kind, images or (b, v), H = W or N, patch, C)
 SHAPES = {"croco_256": ("croco", 48, 256, 16, 1024), "assemble": ("assemble", (16, 3), 256, 0, 1024),
@@ -106,64 +104,26 @@ def run(name, warmup, iters):
     dev = torch.device("cuda")
     gen = torch.Generator(dev).manual_seed(0)
     params, one_set, eager, front = make(name, dev, gen)
-    first = one_set()
-    set_bytes = sum(t.numel() * t.element_size() for t in first.values())
-    nsets = max(2, -(-2 * CACHE_BYTES // set_bytes))
-    sets = [first] + [one_set() for _ in range(nsets - 1)]
+    sets, set_bytes = steptime.input_sets(one_set)
     fns = {"eager": eager, "front": front, "eager_repeat": eager}
 
-    def step(var, s, between=None):
-        out, lv = fns[var](s)
-        if between is not None:
-            between()
-        return out, torch.autograd.grad(out, lv, s["up"])
+    def step(var):
+        def run_step(s, between=None):
+            out, lv = fns[var](s)
+            if between is not None:
+                between()
+            return [out.detach(), *torch.autograd.grad(out, lv, s["up"])]
+        return run_step
 
-    for var in VARIANTS[:2]:
-        for i in range(warmup):
-            step(var, sets[i % nsets])
-    torch.cuda.synchronize()
-    times = {var: [] for var in VARIANTS}
-    for i in range(iters):                                                   # the variants alternate, on rotating buffers
-        for vi, var in enumerate(VARIANTS):
-            s = sets[(len(VARIANTS) * i + vi) % nsets]
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            step(var, s)
-            e1.record()
-            e1.synchronize()
-            times[var].append(e0.elapsed_time(e1))
-    res = {"shape": name, "spec": SHAPES[name], "input_sets": nsets, "input_set_bytes": set_bytes,
-           "parameters": sum(p.numel() for p in params.values()), "variants": {}}
-    results = {}
-    for var in VARIANTS:
-        torch.cuda.synchronize()
-        torch.cuda.reset_peak_memory_stats()
-        before = torch.cuda.memory_allocated()
-        held = []
-        out, grads = step(var, sets[0], lambda: held.append(torch.cuda.memory_allocated() - before))
-        torch.cuda.synchronize()
-        peak = torch.cuda.max_memory_allocated() - before
-        results[var] = [out.detach().clone()] + [g.clone() for g in grads]
-        del out, grads
-        with warnings.catch_warnings(record=True) as caught:
-            warnings.simplefilter("always")
-            torch.cuda.set_sync_debug_mode("warn")
-            try:
-                step(var, sets[0])
-            finally:
-                torch.cuda.set_sync_debug_mode("default")
-        torch.cuda.synchronize()
-        res["variants"][var] = {"ms_median": statistics.median(times[var]), "ms_min": min(times[var]), "ms_max": max(times[var]),
-                                "bytes_allocated_peak": peak, "bytes_held_after_forward": held[0],
-                                "host_syncs": sum("synchroniz" in str(w.message).lower() for w in caught),
-                                "iters": iters, "warmup": warmup}
-    rel = lambda x, y: float((x - y).abs().max() / y.abs().max().clamp_min(1e-30))      # noqa: E731
-    res["max_rel_diff_front_vs_eager"] = max(rel(x, y) for x, y in zip(results["front"], results["eager"]))
+    res = {"shape": name, "spec": SHAPES[name], "input_sets": len(sets), "input_set_bytes": set_bytes,
+           "parameters": sum(p.numel() for p in params.values())}
+    res["variants"], results = steptime.alternate(VARIANTS, {var: step(var) for var in VARIANTS}, sets, warmup, iters,
+                                                  warm=VARIANTS[:2], held=True, syncs=True, ms_max=True)
+    res["max_rel_diff_front_vs_eager"] = steptime.max_rel_diff(results["front"], results["eager"])
     ms = {var: res["variants"][var]["ms_median"] for var in VARIANTS}
-    res["eager_spread_ms"] = abs(ms["eager"] - ms["eager_repeat"])
-    res["gain_ms"] = min(ms["eager"], ms["eager_repeat"]) - ms["front"]
-    res["speedup_front_over_eager"] = min(ms["eager"], ms["eager_repeat"]) / ms["front"]
-    res["faster_beyond_spread"] = bool(res["gain_ms"] > res["eager_spread_ms"])
+    spread = steptime.spread_summary(ms["eager"], ms["front"], ms["eager_repeat"])
+    res.update(eager_spread_ms=spread["spread_ms"], gain_ms=spread["gain_ms"], speedup_front_over_eager=spread["speedup"],
+               faster_beyond_spread=spread["faster_beyond_spread"])
     return res
 
 
@@ -174,21 +134,11 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "front_time.json"))
     args = ap.parse_args()
-    if args.iters < 10 or args.warmup < 3:
-        raise SystemExit("front_time.py: the median is taken over at least 10 steps after at least 3 warm-ups")
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("front_time.py needs a GPU")
+    steptime.require_counts("front_time", args, 10, 3)
+    res = steptime.require_gpu("front_time")
     names = list(SHAPES) if args.shapes == "all" else args.shapes.split(",")
-    res = {"tool": "front_time", "device": torch.cuda.get_device_name(0), "results": []}
-    for n in names:
-        res["results"].append(run(n, args.warmup, args.iters))
-        print(json.dumps(res["results"][-1]), file=sys.stderr, flush=True)
-        torch.cuda.empty_cache()
-    line = json.dumps(res)
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(args.out).write_text(line + "\n")
-    print(line)
+    res["results"] = [steptime.note(run(n, args.warmup, args.iters)) for n in names]
+    steptime.emit(res, args.out)
 
 
 if __name__ == "__main__":

@@ -21,33 +21,17 @@ from __future__ import annotations
 import argparse
 import ctypes as C
 import importlib
-import json
-import statistics
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
+import steptime  # noqa: E402
+
 WORKLOADS = {"train": (16, True), "train_10view": (3, True), "test_step": (3, False)}      # pairs, backward
 SIDE = 256
 F32_MATRIX_PEAK = 157.3e12      # FLOP/s, MI355X
-
-
-def _median_ms(fn, warmup, iters):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1))
-    return {"ms_median": statistics.median(times), "ms_min": min(times)}
 
 
 def run(workload, variants, warmup, iters, sd, W):
@@ -79,7 +63,7 @@ def run(workload, variants, warmup, iters, sd, W):
     fns = {"product": product, "eager": eager}
     out = {"workload": workload, "pairs": n, "backward": backward, "variants": {}}
     for var in variants:
-        out["variants"][var] = _median_ms(fns[var], warmup, iters)
+        out["variants"][var] = steptime.median_ms(fns[var], warmup, iters)
     v = out["variants"]
     if "eager" in v and "product" in v:
         out["eager_over_product"] = v["eager"]["ms_median"] / v["product"]["ms_median"]
@@ -108,7 +92,7 @@ def layers(n_img, warmup, iters, W):
             _lib.check(lib.spf_lpips_conv3x3(C.c_void_p(xin.data_ptr()), None, C.c_void_p(wp.data_ptr()),
                                              C.c_void_p(bias.data_ptr()), C.c_void_p(out.data_ptr()), n_img, side, side,
                                              ci, co, 1, stream), "spf_lpips_conv3x3")
-        t = _median_ms(call, warmup, iters)
+        t = steptime.median_ms(call, warmup, iters)
         flop = 2.0 * n_img * side * side * 9 * ci * co
         tf = flop / (t["ms_median"] * 1e-3) / 1e12
         res.append({"layer": l + 1, "side": side, "cin": ci, "cout": co, "images": n_img, "ms_median": t["ms_median"],
@@ -125,22 +109,16 @@ def main():
     ap.add_argument("--no-layers", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("lpips_time.py needs a GPU")
+    steptime.require_counts("lpips_time", args, 2, 0)
+    res = {**steptime.require_gpu("lpips_time"), "warmup": args.warmup, "iters": args.iters}
     from tests import lpips_oracle as lo
     lp = importlib.import_module("spfsplatv2_amd.lpips")
     sd = lo.make_weights(1)
     W = lp.LpipsWeights.from_state_dict(sd)
-    res = {"tool": "lpips_time", "device": torch.cuda.get_device_name(0), "warmup": args.warmup, "iters": args.iters,
-           "results": [run(w, args.variants.split(","), args.warmup, args.iters, sd, W)
-                       for w in args.workloads.split(",") if w]}
+    res["results"] = [run(w, args.variants.split(","), args.warmup, args.iters, sd, W) for w in args.workloads.split(",") if w]
     if not args.no_layers:
         res["conv_layers_forward"] = layers(32, args.warmup, args.iters, W)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        Path(args.out).write_text(line + "\n")
+    steptime.emit(res, args.out)
 
 
 if __name__ == "__main__":

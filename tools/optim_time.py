@@ -15,21 +15,20 @@ above 0.5 (the clip is active) and no element is near the guard's threshold (no 
 Variant a runs twice, before and after b (a, b, a), each on its own copy of the parameters.  Before every step, outside
 the timed span, every parameter gets a fresh clone of its seeded gradient (``zero_grad`` dropped the last one, and the
 eager clip scales gradients in place).  Times are device events around each step (median over --iters >= 100 after
---warmup >= 20), syncs the warnings of ``torch.cuda.set_sync_debug_mode("warn")`` during one step, bytes the peak of
+--warmup >= 20), syncs the warnings of torch's sync debug mode during one step, bytes the peak of
 allocated device memory during one step above what was allocated before it.  Prints one JSON line (and writes it to
 --out, default profiles/optim_time.json).
 """
 from __future__ import annotations
 
 import argparse
-import json
-import statistics
 import sys
-import warnings
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
+
+import steptime  # noqa: E402
 
 GRAD_SIGMA = 1e-4
 LR, BACKBONE_LR_MULTIPLIER = 2e-4, 0.1
@@ -126,36 +125,11 @@ def run(encoder_blocks, decoder_blocks, warmup, iters):
             for p, g in zip(params, seeded):
                 p.grad = g.clone()
 
-        for _ in range(warmup):
-            fresh()
-            step()
-        torch.cuda.synchronize()
-        times = []
-        for _ in range(iters):
-            fresh()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            step()
-            e1.record()
-            e1.synchronize()
-            times.append(e0.elapsed_time(e1))
+        res = steptime.median_ms(step, warmup, iters, before=fresh)
         fresh()
-        torch.cuda.synchronize()
-        base = torch.cuda.memory_allocated()
-        torch.cuda.reset_peak_memory_stats()
-        with warnings.catch_warnings(record=True) as rec:
-            warnings.simplefilter("always")
-            torch.cuda.set_sync_debug_mode("warn")
-            try:
-                max_gradient = step()
-            finally:
-                torch.cuda.set_sync_debug_mode("default")
-        torch.cuda.synchronize()
-        peak = torch.cuda.max_memory_allocated() - base
-        syncs = sum(1 for r in rec if "synchronizing" in str(r.message).lower())      # (not the mode's own notice)
-        ms = statistics.median(times)
-        return {"ms_median": ms, "ms_min": min(times), "syncs_per_step": syncs, "peak_extra_bytes_allocated": int(peak),
-                "tb_per_s_if_32_bytes_per_parameter": 32.0 * numel / ms * 1e-9,
+        (syncs, max_gradient), peak, _ = steptime.peak_step(lambda: steptime.syncs_and_result(step))
+        return {**res, "syncs_per_step": syncs, "peak_extra_bytes_allocated": int(peak),
+                "tb_per_s_if_32_bytes_per_parameter": 32.0 * numel / res["ms_median"] * 1e-9,
                 "max_gradient": float(max_gradient), "iters": iters, "warmup": warmup}
 
     pa, sa = make("a")
@@ -177,18 +151,10 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "optim_time.json"), help="also write the JSON line to this file")
     args = ap.parse_args()
-    if args.iters < 100 or args.warmup < 20:
-        raise SystemExit("optim_time.py: the median is taken over at least 100 steps after at least 20 warm-ups")
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("optim_time.py needs a GPU")
-    res = {"tool": "optim_time", "device": torch.cuda.get_device_name(0),
-           "results": [run(args.encoder_blocks, args.decoder_blocks, args.warmup, args.iters)]}
-    line = json.dumps(res)
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(line + "\n")
-    print(line)
+    steptime.require_counts("optim_time", args, 100, 20)
+    res = steptime.require_gpu("optim_time")
+    res["results"] = [run(args.encoder_blocks, args.decoder_blocks, args.warmup, args.iters)]
+    steptime.emit(res, args.out)
 
 
 if __name__ == "__main__":

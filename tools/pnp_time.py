@@ -7,7 +7,7 @@ tests/pnp_cases.py with 30 % gross outliers and 0.5 px noise, each with its own 
 
 Times: device events around each call, median over --iters after --warmup; the inputs rotate over enough sets to exceed
 twice the 256 MB last-level cache (cold buffers).  Host syncs: the synchronising calls torch reports during one call
-(torch.cuda.set_sync_debug_mode("warn")).  If ``cv2`` can be imported where this runs, the reference's expression is timed
+(steptime.count_syncs).  If ``cv2`` can be imported where this runs, the reference's expression is timed
 on the same inputs as well -- the copy to the host, ``cv2.solvePnPRansac`` with the reference's flags (100 iterations,
 5 px, SOLVEPNP_SQPNP) per view in a Python loop, and the copy back --, wall clock; otherwise the file says that no
 comparison was possible.  There is no speed gate: no baseline exists on this library to regress against.  Prints one
@@ -16,17 +16,16 @@ JSON line and writes it to --out.
 from __future__ import annotations
 
 import argparse
-import json
 import statistics
 import sys
 import time
-import warnings
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
-CACHE_BYTES = 256 << 20
+import steptime  # noqa: E402
+
 SHAPES = ((1, 1, 256, 256), (1, 3, 256, 256), (16, 3, 256, 256))
 DISTINCT_VIEWS = 6                      # planted scenes are built on the host; a set cycles through this many
 
@@ -42,9 +41,8 @@ def make_sets(shape, dev):
     one = {k: torch.from_numpy(np.stack([x[k] for x in pick])).reshape(b, v, *pick[0][k].shape).to(dev)
            for k in ("pts", "opacity", "K")}
     planted = torch.from_numpy(np.stack([x["pose"] for x in pick])).reshape(b, v, 4, 4)
-    set_bytes = sum(t.numel() * t.element_size() for t in one.values())
-    nsets = max(2, -(-2 * CACHE_BYTES // set_bytes))
-    return [one] + [{k: t.clone() for k, t in one.items()} for _ in range(nsets - 1)], set_bytes, planted
+    sets, set_bytes = steptime.input_sets(lambda: {k: t.clone() for k, t in one.items()})
+    return sets, set_bytes, planted
 
 
 def reference_cv2(cv2, s, h, w):
@@ -79,31 +77,12 @@ def run(shape, warmup, iters, cv2):
     b, v, h, w = shape
     sets, set_bytes, planted = make_sets(shape, dev)
     call = lambda s: spf.pnp_poses(s["pts"], s["opacity"], s["K"], h, w)       # noqa: E731
-    for i in range(warmup):
-        call(sets[i % len(sets)])
-    torch.cuda.synchronize()
-    times = []
-    for i in range(iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        res = call(sets[i % len(sets)])
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1))
-    with warnings.catch_warnings(record=True) as caught:
-        warnings.simplefilter("always")
-        torch.cuda.set_sync_debug_mode("warn")
-        try:
-            call(sets[0])
-        finally:
-            torch.cuda.set_sync_debug_mode("default")
-    torch.cuda.synchronize()
+    ms = steptime.median_ms(call, warmup, iters, sets=sets, ms_max=True)
+    syncs, res = steptime.syncs_and_result(lambda: call(sets[0]))          # (every set is a copy of the first)
     poses = res.poses.cpu().double()
     out = {"shape": list(shape), "input_sets": len(sets), "input_set_bytes": set_bytes,
            "workspace_bytes": int(spf._lib.load().spf_pnp_workspace_bytes(b * v, h, w, 128)),
-           "ms_median": statistics.median(times), "ms_min": min(times), "ms_max": max(times), "iters": iters, "warmup": warmup,
-           # (torch's once-per-process notice that the debug mode is a prototype feature names the word too)
-           "host_syncs": sum("synchroniz" in str(x.message).lower() and "prototype" not in str(x.message) for x in caught),
+           **ms, "iters": iters, "warmup": warmup, "host_syncs": syncs,
            "views_succeeded": int(res.success.sum()), "views": b * v,
            "inliers_min_max": [int(res.inliers.min()), int(res.inliers.max())], "candidates": h * w,
            "max_abs_pose_diff_from_planted": float((poses - planted).abs().max())}
@@ -126,27 +105,17 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "pnp_time.json"))
     args = ap.parse_args()
-    if args.iters < 10 or args.warmup < 3:
-        raise SystemExit("pnp_time.py: the median is taken over at least 10 calls after at least 3 warm-ups")
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("pnp_time.py needs a GPU")
+    steptime.require_counts("pnp_time", args, 10, 3)
+    res = steptime.require_gpu("pnp_time")
     try:
         import cv2
     except ImportError:
         cv2 = None
-    res = {"tool": "pnp_time", "device": torch.cuda.get_device_name(0),
-           "comparison": "cv2.solvePnPRansac timed on the same inputs" if cv2 is not None else
-           "none: cv2 cannot be imported here, so the reference's expression was not timed",
-           "kernel_trace": "none taken: the times are whole calls between device events", "results": []}
-    for shape in SHAPES:
-        res["results"].append(run(shape, args.warmup, args.iters, cv2))
-        print(json.dumps(res["results"][-1]), file=sys.stderr, flush=True)
-        torch.cuda.empty_cache()
-    line = json.dumps(res)
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(args.out).write_text(line + "\n")
-    print(line)
+    res.update(comparison="cv2.solvePnPRansac timed on the same inputs" if cv2 is not None else
+               "none: cv2 cannot be imported here, so the reference's expression was not timed",
+               kernel_trace="none taken: the times are whole calls between device events")
+    res["results"] = [steptime.note(run(shape, args.warmup, args.iters, cv2)) for shape in SHAPES]
+    steptime.emit(res, args.out)
 
 
 if __name__ == "__main__":

@@ -10,19 +10,18 @@ makes, model_wrapper.py:337-345) and estimate_intrinsics.  Variants:
      two `if focal <= 0`
   b  the HIP pose path (spfsplatv2_amd.pose)
 Times are device events around each step (median over --iters >= 100 after --warmup >= 20), syncs the warnings of
-torch.cuda.set_sync_debug_mode("warn") during one step.  Prints one JSON line (and writes it to --out).
+torch's sync debug mode during one step.  Prints one JSON line (and writes it to --out).
 """
 from __future__ import annotations
 
 import argparse
-import json
-import statistics
 import sys
-import warnings
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
+
+import steptime  # noqa: E402
 
 
 def make_inputs(b, v, h, w, cv, seed=0):
@@ -65,30 +64,11 @@ def run(shape, cv, variants, warmup, iters):
     out = {"shape": list(shape), "context_views": cv, "variants": {}}
     seen = {}
     for var in variants:
-        for _ in range(warmup):
-            step(var)
-        torch.cuda.synchronize()
-        times = []
-        for _ in range(iters):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            step(var)
-            e1.record()
-            e1.synchronize()
-            times.append(e0.elapsed_time(e1))
-        torch.cuda.synchronize()
-        with warnings.catch_warnings(record=True) as rec:
-            warnings.simplefilter("always")
-            torch.cuda.set_sync_debug_mode("warn")
-            try:
-                poses, depth, errs, K = step(var)
-            finally:
-                torch.cuda.set_sync_debug_mode("default")
-        syncs = sum(1 for r in rec if "synchroniz" in str(r.message).lower())
+        ms = steptime.median_ms(lambda: step(var), warmup, iters)
+        syncs, (poses, depth, errs, K) = steptime.syncs_and_result(lambda: step(var))
         seen[var] = {"focal_scene0": float(K[0, 0, 0]) * h, "error_R_deg": float(errs[1][0]), "error_t_deg": float(errs[1][1]),
                      "depth_mean": float(depth.mean()), "d_enc_abs_max": float(leaf.grad.abs().max())}
-        out["variants"][var] = {"ms_median": statistics.median(times), "ms_min": min(times), "syncs_per_step": syncs,
-                                "iters": iters, "warmup": warmup}
+        out["variants"][var] = {**ms, "syncs_per_step": syncs, "iters": iters, "warmup": warmup}
     out["values_per_variant"] = seen
     t = {k: r["ms_median"] for k, r in out["variants"].items()}
     if "a" in t and "b" in t:
@@ -105,19 +85,11 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
-    if args.iters < 100 or args.warmup < 20:
-        raise SystemExit("pose_time.py: the median is taken over at least 100 steps after at least 20 warm-ups")
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("pose_time.py needs a GPU")
+    steptime.require_counts("pose_time", args, 100, 20)
+    res = steptime.require_gpu("pose_time")
     shape = tuple(int(x) for x in args.shape.split("x"))
-    res = {"tool": "pose_time", "device": torch.cuda.get_device_name(0),
-           "results": [run(shape, args.context_views, args.variants.split(","), args.warmup, args.iters)]}
-    line = json.dumps(res)
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(line + "\n")
-    print(line)
+    res["results"] = [run(shape, args.context_views, args.variants.split(","), args.warmup, args.iters)]
+    steptime.emit(res, args.out)
 
 
 if __name__ == "__main__":

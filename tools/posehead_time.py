@@ -23,15 +23,14 @@ counter pass is taken here.  Prints one JSON line and writes it to --out.
 from __future__ import annotations
 
 import argparse
-import json
-import statistics
 import sys
-import warnings
 from pathlib import Path
 from types import SimpleNamespace
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
+
+import steptime  # noqa: E402
 
 # name: (kind, sizes)
 SHAPES = {"camera_B16_S3": ("camera", dict(B=16, S=3, N=8, dim=2048, heads=16, depth=4, iterations=4)),
@@ -91,59 +90,18 @@ def eager_camera_head(head, tokens, iterations):
 
 
 # ---- measurement -----------------------------------------------------------------------------------------------------
-def timed(fn):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def count_syncs(fn) -> int:
-    import torch
-    torch.cuda.synchronize()
-    with warnings.catch_warnings(record=True) as seen:
-        warnings.simplefilter("always")
-        torch.cuda.set_sync_debug_mode("warn")
-        try:
-            fn()
-        finally:
-            torch.cuda.set_sync_debug_mode("default")
-    return sum("synchroniz" in str(w.message).lower() and "prototype" not in str(w.message) for w in seen)
-
-
 def measure(steps, sets, warmup, iters, label):
-    import torch
-    times = {var: [] for var in VARIANTS}
-    for var in VARIANTS[:2]:
-        for i in range(warmup):
-            steps[var](sets[i % 2])
-        torch.cuda.synchronize()
-        print(f"{label}: {var} warm", file=sys.stderr, flush=True)
-    for i in range(iters):
-        for vi, var in enumerate(VARIANTS):
-            times[var].append(timed(lambda: steps[var](sets[(len(VARIANTS) * i + vi) % 2])))
-    out, results = {}, {}
-    for var in VARIANTS:
-        torch.cuda.synchronize()
-        torch.cuda.reset_peak_memory_stats()
-        before = torch.cuda.memory_allocated()
-        res = steps[var](sets[0])
-        torch.cuda.synchronize()
-        out[var] = {"ms_median": statistics.median(times[var]), "ms_min": min(times[var]), "ms_max": max(times[var]),
-                    "bytes_allocated_peak": torch.cuda.max_memory_allocated() - before, "iters": iters, "warmup": warmup}
-        results[var] = [t.detach().clone() for t in res]
-        del res
-        out[var]["host_syncs_per_step"] = count_syncs(lambda: steps[var](sets[0]))
-    a, b, r = (out[v]["ms_median"] for v in VARIANTS)
-    rel = lambda x, y: float((x - y).abs().max() / y.abs().max().clamp_min(1e-30))
-    return {"variants": out, "baseline_spread_ms": abs(a - r), "gain_ms": min(a, r) - b, "speedup_over_baseline": min(a, r) / b,
-            "faster_beyond_spread": bool(min(a, r) - b > abs(a - r)), "slower_beyond_spread": bool(b - max(a, r) > abs(a - r)),
+    out, results = steptime.alternate(VARIANTS, steps, sets, warmup, iters, warm=VARIANTS[:2], syncs=True, ms_max=True,
+                                      label=label)
+    for rec in out.values():
+        rec["host_syncs_per_step"] = rec.pop("host_syncs")
+    spread = steptime.spread_summary(*(out[v]["ms_median"] for v in ("baseline", "product", "baseline_repeat")))
+    return {"variants": out, "baseline_spread_ms": spread["spread_ms"], "gain_ms": spread["gain_ms"],
+            "speedup_over_baseline": spread["speedup"], "faster_beyond_spread": spread["faster_beyond_spread"],
+            "slower_beyond_spread": spread["slower_beyond_spread"],
             "bytes_peak_saved": out["baseline"]["bytes_allocated_peak"] - out["product"]["bytes_allocated_peak"],
-            "max_rel_diff_product_vs_baseline": max(rel(x, y) for x, y in zip(results["product"], results["baseline"])),
-            "max_rel_diff_repeat_vs_baseline": max(rel(x, y) for x, y in zip(results["baseline_repeat"], results["baseline"]))}
+            "max_rel_diff_product_vs_baseline": steptime.max_rel_diff(results["product"], results["baseline"]),
+            "max_rel_diff_repeat_vs_baseline": steptime.max_rel_diff(results["baseline_repeat"], results["baseline"])}
 
 
 def _grads(outs, wrt):
@@ -207,23 +165,12 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "posehead_time.json"))
     args = ap.parse_args()
-    if args.iters < 10 or args.warmup < 3:
-        raise SystemExit("posehead_time.py: the median is taken over at least 10 steps after at least 3 warm-ups")
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("posehead_time.py needs a GPU")
-    names = list(SHAPES) if args.shapes == "all" else args.shapes.split(",")
-    res = {"tool": "posehead_time", "device": torch.cuda.get_device_name(0), "kernel_trace": "not taken",
-           "counters": "not taken", "results": []}
-    for n in names:
+    steptime.require_counts("posehead_time", args, 10, 3)
+    res = {**steptime.require_gpu("posehead_time"), "kernel_trace": "not taken", "counters": "not taken", "results": []}
+    for n in SHAPES if args.shapes == "all" else args.shapes.split(","):
         kind, s = SHAPES[n]
-        res["results"].append((run_camera if kind == "camera" else run_poses)(n, s, args.warmup, args.iters))
-        print(json.dumps(res["results"][-1]), file=sys.stderr, flush=True)
-        torch.cuda.empty_cache()
-    line = json.dumps(res)
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(args.out).write_text(line + "\n")
-    print(line)
+        res["results"].append(steptime.note((run_camera if kind == "camera" else run_poses)(n, s, args.warmup, args.iters)))
+    steptime.emit(res, args.out)
 
 
 if __name__ == "__main__":

@@ -8,20 +8,19 @@ Variants, per training step (the call of model_wrapper.py:326-329: both predicti
      boolean index-puts of invalid_to_zeros, the boolean gathers of the loss
   b  the HIP loss (spfsplatv2_amd.Regr3D)
 Times are device events around each step (median over --iters >= 100 after --warmup), syncs the warnings of
-torch.cuda.set_sync_debug_mode("warn") during one step.  Prints one JSON line (and writes it to --out).
+torch's sync debug mode during one step.  Prints one JSON line (and writes it to --out).
 """
 from __future__ import annotations
 
 import argparse
-import json
 import math
-import statistics
 import sys
-import warnings
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
+
+import steptime  # noqa: E402
 
 DEFAULT_SHAPES = "16x256x256,3x256x256"
 
@@ -93,29 +92,10 @@ def run(shape, variants, warmup, iters):
     out = {"shape": list(shape), "points": 2 * b * h * w, "variants": {}}
     losses = {}
     for var in variants:
-        for _ in range(warmup):
-            step(var)
-        torch.cuda.synchronize()
-        times = []
-        for _ in range(iters):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            step(var)
-            e1.record()
-            e1.synchronize()
-            times.append(e0.elapsed_time(e1))
-        torch.cuda.synchronize()
-        with warnings.catch_warnings(record=True) as rec:
-            warnings.simplefilter("always")
-            torch.cuda.set_sync_debug_mode("warn")
-            try:
-                loss = step(var)
-            finally:
-                torch.cuda.set_sync_debug_mode("default")
-        syncs = sum(1 for r in rec if "synchroniz" in str(r.message).lower())
+        ms = steptime.median_ms(lambda: step(var), warmup, iters)
+        syncs, loss = steptime.syncs_and_result(lambda: step(var))
         losses[var] = float(loss.detach())
-        out["variants"][var] = {"ms_median": statistics.median(times), "ms_min": min(times), "syncs_per_step": syncs,
-                                "iters": iters, "warmup": warmup}
+        out["variants"][var] = {**ms, "syncs_per_step": syncs, "iters": iters, "warmup": warmup}
     out["loss_per_variant"] = losses
     t = {k: r["ms_median"] for k, r in out["variants"].items()}
     if "a" in t and "b" in t:
@@ -131,19 +111,11 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
-    if args.iters < 100:
-        raise SystemExit("regr3d_time.py: the median is taken over at least 100 steps")
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("regr3d_time.py needs a GPU")
+    steptime.require_counts("regr3d_time", args, 100, 0)
+    res = steptime.require_gpu("regr3d_time")
     shapes = [tuple(int(x) for x in s.split("x")) for s in args.shapes.split(",") if s]
-    res = {"tool": "regr3d_time", "device": torch.cuda.get_device_name(0),
-           "results": [run(s, args.variants.split(","), args.warmup, args.iters) for s in shapes]}
-    line = json.dumps(res)
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(line + "\n")
-    print(line)
+    res["results"] = [run(s, args.variants.split(","), args.warmup, args.iters) for s in shapes]
+    steptime.emit(res, args.out)
 
 
 if __name__ == "__main__":

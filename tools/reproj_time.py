@@ -9,7 +9,7 @@ Variants, per training step (one loss per context view, every input requiring gr
   b  the HIP loss (spfsplatv2_amd.reproj_loss), once per view on pts3d[:, i]
   c  the HIP loss, all views in one call
 Times are device events around each step (median over --iters after --warmup), syncs the warnings of
-torch.cuda.set_sync_debug_mode("warn") during one step.  Prints one JSON line.
+torch's sync debug mode during one step.  Prints one JSON line.
 
 --stats reads a `rocprofv3 --kernel-trace --stats` kernel_stats.csv of a run of ONE shape (e.g. `--variants c
 --shapes re10k`) and prints the HIP kernels' bytes over their mean time: 12 B per point forward (pts3d read), 24 B per
@@ -18,16 +18,14 @@ point backward (pts3d read, dL/dpts3d written); the per-slot partials are < 0.1 
 from __future__ import annotations
 
 import argparse
-import csv
-import json
 import math
-import statistics
 import sys
-import warnings
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
+
+import steptime  # noqa: E402
 
 SHAPES = {"re10k": (16, 2, 256, 256), "re10k_10view": (3, 10, 256, 256)}
 WEIGHT, STEP, TOTAL = 0.001, 30_000, 200_001
@@ -111,29 +109,10 @@ def run(shape, variants, warmup, iters):
     out = {"shape": shape, "b": b, "v": v, "h": h, "w": w, "points": b * v * h * w, "variants": {}}
     losses = {}
     for var in variants:
-        for _ in range(warmup):
-            step(var)
-        torch.cuda.synchronize()
-        times = []
-        for _ in range(iters):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            step(var)
-            e1.record()
-            e1.synchronize()
-            times.append(e0.elapsed_time(e1))
-        torch.cuda.synchronize()
-        with warnings.catch_warnings(record=True) as rec:
-            warnings.simplefilter("always")
-            torch.cuda.set_sync_debug_mode("warn")
-            try:
-                loss = step(var)
-            finally:
-                torch.cuda.set_sync_debug_mode("default")
-        syncs = sum(1 for r in rec if "synchroniz" in str(r.message).lower())
+        ms = steptime.median_ms(lambda: step(var), warmup, iters)
+        syncs, loss = steptime.syncs_and_result(lambda: step(var))
         losses[var] = float(loss)
-        out["variants"][var] = {"ms_median": statistics.median(times), "ms_min": min(times), "syncs_per_step": syncs,
-                                "iters": iters, "warmup": warmup}
+        out["variants"][var] = {**ms, "syncs_per_step": syncs, "iters": iters, "warmup": warmup}
     out["loss_per_variant"] = losses
     t = {k: r["ms_median"] for k, r in out["variants"].items()}
     if "a" in t and "c" in t:
@@ -148,22 +127,9 @@ def kernel_stats(path, shape):
     b, v, h, w = SHAPES[shape]
     pts = b * v * h * w
     need = {"spf_reproj_fwd_kernel": 12 * pts, "spf_reproj_bwd_kernel": 24 * pts}
-    res = {"shape": shape, "points": pts, "kernels": {}}
-    with open(path, newline="") as f:
-        for row in csv.DictReader(f):
-            name = row.get("Name") or row.get("KernelName") or ""
-            avg = float(row.get("AverageNs") or row.get("AverageNs ") or 0)
-            calls = int(float(row.get("Calls") or 0))
-            if "spf_reproj" not in name:
-                continue
-            short = name.split("(")[0].split("<")[0].split("::")[-1].strip()
-            ent = {"calls": calls, "avg_us": avg / 1e3, "name": name[:120]}
-            if short in need and avg > 0:
-                bps = need[short] / (avg * 1e-9)
-                ent.update(bytes=need[short], GBps=bps / 1e9, share_of_peak=bps / HBM_PEAK,
-                           share_of_achievable=bps / HBM_ACHIEVABLE)
-            res["kernels"][name[:120]] = ent
-    return res
+    rates = {"share_of_peak": HBM_PEAK, "share_of_achievable": HBM_ACHIEVABLE}
+    return {"shape": shape, "points": pts,
+            "kernels": steptime.kernel_stats(path, ("spf_reproj",), need, rates, width=120, named=True)}
 
 
 def main():
@@ -177,14 +143,12 @@ def main():
     shapes = [s for s in args.shapes.split(",") if s]
     if args.stats:
         assert len(shapes) == 1, "--stats reads the profile of one shape"
-        print(json.dumps(kernel_stats(args.stats, shapes[0])))
+        steptime.emit(kernel_stats(args.stats, shapes[0]), None)
         return
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("reproj_time.py needs a GPU")
-    res = {"tool": "reproj_time", "device": torch.cuda.get_device_name(0),
-           "results": [run(s, args.variants.split(","), args.warmup, args.iters) for s in shapes]}
-    print(json.dumps(res))
+    steptime.require_counts("reproj_time", args, 2, 0)
+    res = steptime.require_gpu("reproj_time")
+    res["results"] = [run(s, args.variants.split(","), args.warmup, args.iters) for s in shapes]
+    steptime.emit(res, None)
 
 
 if __name__ == "__main__":

@@ -20,9 +20,6 @@ gradients (16 B per element).
 from __future__ import annotations
 
 import argparse
-import csv
-import json
-import statistics
 import sys
 import time
 from pathlib import Path
@@ -30,24 +27,10 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
+import steptime  # noqa: E402
+
 SHAPES = {"headline": (32, 3, 256, 256), "re10k_10view": (30, 3, 256, 256), "test_step": (3, 3, 256, 256)}
 HBM_PEAK = 8.0e12          # B/s, MI355X
-
-
-def _median_ms(fn, warmup, iters):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1))
-    return {"ms_median": statistics.median(times), "ms_min": min(times)}
 
 
 def run(shape, variants, warmup, iters):
@@ -77,9 +60,9 @@ def run(shape, variants, warmup, iters):
     out = {"shape": shape, "nchw": list(SHAPES[shape]), "variants": {}}
     for var in variants:
         f, metric = fns[var]
-        out["variants"][var] = {"forward": _median_ms(lambda: fwd(f), warmup, iters),
-                                "forward_backward": _median_ms(lambda: fwd_bwd(f), warmup, iters),
-                                "compute_ssim": _median_ms(lambda: fwd(lambda a, b: metric()), warmup, iters)}
+        out["variants"][var] = {"forward": steptime.median_ms(lambda: fwd(f), warmup, iters),
+                                "forward_backward": steptime.median_ms(lambda: fwd_bwd(f), warmup, iters),
+                                "compute_ssim": steptime.median_ms(lambda: fwd(lambda a, b: metric()), warmup, iters)}
     v = out["variants"]
     if "eager" in v and "product" in v:
         out["speedup"] = {k: v["eager"][k]["ms_median"] / v["product"][k]["ms_median"] for k in v["eager"]}
@@ -99,20 +82,8 @@ def kernel_stats(path, shape):
     n, c, h, w = SHAPES[shape]
     elems = n * c * h * w
     need = {"spf_ssim_fwd_kernel": 8 * elems, "spf_ssim_bwd_kernel": 16 * elems}
-    res = {"shape": shape, "elements": elems, "kernels": {}}
-    with open(path, newline="") as f:
-        for row in csv.DictReader(f):
-            name = row.get("Name") or row.get("KernelName") or ""
-            if "spf_ssim" not in name and "spf_psnr" not in name:
-                continue
-            avg = float(row.get("AverageNs") or 0)
-            short = name.split("(")[0].split("<")[0].split("::")[-1].strip()
-            ent = {"calls": int(float(row.get("Calls") or 0)), "avg_us": avg / 1e3}
-            if short in need and avg > 0:
-                bps = need[short] / (avg * 1e-9)
-                ent.update(bytes=need[short], GBps=bps / 1e9, share_of_peak=bps / HBM_PEAK)
-            res["kernels"][name[:100]] = ent
-    return res
+    return {"shape": shape, "elements": elems,
+            "kernels": steptime.kernel_stats(path, ("spf_ssim", "spf_psnr"), need, {"share_of_peak": HBM_PEAK}, width=100)}
 
 
 def main():
@@ -127,17 +98,12 @@ def main():
     shapes = [s for s in args.shapes.split(",") if s]
     if args.stats:
         assert len(shapes) == 1, "--stats reads the profile of one shape"
-        print(json.dumps(kernel_stats(args.stats, shapes[0])))
+        steptime.emit(kernel_stats(args.stats, shapes[0]), None)
         return
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("ssim_time.py needs a GPU")
-    res = {"tool": "ssim_time", "device": torch.cuda.get_device_name(0), "warmup": args.warmup, "iters": args.iters,
-           "results": [run(s, args.variants.split(","), args.warmup, args.iters) for s in shapes]}
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        Path(args.out).write_text(line + "\n")
+    steptime.require_counts("ssim_time", args, 2, 0)
+    res = {**steptime.require_gpu("ssim_time"), "warmup": args.warmup, "iters": args.iters}
+    res["results"] = [run(s, args.variants.split(","), args.warmup, args.iters) for s in shapes]
+    steptime.emit(res, args.out)
 
 
 if __name__ == "__main__":

@@ -29,13 +29,13 @@ one JSON line and writes it to --out.
 from __future__ import annotations
 
 import argparse
-import json
-import statistics
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
+
+import steptime  # noqa: E402
 
 # name: (b, v, h, w, synthetic config of the decoder group)
 SHAPES = {"b16_v2_256x256": (16, 2, 256, 256, "REF2V"), "b4_v10_256x256": (4, 10, 256, 256, "REF10V")}
@@ -71,49 +71,17 @@ def tail_gaussians(pts, raw, exponent, split):
     return {k: getattr(g, k) for k in FIELDS + ("harmonics_band4",)}
 
 
-def timed(fn):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
 def measure(variants, steps, sets, warmup, iters, label):
     """``steps[var](set, between=None) -> tensors``; alternates the variants on rotating input sets."""
-    import torch
-    times = {var: [] for var in variants}
-    for var in variants[:2]:
-        for i in range(warmup):
-            steps[var](sets[i % 2])
-        torch.cuda.synchronize()
-        print(f"{label}: {var} warm", file=sys.stderr, flush=True)
-    for i in range(iters):
-        for vi, var in enumerate(variants):
-            times[var].append(timed(lambda: steps[var](sets[(len(variants) * i + vi) % 2])))
-    out, results = {}, {}
-    for var in variants:
-        torch.cuda.synchronize()
-        torch.cuda.reset_peak_memory_stats()
-        before = torch.cuda.memory_allocated()
-        held = []
-        res = steps[var](sets[0], lambda: held.append(torch.cuda.memory_allocated() - before))
-        torch.cuda.synchronize()
-        out[var] = {"ms_median": statistics.median(times[var]), "ms_min": min(times[var]), "ms_max": max(times[var]),
-                    "bytes_allocated_peak": torch.cuda.max_memory_allocated() - before, "bytes_held_after_forward": held[0],
-                    "iters": iters, "warmup": warmup}
-        results[var] = [t.detach().clone() for t in res]
-        del res
-    a, b, r = (out[v]["ms_median"] for v in variants)
-    summary = {"variants": out, "baseline_spread_ms": abs(a - r), "gain_ms": min(a, r) - b,
-               "speedup_over_baseline": min(a, r) / b, "faster_beyond_spread": bool(min(a, r) - b > abs(a - r)),
-               "bytes_peak_saved": out[variants[0]]["bytes_allocated_peak"] - out[variants[1]]["bytes_allocated_peak"]}
-    rel = lambda x, y: float((x - y).abs().max() / y.abs().max().clamp_min(1e-30))
-    summary["max_rel_diff_new_vs_baseline"] = max(rel(x, y) for x, y in zip(results[variants[1]], results[variants[0]]))
-    summary["max_rel_diff_repeat_vs_baseline"] = max(rel(x, y) for x, y in zip(results[variants[2]], results[variants[0]]))
-    return summary
+    out, results = steptime.alternate(variants, steps, sets, warmup, iters, warm=variants[:2], held=True, ms_max=True,
+                                      label=label)
+    base, new, repeat = variants
+    spread = steptime.spread_summary(out[base]["ms_median"], out[new]["ms_median"], out[repeat]["ms_median"])
+    return {"variants": out, "baseline_spread_ms": spread["spread_ms"], "gain_ms": spread["gain_ms"],
+            "speedup_over_baseline": spread["speedup"], "faster_beyond_spread": spread["faster_beyond_spread"],
+            "bytes_peak_saved": out[base]["bytes_allocated_peak"] - out[new]["bytes_allocated_peak"],
+            "max_rel_diff_new_vs_baseline": steptime.max_rel_diff(results[new], results[base]),
+            "max_rel_diff_repeat_vs_baseline": steptime.max_rel_diff(results[repeat], results[base])}
 
 
 def run_tail(name, split, warmup, iters):
@@ -219,26 +187,15 @@ def main():
     ap.add_argument("--decoder-batch", type=int, default=0, help="batch items of the decoder group (0: not run)")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "tail_time.json"))
     args = ap.parse_args()
-    if args.iters < 10 or args.warmup < 3:
-        raise SystemExit("tail_time.py: the median is taken over at least 10 steps after at least 3 warm-ups")
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("tail_time.py needs a GPU")
-    names = list(SHAPES) if args.shapes == "all" else args.shapes.split(",")
-    res = {"tool": "tail_time", "device": torch.cuda.get_device_name(0), "exponent": EXPONENT, "results": [], "decoder": []}
-    for n in names:
+    steptime.require_counts("tail_time", args, 10, 3)
+    res = {**steptime.require_gpu("tail_time"), "exponent": EXPONENT, "results": [], "decoder": []}
+    for n in SHAPES if args.shapes == "all" else args.shapes.split(","):
         for split in (True, False):
-            res["results"].append(run_tail(n, split, args.warmup, args.iters))
-            print(json.dumps(res["results"][-1]), file=sys.stderr, flush=True)
-            torch.cuda.empty_cache()
+            res["results"].append(steptime.note(run_tail(n, split, args.warmup, args.iters)))
         if args.decoder_batch > 0:
-            res["decoder"].append(run_decoder(n, min(args.decoder_batch, SHAPES[n][0]), args.warmup, args.iters))
-            print(json.dumps(res["decoder"][-1]), file=sys.stderr, flush=True)
-            torch.cuda.empty_cache()
-    line = json.dumps(res)
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(args.out).write_text(line + "\n")
-    print(line)
+            nb = min(args.decoder_batch, SHAPES[n][0])
+            res["decoder"].append(steptime.note(run_decoder(n, nb, args.warmup, args.iters)))
+    steptime.emit(res, args.out)
 
 
 if __name__ == "__main__":

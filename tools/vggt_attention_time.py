@@ -18,15 +18,14 @@ what was allocated before it.  Prints one JSON line and writes it to --out.
 from __future__ import annotations
 
 import argparse
-import json
-import statistics
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
-from tools.attention_time import CACHE_BYTES, positions  # noqa: E402
+import steptime  # noqa: E402
+from attention_time import positions  # noqa: E402
 
 # name: (B, H, views S, tokens per view P, mask)
 SHAPES = {
@@ -69,10 +68,7 @@ def run(name, warmup, iters):
     N = S * P
     dev = torch.device("cuda")
     gen = torch.Generator().manual_seed(0)
-    one = make_set(B, H, N, gen, dev)
-    set_bytes = sum(t.numel() * t.element_size() for t in one.values())
-    nsets = max(2, -(-2 * CACHE_BYTES // set_bytes))
-    sets = [one] + [make_set(B, H, N, gen, dev) for _ in range(nsets - 1)]
+    sets, set_bytes = steptime.input_sets(lambda: make_set(B, H, N, gen, dev))
     mask = view_mask(S, P, 1).to(dev) if masked else None
     params = [(1.0 + 0.3 * torch.randn(64, generator=gen)).to(dev).requires_grad_(True),
               (0.1 * torch.randn(64, generator=gen)).to(dev).requires_grad_(True),
@@ -83,42 +79,15 @@ def run(name, warmup, iters):
         leaf = s["qkv"].detach().requires_grad_(True)
         return leaf, leaf * 1
 
-    res = {"shape": name, "B": B, "H": H, "N": N, "mask": masked, "norm": True, "dtype": "float32", "input_sets": nsets,
-           "input_set_bytes": set_bytes, "variants": {}}
-    times = {"eager": [], "fused": []}
-    for var in times:
-        for i in range(warmup):
-            step(var, H, sets[i % nsets], mask, params, *prepare(sets[i % nsets]))
-    torch.cuda.synchronize()
-    for i in range(iters):                              # the two variants alternate, on rotating buffers
-        for var in times:
-            s = sets[(2 * i + (var == "fused")) % nsets]
-            prepared = prepare(s)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            step(var, H, s, mask, params, *prepared)
-            del prepared
-            e1.record()
-            e1.synchronize()
-            times[var].append(e0.elapsed_time(e1))
-    results = {}
-    for var in times:
-        prepared = prepare(sets[0])
-        torch.cuda.synchronize()
-        torch.cuda.reset_peak_memory_stats()
-        before = torch.cuda.memory_allocated()
-        results[var] = step(var, H, sets[0], mask, params, *prepared)
-        del prepared
-        torch.cuda.synchronize()
-        res["variants"][var] = {"ms_median": statistics.median(times[var]), "ms_min": min(times[var]),
-                                "bytes_allocated_peak": torch.cuda.max_memory_allocated() - before,
-                                "iters": iters, "warmup": warmup}
+    res = {"shape": name, "B": B, "H": H, "N": N, "mask": masked, "norm": True, "dtype": "float32", "input_sets": len(sets),
+           "input_set_bytes": set_bytes}
+    variants = ("eager", "fused")
+    steps = {var: (lambda s, leaf, qkv, var=var: step(var, H, s, mask, params, leaf, qkv)) for var in variants}
+    res["variants"], results = steptime.alternate(variants, steps, sets, warmup, iters, prepare=prepare)
     # the two variants against each other (not an accuracy figure: the gate's figures are the tests')
-    o_e, g_e = results["eager"]
-    o_f, g_f = results["fused"]
-    rel = lambda a, b: float((a - b).abs().max() / b.abs().max())
-    res["fused_vs_eager_max_rel"] = {"out": rel(o_f, o_e), "dqkv": rel(g_f[0], g_e[0]),
-                                     "dparams": max(rel(a, b) for a, b in zip(g_f[1:], g_e[1:]))}
+    (o_e, g_e), (o_f, g_f) = results["eager"], results["fused"]
+    res["fused_vs_eager_max_rel"] = {"out": steptime.rel_diff(o_f, o_e), "dqkv": steptime.rel_diff(g_f[0], g_e[0]),
+                                     "dparams": steptime.max_rel_diff(g_f[1:], g_e[1:])}
     res["speedup_fused_over_eager"] = res["variants"]["eager"]["ms_median"] / res["variants"]["fused"]["ms_median"]
     return res
 
@@ -130,20 +99,11 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "vggt_attention_time.json"))
     args = ap.parse_args()
-    if args.iters < 100 or args.warmup < 20:
-        raise SystemExit("vggt_attention_time.py: the median is taken over at least 100 steps after at least 20 warm-ups")
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("vggt_attention_time.py needs a GPU")
+    steptime.require_counts("vggt_attention_time", args, 100, 20)
+    res = steptime.require_gpu("vggt_attention_time")
     names = list(SHAPES) if args.shapes == "all" else args.shapes.split(",")
-    res = {"tool": "vggt_attention_time", "device": torch.cuda.get_device_name(0), "results": []}
-    for n in names:
-        res["results"].append(run(n, args.warmup, args.iters))
-        print(json.dumps(res["results"][-1]), file=sys.stderr, flush=True)
-    line = json.dumps(res)
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(args.out).write_text(line + "\n")
-    print(line)
+    res["results"] = [steptime.note(run(n, args.warmup, args.iters)) for n in names]
+    steptime.emit(res, args.out)
 
 
 if __name__ == "__main__":
